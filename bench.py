@@ -19,7 +19,23 @@ scaling.
   5  2,000 rooms x 5 participants, VP9/AV1 SVC with dependency descriptors
      + Opus DTX, congestion-driven layer drops (the serial SVC decide path)
 
-Prints ONE JSON line (rank 0).
+--steps N beyond ROUND_STEPS runs in rounds (see main): each round starts a
+fresh engine, forwards the --warmup batches untimed and times its share of the
+N steps on the batches that follow, so every timed step is a batch the engine
+has not seen, in steady state, and the inputs held in HBM stay bounded;
+`ms_per_step` is the rounds' timed time over N.  An engine made later in a
+process can get hardware queues on which decide and emit overlap less; main's
+next_engine says what was measured and how the rounds are kept on engines like
+the first.  The line's `round_ms_per_step` gives the fastest and slowest round,
+`rounds_uneven` (and a warning) marks a line whose rounds differ by over 15 %,
+and LKF_HOST_PROF=1 prints each round's time.
+
+A plain run sets up, warms up, times the steps and prints ONE JSON line
+(rank 0).  --full adds what takes work of its own after the timed region: the
+CPU baseline (--no-cpu-baseline leaves it out) and the parity gate against the
+CPU oracle (--no-parity); without --full the line's `cpu_baseline`, `parity`
+and `parity_gate` are null.  --dump-outputs DIR writes the last timed step's
+output (dump_outputs below).
 """
 import argparse
 import ctypes as C
@@ -363,6 +379,45 @@ def parity_gate(eng, pkg, config, room_ids, nb, batch_s, ingress, trace, threads
     return res
 
 
+ROUND_STEPS = 64  # timed steps per round (main): the distinct batches held in HBM beyond the warmup's
+DUMP_RECORDS = 1 << 18  # --dump-outputs: sampled output records (x 9 float64 columns, 19 MB)
+DUMP_CHUNKS, DUMP_CHUNK = 1 << 12, 1 << 11  # --dump-outputs: sampled runs of wire bytes (float32, 34 MB)
+
+
+def dump_outputs(dirpath, recs, arena, suffix=""):
+    """--dump-outputs: what a caller of the timed path receives for its last
+    step (lkf_drain: the output records and the wire bytes they point into) as
+    float .npy files, every value exact, under 64 MB in all:
+      out_totals.npy       float64 [2]: records, wire bytes
+      out_records.npy      float64 [k, 9]: OUT_DTYPE's fields in order, of all
+                           records or, beyond DUMP_RECORDS of them, of those
+                           at out_records_idx
+      out_records_idx.npy  float64 [k]: their positions, ascending
+      out_bytes.npy        float32: all wire bytes [1, n] or, beyond DUMP_CHUNKS
+                           x DUMP_CHUNK of them, [DUMP_CHUNKS, DUMP_CHUNK]: the
+                           runs of bytes that start at out_bytes_idx
+      out_bytes_idx.npy    float64: the runs' first positions, ascending
+    The sample is seeded: two builds given the same arguments dump the same
+    positions."""
+    os.makedirs(dirpath, exist_ok=True)
+
+    def save(name, a):
+        np.save(os.path.join(dirpath, name + suffix + ".npy"), a)
+
+    rng = np.random.default_rng(20240521)
+    ri = np.arange(len(recs)) if len(recs) <= DUMP_RECORDS else np.sort(rng.integers(0, len(recs), DUMP_RECORDS))
+    if len(arena) <= DUMP_CHUNKS * DUMP_CHUNK:
+        bi, run = np.zeros(1, dtype=np.int64), len(arena)
+    else:
+        bi, run = np.sort(rng.integers(0, len(arena) - DUMP_CHUNK + 1, DUMP_CHUNKS)), DUMP_CHUNK
+    r = recs[ri]
+    save("out_totals", np.array([len(recs), len(arena)], dtype=np.float64))
+    save("out_records", np.stack([r[f].astype(np.float64) for f in recs.dtype.names], axis=1))
+    save("out_records_idx", ri.astype(np.float64))
+    save("out_bytes", arena[bi[:, None] + np.arange(run)].astype(np.float32))
+    save("out_bytes_idx", bi.astype(np.float64))
+
+
 def launch_ranks(n):
     """`bench.py --gpus N` without a torch.distributed launcher: start N fresh
     child processes of this script, one per GPU, with RANK / LOCAL_RANK /
@@ -434,6 +489,7 @@ def kernel_sources_sha():
 
 
 def main():
+    t_start = time.perf_counter()
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=30)
@@ -442,7 +498,13 @@ def main():
                     help="BASELINE.json configs[N-1] (2 = configs[1], the headline)")
     ap.add_argument("--rooms", type=int, default=0, help="rooms per GPU (0: the config's)")
     ap.add_argument("--batch-s", type=float, default=1.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also run the CPU baseline and the parity gate against the CPU "
+                         "oracle (a plain run times the steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write the last timed step's output records and wire bytes (a seeded sample when large) "
+                         "as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--cpu-threads", type=int, default=0)
     # HBM traffic per launch from the committed rocprofv3 --pmc FETCH_SIZE/WRITE_SIZE
     # summary of this same workload (scripts/gpu_pmc.sh -> profiles/)
@@ -465,8 +527,8 @@ def main():
                     help="deployment shape: the stream allocator's AllocateOptimal for this many video DownTracks "
                          "after every step's run (a control-rate call: it waits for the queued runs)")
     ap.add_argument("--no-parity", action="store_true",
-                    help="skip the parity gate (the CPU oracle over the same rooms and batches, compared after "
-                         "the timed region: counters, every Forwarder state, RTPStatsSender, RTPStatsReceiver)")
+                    help="with --full: skip the parity gate (the CPU oracle over the same rooms and batches, compared "
+                         "after the timed region: counters, every Forwarder state, RTPStatsSender, RTPStatsReceiver)")
     ap.add_argument("--srtp-profile", choices=["aes_cm", "gcm"], default="aes_cm",
                     help="with --srtp: SRTP_AES128_CM_HMAC_SHA1_80 or SRTP_AEAD_AES_128_GCM transports")
     ap.add_argument("--dist-backend", choices=["nccl", "gloo"], default="nccl",
@@ -518,7 +580,17 @@ def main():
     pkg = importlib.import_module("livekit-server_amd")
     wl = importlib.import_module("livekit-server_amd.workload")
 
-    nb = args.warmup + args.steps
+    # The timed steps run in rounds of at most ROUND_STEPS: every round starts
+    # a fresh engine, forwards the W warmup batches (untimed) and then times
+    # its share of the steps on the batches that follow, so that the distinct
+    # batches resident in HBM, and the time and host memory that generating
+    # them takes, do not grow with --steps.  Up to ROUND_STEPS steps there is
+    # one round.  The larger rounds come last: the last round runs the whole
+    # trace (nb batches), and is what --full's parity gate and --dump-outputs
+    # look at.
+    rounds = max(1, -(-args.steps // ROUND_STEPS))
+    ks = [args.steps // rounds] * (rounds - args.steps % rounds) + [args.steps // rounds + 1] * (args.steps % rounds)
+    nb = args.warmup + ks[-1]
     # rooms -> ranks: LPT bin packing by expected tuples per batch (SURVEY.md
     # §8(e)); configs[1]'s rooms are all the same shape, so every rank gets
     # args.rooms of them
@@ -531,27 +603,32 @@ def main():
     lib = os.environ.get("LKF_LIB") or None
     if lib and os.sep not in lib:  # a name: one of the in-tree builds
         lib = os.path.join(ROOT, "livekit-server_amd", "lib", lib)
-    if dry:  # (test infrastructure: the oracle behind Engine's bench-facing methods)
-        eng = importlib.import_module("tests.dryrun_engine").DryRunEngine.for_trace(trace)
-    else:
-        eng = pkg.Engine.for_trace(trace, device=local, lib_path=lib)
-    wl.load_topology(eng.api, eng.h, trace)
 
-    if args.ingress:
-        wl.load_streams(eng.api, eng.h, trace)
-    if args.srtp:  # one transport per (room, subscriber), seeded master keys
-        rng = np.random.default_rng(1234)
-        tps = {}
-        for d in range(trace.ndts):
-            k = (int(trace.tracks[trace.downtracks[d].track].room), int(trace.downtracks[d].subscriber))
-            if k not in tps:
-                gcm = args.srtp_profile == "gcm"
-                tps[k] = eng.api["add_transport"](eng.h, C.byref(pkg.transport_params(
-                    rng.integers(0, 256, 16, dtype=np.uint8).tobytes(),
-                    rng.integers(0, 256, 12 if gcm else 14, dtype=np.uint8).tobytes(),
-                    pkg.abi.LKF_SRTP_AEAD_AES_128_GCM if gcm else pkg.abi.LKF_SRTP_AES128_CM_HMAC_SHA1_80)))
-                assert tps[k] >= 0
-            assert eng.api["set_downtrack_transport"](eng.h, d, tps[k]) == 0
+    def new_engine():
+        """A fresh engine with the trace's topology (one per round)."""
+        if dry:  # (test infrastructure: the oracle behind Engine's bench-facing methods)
+            eng = importlib.import_module("tests.dryrun_engine").DryRunEngine.for_trace(trace)
+        else:
+            eng = pkg.Engine.for_trace(trace, device=local, lib_path=lib)
+        wl.load_topology(eng.api, eng.h, trace)
+        if args.ingress:
+            wl.load_streams(eng.api, eng.h, trace)
+        if args.srtp:  # one transport per (room, subscriber), seeded master keys
+            rng = np.random.default_rng(1234)
+            tps = {}
+            for d in range(trace.ndts):
+                k = (int(trace.tracks[trace.downtracks[d].track].room), int(trace.downtracks[d].subscriber))
+                if k not in tps:
+                    gcm = args.srtp_profile == "gcm"
+                    tps[k] = eng.api["add_transport"](eng.h, C.byref(pkg.transport_params(
+                        rng.integers(0, 256, 16, dtype=np.uint8).tobytes(),
+                        rng.integers(0, 256, 12 if gcm else 14, dtype=np.uint8).tobytes(),
+                        pkg.abi.LKF_SRTP_AEAD_AES_128_GCM if gcm else pkg.abi.LKF_SRTP_AES128_CM_HMAC_SHA1_80)))
+                    assert tps[k] >= 0
+                assert eng.api["set_downtrack_transport"](eng.h, d, tps[k]) == 0
+        return eng
+
+    eng = new_engine()
 
     # inputs resident in HBM before the timed region (--host-io: in pinned host memory)
     dpk, dar, meta, ddd = [], [], [], []
@@ -567,8 +644,8 @@ def main():
         if args.host_io:
             tp = tp.pin_memory()
         ta = torch.zeros(alen + 64, dtype=torch.uint8, device=hdev, pin_memory=args.host_io)
-        if alen:
-            ta[:alen].copy_(torch.frombuffer(bytearray(C.string_at(ar, alen)), dtype=torch.uint8))
+        if alen:  # (copied straight from the trace's arena: 0.3 GB per configs[1] batch)
+            ta[:alen].copy_(torch.from_numpy(np.ctypeslib.as_array(ar, shape=(alen,))))
         dpk.append(tp)
         dar.append(ta)
         meta.append((n, alen))
@@ -674,8 +751,8 @@ def main():
                                    axis=1).reshape(-1, 3, 4)
         aout = np.zeros(args.alloc_per_step, dtype=pkg.abi.ALLOCATION_DTYPE)
 
-    def step(b):
-        ta = time.perf_counter()
+    def feed(eng, b):
+        """Batch b's control ops and input into `eng` -> the host times around the submit."""
         wl.queue_events(eng.api, eng.h, trace, b)
         tb = time.perf_counter()
         n, alen = meta[b]
@@ -687,7 +764,39 @@ def main():
             eng.submit_device(C.c_void_p(dpk[b].data_ptr()), n, C.c_void_p(dar[b].data_ptr()), alen)
             if has_dd:
                 assert eng.api["submit_dd_device"](eng.h, C.c_void_p(ddd[b].data_ptr()), n) == 0
-        tc = time.perf_counter()
+        return tb, time.perf_counter()
+
+    def next_engine(old, first):
+        """The next round's engine (untimed).  Which hardware queues the HIP
+        runtime gives an engine's six streams depends on the streams created
+        and destroyed in the process before it, and the decide / emit overlap
+        on the queues: measured on an MI355X (configs[1], 64-step rounds), an
+        engine created after its predecessor was destroyed runs every round at
+        1.00-1.04 ms/step where the first engine runs at 0.71-0.75; with the
+        engines kept alive the second is slow (0.91-0.94) and the third fast
+        again; with a standing engine, and each engine created before its
+        predecessor is destroyed, fast and slow engines alternate strictly
+        (0.70-0.72 / 1.00-1.02, seven rounds, twice).  So this keeps a standing
+        engine (made before the second round, never run) and between rounds
+        makes a spare engine, runs one batch through its streams and drops it,
+        which puts every round on a fast engine as the first is.  The line's
+        `round_ms_per_step` shows whether that held."""
+        if first:
+            standing.append(new_engine())
+        else:
+            spare = new_engine()
+            old.close()
+            feed(spare, 0)
+            spare.run(sp)
+            spare.sync()
+            old = spare
+        eng = new_engine()
+        old.close()
+        return eng
+
+    def step(b):
+        ta = time.perf_counter()
+        tb, tc = feed(eng, b)
         eng.run(sp)
         if speakers and not tick_on and not dry:  # Room.audioUpdateWorker's tick (ranking stays in HBM; N > 1: summary_tick)
             assert eng.api["speakers_enqueue"](eng.h, 1700000000 * 10**9 + int((b + 1) * args.batch_s * 1e9)) == 0
@@ -711,40 +820,69 @@ def main():
             hprof[1] += tc - tb
             hprof[2] += td - tc
 
-    for b in range(args.warmup):
-        step(b)
-    csync()
-    eng.sync()
-    warm_cum = eng.cumulative(reset=True)
-    if dist:
-        dist.barrier()
-    csync()
-    t0 = time.perf_counter()
-    for b in range(args.warmup, nb):
-        step(b)
-    if args.host_io:
-        drain_prev(0)  # the last batch's output reaches host memory inside the timed region
-        eng.drain_wait()
-    t_host = time.perf_counter() - t0  # host time to enqueue the K steps (control ops, submit, lkf_run)
+    def add_cum(a, c):
+        if a is None:
+            return c
+        out = {k: a[k] + c[k] for k in ("tuples", "forwarded", "out_bytes", "arena_bytes")}
+        out["drops"] = [x + y for x, y in zip(a["drops"], c["drops"])]
+        return out
+
+    # elapsed, t_host, the HIP-event sums and cum_all add up over the rounds;
+    # warm_cum and cum are the last round's (the parity gate's)
+    elapsed = t_host = dec_ms = emit_ms = tot_ms = prot_ms = 0.0
+    cum_all = None
+    standing, round_ms = [], []
+    for r, k_r in enumerate(ks):
+        tr0 = time.perf_counter()
+        if r:
+            eng = next_engine(eng, r == 1)
+        tr1 = time.perf_counter()
+        for b in range(args.warmup):
+            step(b)
+        csync()
+        eng.sync()
+        warm_cum = eng.cumulative(reset=True)
+        if dist:
+            dist.barrier()
+        csync()
+        t0 = time.perf_counter()
+        for b in range(args.warmup, args.warmup + k_r):
+            step(b)
+        if args.host_io:
+            drain_prev(0)  # the last batch's output reaches host memory inside the timed region
+            eng.drain_wait()
+        t_host += time.perf_counter() - t0  # host time to enqueue the steps (control ops, submit, lkf_run)
+        csync()
+        if dist:
+            dist.barrier()
+        t1 = time.perf_counter()
+        eng.sync()
+        elapsed += t1 - t0
+        round_ms.append(1e3 * (t1 - t0) / k_r)
+        cum = eng.cumulative()
+        tr2 = time.perf_counter()
+        cum_all = add_cum(cum_all, cum)
+        # HIP-event window: the round's k_r timed runs (the engine keeps the last 256 runs' events)
+        d_, e_, t_ = eng.timing_window(k_r)
+        dec_ms, emit_ms, tot_ms = dec_ms + d_, emit_ms + e_, tot_ms + t_
+        if args.srtp:
+            pm = C.c_float()
+            assert eng.lib.lkf_protect_timing_window(C.c_void_p(eng.h), k_r, C.byref(pm)) == 0
+            prot_ms += pm.value
+        if hprof is not None:
+            print("round %d: engine %.3f s, warmup %.3f s, %d steps %.4f ms/step, counters %.3f s, events %.3f s" %
+                  (r, tr1 - tr0, t0 - tr1, k_r, 1e3 * (t1 - t0) / k_r, tr2 - t1, time.perf_counter() - tr2),
+                  file=sys.stderr)
     if hprof is not None:
         print("host ms/step (incl. warmup): queue_events %.4f submit %.4f run %.4f" %
-              tuple(1e3 * x / nb for x in hprof), file=sys.stderr)
-    csync()
-    if dist:
-        dist.barrier()
-    t1 = time.perf_counter()
-    eng.sync()
-    elapsed = t1 - t0
-    cum = eng.cumulative()
-    # HIP-event window: the engine keeps the last 256 runs' events; longer runs
-    # time the last `win` steps and scale the sums to all K steps (steady state)
-    win = min(args.steps, 250)
-    dec_ms, emit_ms, tot_ms = (v * args.steps / win for v in eng.timing_window(win))
-    prot_ms = 0.0
-    if args.srtp:
-        pm = C.c_float()
-        assert eng.lib.lkf_protect_timing_window(C.c_void_p(eng.h), win, C.byref(pm)) == 0
-        prot_ms = pm.value * args.steps / win
+              tuple(1e3 * x / (args.steps + rounds * args.warmup) for x in hprof), file=sys.stderr)
+    # (after the timed region; every rank writes its own rooms' output.  lkf_drain
+    # waits for the engine and copies the last run's records and wire bytes out of
+    # its batch context; neither it nor --host-io's lkf_drain_run_async consumes
+    # them, so it may follow that drain of the same batch)
+    if args.dump_outputs:
+        recs, arena = pkg.drain_arrays(eng.api, eng.h)
+        dump_outputs(args.dump_outputs, recs, arena, "_rank%d" % rank if rank else "")
     coll = None
     if dist or tick_on:
         # the per-room speaker and per-subscriber bandwidth
@@ -787,7 +925,7 @@ def main():
                         "their enqueue"}
 
     cpu = None
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         # the GPU box gives one GPU a 16-CPU share (os.cpu_count() is the whole
         # host); at N > 1 every rank runs its share at once (N x 16 threads on
         # the node, the memory system shared as the GPUs' hosts would share it)
@@ -829,7 +967,7 @@ def main():
         cpu["thread_scaling_eff"] = round(v_all / (v1 * used * world), 3) if v1 else None
 
     parity = None
-    if not args.no_parity and not args.srtp and not args.alloc_per_step:
+    if args.full and not args.no_parity and not args.srtp and not args.alloc_per_step:
         # (outside the timed region; every rank checks its own rooms)
         thr = args.cpu_threads or min(16, os.cpu_count() or 1)
         parity = parity_gate(eng, pkg, args.config, plan[rank], nb, args.batch_s, args.ingress, trace, thr,
@@ -838,10 +976,13 @@ def main():
             ok = torch.tensor([1.0 if parity["parity"] else 0.0], dtype=torch.float64, device=cdev)
             dist.all_reduce(ok, op=dist.ReduceOp.MIN)
             parity["parity_all_ranks"] = bool(ok.item() > 0)
+    cum = cum_all  # (from here on: every round's timed steps)
     fwd = cum["forwarded"]
-    steps_pkts = sum(meta[b][0] for b in range(args.warmup, nb))
-    algo, b_in, b_ing = algorithmic_bytes(trace, range(args.warmup, nb), fwd, cum["out_bytes"], trace.ndts,
-                                          ingress=args.ingress)
+    steps_pkts = sum(meta[args.warmup + i][0] for k_r in ks for i in range(k_r))
+    algo, b_in, b_ing = cum["out_bytes"] + 32 * fwd, 0, 0
+    for k_r in sorted(set(ks)):  # (the rounds have at most two lengths)
+        part = algorithmic_bytes(trace, range(args.warmup, args.warmup + k_r), 0, 0, trace.ndts, ingress=args.ingress)
+        algo, b_in, b_ing = (x + ks.count(k_r) * y for x, y in zip((algo, b_in, b_ing), part))
     payload_in = b_in - 64 * steps_pkts
     # per-kernel algorithmic bytes (the two halves of SURVEY.md §8(d)'s B):
     #   decide: packet descriptors once + sequencer record per forwarded tuple + DT hot state
@@ -898,6 +1039,8 @@ def main():
             "unit": "forwarded RTP pkts/s",
             "n_gpus": world,
             "steps": args.steps,
+            "rounds": rounds,
+            "round_ms_per_step": {"min": round(min(round_ms), 4), "max": round(max(round_ms), 4)},
             "warmup": args.warmup,
             "ms_per_step": round(ms_step, 4),
             "higher_is_better": True,
@@ -939,7 +1082,7 @@ def main():
             line["note"] = ("launcher rehearsal: the CPU oracle stood in for the engine (tests/dryrun_engine.py); "
                             "not a measurement")
         if args.host_io:  # PCIe-inclusive deployment shape (never the headline value)
-            h2d = sum(meta[b][0] * 64 + meta[b][1] for b in range(args.warmup, nb))
+            h2d = sum(meta[args.warmup + i][0] * 64 + meta[args.warmup + i][1] for k_r in ks for i in range(k_r))
             line["host_io"] = {"h2d_bytes_per_step": h2d // args.steps,
                                "d2h_bytes_per_step": (drained[0] * 40 + drained[1]) // args.steps,
                                "drained_records": drained[0], "records_forwarded": fwd,
@@ -957,8 +1100,21 @@ def main():
             line["control"] = {"alloc_optimal_per_step": args.alloc_per_step,
                                "note": "lkf_allocate_optimal after every run: waits for the queued runs (no overlap "
                                        "across that step boundary)"}
+        # two guards on a run of many rounds: its rounds must agree (a round
+        # on a slow engine, see next_engine, is 40 % off; rounds on like engines
+        # stay within 5 %), and what it spends outside its steps is bounded
+        if max(round_ms) > 1.15 * min(round_ms):
+            line["rounds_uneven"] = True
+            print("bench: WARNING: the rounds disagree (%.4f .. %.4f ms/step): ms_per_step and value are not the "
+                  "steady state's" % (min(round_ms), max(round_ms)), file=sys.stderr)
+        line["outside_steps_s"] = round(time.perf_counter() - t_start - elapsed, 1)
+        if line["outside_steps_s"] > 30:
+            print("bench: WARNING: %.1f s outside the timed steps (setup, and per round a new engine and the warmup)"
+                  % line["outside_steps_s"], file=sys.stderr)
         print(json.dumps(line))
     eng.close()
+    for e in standing:
+        e.close()
     if dist:
         dist.destroy_process_group()
 

@@ -12,7 +12,7 @@ rc=$?
 echo "pytest rc=$rc"; tail -5 $OUT/pytest_gpu.log
 if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then exit $rc; fi
 if [ "${RUN_BENCH:-1}" = "1" ]; then
-  timeout -k 10 ${BENCH_TIMEOUT:-600} python bench.py ${BENCH_ARGS:---steps 5 --warmup 1} > $OUT/bench.log 2>&1
+  timeout -k 10 ${BENCH_TIMEOUT:-600} python bench.py --full ${BENCH_ARGS:---steps 5 --warmup 1} > $OUT/bench.log 2>&1
   brc=$?
   echo "bench rc=$brc"; tail -3 $OUT/bench.log
   exit $brc

@@ -34,7 +34,7 @@ for item in "${LIST[@]}"; do
     python3 -c "import json,sys; d=json.load(open('$O/${ROUND:-r5}_pmc_$name.json')); print('$name hbm_bytes_per_step', d.get('hbm_bytes_per_step'))"
   fi
   if [ "${BENCH:-1}" = "1" ]; then
-    timeout -k 10 600 python3 bench.py $args --steps ${STEPS:-20} --warmup 5 ${BENCH_EXTRA:-} > $O/bench_$name.log 2>&1
+    timeout -k 10 600 python3 bench.py --full $args --steps ${STEPS:-20} --warmup 5 ${BENCH_EXTRA:-} > $O/bench_$name.log 2>&1
     rc=$?; echo "$name bench rc=$rc"; [ $rc -eq 0 ] || { tail -5 $O/bench_$name.log; exit $rc; }
     grep '^{' $O/bench_$name.log | tail -1 > $O/bench_$name.json; cut -c1-300 $O/bench_$name.json
   fi

@@ -6,7 +6,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 export TMPDIR=/tmp
 O=gpurun_out/paritydbg; mkdir -p $O
 for k in ${PD_STEPS:-1 3 7 20}; do
-  timeout -k 10 300 python3 bench.py --steps $k --warmup 5 --no-cpu-baseline ${PD_ARGS:-} > $O/steps$k.log 2>&1
+  timeout -k 10 300 python3 bench.py --full --steps $k --warmup 5 --no-cpu-baseline ${PD_ARGS:-} > $O/steps$k.log 2>&1
   rc=$?; echo "steps $k rc=$rc"; [ $rc -eq 0 ] || { tail -5 $O/steps$k.log; exit $rc; }
   python3 - $O/steps$k.log <<'PY'
 import json, sys

@@ -16,7 +16,7 @@ if [ -n "${R6_BENCH:-}" ]; then
   IFS='|' read -ra LIST <<< "$R6_BENCH"
   i=0
   for a in "${LIST[@]}"; do
-    timeout -k 10 ${BENCH_TIMEOUT:-400} python3 bench.py $a > $O/bench_$i.log 2>&1
+    timeout -k 10 ${BENCH_TIMEOUT:-400} python3 bench.py --full $a > $O/bench_$i.log 2>&1
     rc=$?; echo "bench $i rc=$rc: $a"
     [ $rc -eq 0 ] || { tail -8 $O/bench_$i.log; exit $rc; }
     grep '^{' $O/bench_$i.log | tail -1 > $O/bench_$i.json

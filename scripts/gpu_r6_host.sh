@@ -11,7 +11,7 @@ O=gpurun_out/${OUT_NAME:-r6host}
 mkdir -p $O
 for sh in "hostprof:" "hostio:--host-io" "hostio_ingress:--host-io --config 3 --rooms 125"; do
   name=${sh%%:*}; args=${sh#*:}
-  LKF_HOST_PROF=1 timeout -k 10 300 python3 bench.py $args --steps 20 --warmup 5 --no-cpu-baseline > $O/$name.log 2>&1
+  LKF_HOST_PROF=1 timeout -k 10 300 python3 bench.py --full $args --steps 20 --warmup 5 --no-cpu-baseline > $O/$name.log 2>&1
   rc=$?; echo "$name rc=$rc"; [ $rc -eq 0 ] || { tail -5 $O/$name.log; exit $rc; }
   grep '^{' $O/$name.log | tail -1 > $O/$name.json
   grep -E "host ms|lkf host" $O/$name.log

@@ -33,7 +33,7 @@ def test_library_exports_every_declared_symbol(pkg):
     C.CDLL(lib)
 
 
-def test_struct_sizes(abi):
+def test_struct_sizes(abi, tmp_path):
     assert C.sizeof(abi.lkf_pkt) == 64
     assert C.sizeof(abi.lkf_out) == 40
     src = r'''
@@ -44,7 +44,7 @@ int main(void){printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %
  sizeof(lkf_downtrack_params), sizeof(lkf_pkt), sizeof(lkf_out), sizeof(lkf_fwd_state), sizeof(lkf_seq_meta),
  sizeof(lkf_pkt_dd), sizeof(lkf_stream_params), sizeof(lkf_dt_summary), sizeof(lkf_transport_params), sizeof(lkf_video_transition), sizeof(lkf_sender_stats), sizeof(lkf_prov_req), sizeof(lkf_prov_result), sizeof(lkf_alloc_group), sizeof(lkf_dd_tracker_status));return 0;}
 '''
-    exe = "/tmp/lkf_sizes"
+    exe = str(tmp_path / "lkf_sizes")
     with open(exe + ".c", "w") as f:
         f.write(src)
     subprocess.run(["gcc", "-I", ROOT, "-o", exe, exe + ".c"], check=True)

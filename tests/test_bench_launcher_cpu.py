@@ -32,7 +32,7 @@ def _bench(*args, timeout=300):
 
 @pytest.mark.parametrize("config,rooms", [(1, 1), (3, 1)])
 def test_launcher_two_ranks_matches_one_process(config, rooms):
-    common = ["--dry-run", "--config", str(config), "--steps", "2", "--warmup", "1", "--cpu-threads", "2"]
+    common = ["--dry-run", "--full", "--config", str(config), "--steps", "2", "--warmup", "1", "--cpu-threads", "2"]
     two = _bench("--gpus", "2", "--rooms", str(rooms), *common)
     one = _bench("--gpus", "1", "--rooms", str(2 * rooms), "--no-cpu-baseline", *common)
     assert two["n_gpus"] == 2 and one["n_gpus"] == 1
@@ -49,6 +49,85 @@ def test_launcher_two_ranks_matches_one_process(config, rooms):
         assert c["rooms_with_speakers"] > 0
     cb = two["cpu_baseline"]
     assert cb["cores"] % 2 == 0 and cb["value"] > 0 and cb["per_rank_value"] > 0  # (threads used x 2 ranks)
+
+
+def test_plain_run_dumps_last_step(tmp_path):
+    """A plain run (no --full) leaves the CPU baseline and the parity gate out
+    and, with --dump-outputs, writes the last timed step's records and wire
+    bytes as float arrays, the same from run to run (here from the dry-run
+    engine, which has the engine's drain call)."""
+    import numpy as np
+    args = ["--dry-run", "--gpus", "1", "--config", "1", "--steps", "2", "--warmup", "1"]
+    a = _bench(*args, "--dump-outputs", str(tmp_path / "a"))
+    b = _bench(*args, "--dump-outputs", str(tmp_path / "b"))
+    assert a["steps"] == 2 and a["ms_per_step"] > 0
+    assert a["cpu_baseline"] is None and a["parity"] is None and a["parity_gate"] is None
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["out_bytes.npy", "out_bytes_idx.npy", "out_records.npy", "out_records_idx.npy",
+                     "out_totals.npy"]
+    arrs = {n: np.load(tmp_path / "a" / n) for n in names}
+    for n in names:
+        assert arrs[n].dtype in (np.float32, np.float64), n
+        assert np.array_equal(arrs[n], np.load(tmp_path / "b" / n)), n
+    assert sum(x.nbytes for x in arrs.values()) <= 64 << 20
+    nrec, nbytes = (int(x) for x in arrs["out_totals.npy"])
+    assert 0 < nrec <= a["forwarded_total"]
+    rec = arrs["out_records.npy"]
+    assert rec.shape == (nrec, 9) and arrs["out_bytes.npy"].shape == (1, nbytes)
+    assert 0 < (rec[:, 2] + rec[:, 5]).max() <= nbytes  # every record's out_off + out_len lies in the wire bytes
+
+
+def test_steps_beyond_one_round_run_in_rounds():
+    """--steps beyond bench.ROUND_STEPS (64) runs in rounds, each on a fresh
+    engine over the same warmup batches and the timed batches after them: 65
+    steps are a round of 32 and one of 33 (the uneven split), and forward what
+    a 32-step run and a 33-step run forward together, with their tuples and
+    bytes.  The parity gate checks the last, longer round."""
+    args = ["--dry-run", "--full", "--no-cpu-baseline", "--gpus", "1", "--config", "1", "--warmup", "2"]
+    a, b = _bench(*args, "--steps", "32"), _bench(*args, "--steps", "33")
+    two = _bench(*args, "--steps", "65")
+    assert (a["rounds"], b["rounds"], two["steps"], two["rounds"]) == (1, 1, 65, 2)
+    assert two["forwarded_total"] == a["forwarded_total"] + b["forwarded_total"] > 0
+    # exact where the three runs see the same input: tuples, and the decide kernel's bytes (packet descriptors,
+    # forwarded tuples, DownTracks); the payload bytes of the 32-step run's last batch are those of a trace that
+    # ends one second sooner, so the totals may differ by less than one step's bytes
+    tup, dec, byt = ([f(x) * x["steps"] for x in (a, b, two)] for f in (
+        lambda x: x["tuples_per_step"], lambda x: x["roofline"]["kernels"][0]["algorithmic_bytes_per_launch"],
+        lambda x: x["roofline"]["algorithmic_bytes_per_step"]))
+    assert tup[2] == tup[0] + tup[1] and dec[2] == dec[0] + dec[1]
+    assert abs(byt[2] - byt[0] - byt[1]) < a["roofline"]["algorithmic_bytes_per_step"]
+    assert a["parity"] is True and b["parity"] is True and two["parity"] is True
+    assert two["parity_gate"]["batches"] == 35 and two["parity_gate"]["forwarded_total"] == \
+        b["parity_gate"]["forwarded_total"]
+    assert set(two["round_ms_per_step"]) == {"min", "max"} and two["outside_steps_s"] >= 0
+
+
+def test_dump_outputs_samples_large_output(tmp_path, abi, monkeypatch):
+    """Beyond its caps --dump-outputs keeps a seeded sample: the records at
+    out_records_idx and the runs of wire bytes that start at out_bytes_idx."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(bench, "DUMP_RECORDS", 100)
+    monkeypatch.setattr(bench, "DUMP_CHUNKS", 8)
+    monkeypatch.setattr(bench, "DUMP_CHUNK", 16)
+    recs = np.zeros(1000, dtype=abi.OUT_DTYPE)
+    recs["ext_sn"] = (1 << 40) + np.arange(1000)
+    recs["layer"] = -1
+    arena = (np.arange(10000) % 251).astype(np.uint8)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), recs, arena)
+    got = {n[:-4]: np.load(tmp_path / "a" / n) for n in os.listdir(tmp_path / "a")}
+    for n, a in got.items():
+        assert np.array_equal(a, np.load(tmp_path / "b" / (n + ".npy"))), n
+    assert got["out_totals"].tolist() == [1000.0, 10000.0]
+    ri, bi = got["out_records_idx"].astype(np.int64), got["out_bytes_idx"].astype(np.int64)
+    assert ri.shape == (100,) and np.all(np.diff(ri) >= 0) and 0 <= ri.min() and ri.max() < 1000
+    assert got["out_records"].shape == (100, 9)
+    assert np.array_equal(got["out_records"][:, 0], (1 << 40) + ri) and np.all(got["out_records"][:, 7] == -1)
+    assert bi.shape == (8,) and 0 <= bi.min() and bi.max() + 16 <= 10000
+    assert got["out_bytes"].dtype == np.float32
+    assert np.array_equal(got["out_bytes"], (bi[:, None] + np.arange(16)) % 251)
 
 
 def test_tick_times():
