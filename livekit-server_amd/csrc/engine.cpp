@@ -10,10 +10,15 @@
 // high-priority decide stream after the caller's stream (which orders the
 // batch's inputs); its "emit" stage (k_emit, counters) runs on a low-priority
 // emit stream after an event.  The decide of batch n+1 depends only on decide
-// n (DownTrack state), so it overlaps emit n.  Per-batch scratch and outputs are double-buffered by run
-// parity: batch n's outputs stay valid until run n+2 is enqueued, and a
-// device batch's input buffers must stay valid until its emit stage is done
-// (lkf_sync, or the enqueue of run n+2).
+// n (DownTrack state), so it overlaps emit n.  Per-batch scratch and outputs
+// live in kCtx (3) batch contexts used in turn: batch n's outputs stay valid
+// until run n+kCtx is enqueued, and a device batch's input buffers must stay
+// valid until its emit stage is done (lkf_sync, or the enqueue of run n+kCtx).
+//
+// Resources are owned by type: device buffers are DevBuf<T> (dev_buf.h),
+// events, streams, graph execs and page-locked memory the owners of
+// hip_own.h; deleting the engine releases them.  Every environment switch is
+// a field of Knobs, read once by lkf_create.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -30,7 +35,10 @@
 #include <vector>
 
 #include "../../include/lkfwd.h"
+#include "ctl_csr.h"
+#include "dev_buf.h"
 #include "fwd_state.h"
+#include "hip_own.h"
 #include "kernels.h"
 
 using namespace lkf;
@@ -51,25 +59,28 @@ DevRegistry &dreg() {
   return r;
 }
 
-template <typename T>
-hipError_t dalloc(T **p, size_t n) {
+}  // namespace
+
+// DevBuf's allocation functions (dev_buf.h): hipMalloc / hipFree + the registry
+int lkf::dev_alloc(void **p, size_t bytes) {
   *p = nullptr;
-  if (n == 0) n = 1;
-  const hipError_t r = hipMalloc(reinterpret_cast<void **>(p), n * sizeof(T));
+  const hipError_t r = hipMalloc(p, bytes);
   if (r == hipSuccess) {
     std::lock_guard<std::mutex> g(dreg().m);
-    dreg().a[reinterpret_cast<uintptr_t>(*p)] = n * sizeof(T);
+    dreg().a[reinterpret_cast<uintptr_t>(*p)] = bytes;
   }
-  return r;
+  return int(r);
 }
 
-hipError_t dfree(void *p) {
-  if (p) {
+int lkf::dev_free(void *p) {
+  {
     std::lock_guard<std::mutex> g(dreg().m);
     dreg().a.erase(reinterpret_cast<uintptr_t>(p));
   }
-  return hipFree(p);
+  return int(hipFree(p));
 }
+
+namespace {
 
 // [src, src + n) inside one live allocation of this registry
 bool dev_range_ok(const void *src, size_t n) {
@@ -81,69 +92,111 @@ bool dev_range_ok(const void *src, size_t n) {
   return s >= it->first && n <= it->second && s - it->first <= it->second - n;
 }
 
-template <typename T>
-static hipError_t grow(T **p, uint64_t &cap, uint64_t need) {
-  if (need <= cap) return hipSuccess;
-  if (*p) (void)dfree(*p);
-  cap = std::max<uint64_t>(need, 1024);
-  return dalloc(p, cap);
-}
-
 constexpr int kStatsWords = 4 + LKF_DROP_NREASONS;
 constexpr uint32_t kIdle = 0xffffffffu;
 
-// Per-batch device scratch, outputs and events (two of them, by run parity).
+// Every environment switch of the engine, read once by lkf_create.  Each says
+// whether it can change the results or only how the work is scheduled.
+struct Knobs {
+  int cuSplit = 0;              // LKF_CU_SPLIT=D: D of every 32 CUs to prep/decide, the rest to emit/sender (scheduling)
+  std::string prio;             // LKF_PRIO=<decide><prep><emit><sender>, h or l each; default hhll (scheduling)
+  int sideCus = 0;              // LKF_SIDE_CUS=N: the NACK side stream on the last N of every 32 CUs (scheduling)
+  int emitWgPerCU = 24;         // LKF_EMIT_WG_PER_CU: the persistent emit grid's workgroups per CU (scheduling)
+  bool emitPersistent = false;  // LKF_EMIT_PERSISTENT=1: emit as a persistent grid-stride launch (scheduling)
+  uint32_t emitLdsPad = 5900;   // LKF_EMIT_LDS: LDS bytes reserved per emit workgroup of an ingest-fed batch (scheduling)
+  uint32_t emitCapFanout = 16;  // LKF_EMIT_CAP_FANOUT: ... when it has fewer DownTracks per track than this (scheduling)
+  uint32_t decideK = 0;         // LKF_DECIDE_K=0..8: DownTracks per decide wave, 0 from the batch (scheduling)
+  bool hostProf = false;        // LKF_HOST_PROF=1: lkf_destroy prints lkf_run's host ms (report only)
+  bool useGraph = true;         // LKF_GRAPH=0: the stages as direct launches instead of graphs (scheduling)
+  bool debugDD = false;         // LKF_DEBUG_DD=1: prints the DD cursors, syncing the prep stream (scheduling)
+  bool skipBktStore = false;    // LKF_SKIP_BKT_STORE=1: no bucket copies; CHANGES RESULTS (RTX from buckets goes stale)
+  bool nackAlone = false;       // LKF_NACK_ALONE=1: the ingest waits for its NACK queues (scheduling)
+
+  static Knobs from_env() {
+    Knobs k;
+    auto num = [](const char *name, int dflt) {
+      const char *v = getenv(name);
+      return v ? atoi(v) : dflt;
+    };
+    k.cuSplit = num("LKF_CU_SPLIT", 0);
+    if (const char *v = getenv("LKF_PRIO")) k.prio = v;
+    k.sideCus = num("LKF_SIDE_CUS", 0);
+    k.emitWgPerCU = std::max(1, num("LKF_EMIT_WG_PER_CU", 24));
+    k.emitPersistent = num("LKF_EMIT_PERSISTENT", 0) != 0;
+    k.emitLdsPad = uint32_t(std::max(0, num("LKF_EMIT_LDS", 5900)));
+    k.emitCapFanout = uint32_t(std::max(0, num("LKF_EMIT_CAP_FANOUT", 16)));
+    k.decideK = uint32_t(std::min(8, std::max(0, num("LKF_DECIDE_K", 0))));
+    k.hostProf = num("LKF_HOST_PROF", 0) != 0;
+    k.useGraph = num("LKF_GRAPH", 1) != 0;
+    k.debugDD = num("LKF_DEBUG_DD", 0) != 0;
+    k.skipBktStore = num("LKF_SKIP_BKT_STORE", 0) != 0;
+    k.nackAlone = num("LKF_NACK_ALONE", 0) != 0;
+    return k;
+  }
+};
+
+// A stream restricted to the CUs i with keep(i % 32) (hipExtStreamCreateWithCUMask).
+template <typename Keep>
+hipError_t cu_mask_stream(Stream &s, int dev, Keep keep) {
+  int ncu = 256;
+  (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
+  std::vector<uint32_t> m(size_t((ncu + 31) / 32), 0);
+  for (int i = 0; i < ncu; i++)
+    if (keep(i % 32)) m[size_t(i / 32)] |= 1u << (i % 32);
+  return hipExtStreamCreateWithCUMask(s.put(), uint32_t(m.size()), m.data());
+}
+
+// Per-batch device scratch, outputs and events (kCtx of them, used in turn).
 struct BatchCtx {
-  uint32_t *dTBegin = nullptr, *dTEnd = nullptr, *dTRuns = nullptr, *dErr = nullptr;
-  uint64_t *dSlotBase = nullptr, *dPartA = nullptr, *dPartB = nullptr, *dTot = nullptr;
-  FwdRec *dRecs = nullptr;    // decide -> emit: forwarded records at slotBase[dt] + j
-  FwdBase *dFBase = nullptr;  // per DownTrack: the base of its records' 32-bit SN / TS
-  FwdBase *dWide = nullptr;   // per tuple slot: a T_WIDE record's full SN / TS
-  uint32_t *dFwdCnt = nullptr;
-  uint64_t *dFwdBytes = nullptr, *dRecBase = nullptr, *dByteBase = nullptr;
-  uint32_t *dGFirst = nullptr;  // emit group g -> output position owning record 64g
-  uint32_t *dTwccBase = nullptr;  // per DownTrack: the batch's first transport-wide sequence number
-  uint32_t *dLayerList = nullptr, *dLayerBefore = nullptr, *dLayerCnt = nullptr;  // k_layer_index
-  lkf_out *dOut = nullptr;
-  uint8_t *dOutArena = nullptr;
-  uint64_t *dStats = nullptr;
-  lkf_pkt *dPktsOwn = nullptr;  // lkf_submit copies land here
-  uint8_t *dArenaOwn = nullptr;
-  lkf_raw_pkt *dRawPkts = nullptr;  // lkf_ingest copies land here
-  uint64_t *dBktStore = nullptr;    // per datagram: what the bucket store copies (kernels.h BucketLaunch)
+  DevBuf<uint32_t> dTBegin, dTEnd, dTRuns, dErr;
+  DevBuf<uint64_t> dSlotBase, dPartA, dTot;
+  DevBuf<FwdRec> dRecs;    // decide -> emit: forwarded records at slotBase[dt] + j
+  DevBuf<FwdBase> dFBase;  // per DownTrack: the base of its records' 32-bit SN / TS
+  DevBuf<FwdBase> dWide;   // per tuple slot: a T_WIDE record's full SN / TS
+  DevBuf<uint32_t> dFwdCnt;
+  DevBuf<uint64_t> dFwdBytes, dRecBase, dByteBase;
+  DevBuf<uint32_t> dGFirst;    // emit group g -> output position owning record 64g
+  DevBuf<uint32_t> dTwccBase;  // per DownTrack: the batch's first transport-wide sequence number
+  DevBuf<uint32_t> dLayerList, dLayerBefore, dLayerCnt;  // k_layer_index
+  DevBuf<lkf_out> dOut;
+  DevBuf<uint8_t> dOutArena;
+  DevBuf<uint64_t> dStats;
+  DevBuf<lkf_pkt> dPktsOwn;  // lkf_submit copies land here
+  DevBuf<uint8_t> dArenaOwn;
+  DevBuf<lkf_raw_pkt> dRawPkts;  // lkf_ingest copies land here
+  DevBuf<uint64_t> dBktStore;    // per datagram: what the bucket store copies (kernels.h BucketLaunch)
   // dependency descriptor (allocated with the first DD track): lkf_submit_dd
   // copies, decoded descriptors, marshalled DD bytes + their bump cursor
-  lkf_pkt_dd *dDDIn = nullptr;
-  DDPkt *dDDPkt = nullptr;
-  uint8_t *dDDArena = nullptr;
-  uint64_t *dDDUsed = nullptr;  // [0] the arena's bump cursor, [1] the spill's (u32)
-  uint16_t *dDDSpill = nullptr;  // custom frame-diff lists longer than kDDFdInline (k_dd_decode)
-  DevEvent *dEvents = nullptr;   // this batch's control ops (per-wave CSR)
-  uint32_t *dEvOff = nullptr;
-  uint32_t *dEvLane = nullptr;   // lane of each op (sorted), for k_ev_offsets
-  uint64_t evCap = 0, evOffCap = 0, evLaneCap = 0;
-  hipEvent_t prepped = nullptr;  // prep stage done (prep stream)
-  hipEvent_t pulled = nullptr;   // the control-op pull from the staging buffer done (own stream)
-  hipEvent_t decided = nullptr;  // decide stage done (decide stream)
-  hipEvent_t sent = nullptr;     // sender statistics done (sender stream)
-  hipEvent_t emitted = nullptr;  // emit stage done (emit stream)
-  hipEvent_t ingested = nullptr;  // this context's ingest done (ingest stream)
+  DevBuf<lkf_pkt_dd> dDDIn;
+  DevBuf<DDPkt> dDDPkt;
+  DevBuf<uint8_t> dDDArena;
+  DevBuf<uint64_t> dDDUsed;   // [0] the arena's bump cursor, [1] the spill's (u32)
+  DevBuf<uint16_t> dDDSpill;  // custom frame-diff lists longer than kDDFdInline (k_dd_decode)
+  DevBuf<DevEvent> dEvents;   // this batch's control ops (per-wave CSR)
+  DevBuf<uint32_t> dEvOff;
+  DevBuf<uint32_t> dEvLane;   // lane of each op (sorted), for k_ev_offsets
+  Event prepped;   // prep stage done (prep stream)
+  Event pulled;    // the control-op pull from the staging buffer done (own stream)
+  Event decided;   // decide stage done (decide stream)
+  Event sent;      // sender statistics done (sender stream)
+  Event emitted;   // emit stage done (emit stream)
+  Event ingested;  // this context's ingest done (ingest stream)
   bool fromIngest = false;        // the pending batch of this context is an ingest's output
   // that ingest also prepared the batch (k_ing_out: track ranges, zeroed
   // counters) for this topology (tracks, DownTracks); lkf_run then skips
   // k_batch_init and k_track_ranges
   bool prepByIngest = false;
   uint32_t prepNT = 0, prepND = 0;
-  uint64_t *dITotal = nullptr;    // that ingest's ExtPacket count (device; k_track_ranges reads it)
+  DevBuf<uint64_t> dITotal;    // that ingest's ExtPacket count (device; k_track_ranges reads it)
   bool used = false;
   // SRTP-protected copy of the output (lkf_protect; allocated on first use)
-  uint8_t *dProt = nullptr;
+  DevBuf<uint8_t> dProt;
   bool protectedRun = false;
   // the run's descriptor (device; k_h2d pulls it from the staging buffer)
-  RunDesc *dDesc = nullptr;
+  DevBuf<RunDesc> dDesc;
   // page-locked, CPU-cached staging of the run's RunDesc + control-op CSR
-  // (malloc + hipHostRegister; k_h2d reads it through the device mapping)
-  uint8_t *stage = nullptr, *stageDev = nullptr;
+  // (k_h2d reads it through the device mapping)
+  StagePair stage;
   uint32_t stageCap = 0;  // ops
   // the prep stage (k_h2d ... layer index) and the decide stage's tail
   // (counters, output scan) as HIP graphs, captured for the engine's topology
@@ -151,7 +204,7 @@ struct BatchCtx {
   // (two prep graphs: [1] with the ingest's prep fused in — k_batch_init /
   // k_track_ranges left out — [0] without; a context alternating between an
   // ingest-prepared batch and another replays both instead of re-capturing)
-  hipGraphExec_t gPrep[2] = {nullptr, nullptr}, gScan = nullptr, gCtl = nullptr;
+  GraphExec gPrep[2], gScan, gCtl;
   uint64_t gPrepEpoch[2] = {0, 0}, gScanEpoch = 0, gCtlEpoch = 0;
 };
 
@@ -159,38 +212,41 @@ struct BatchCtx {
 
 struct lkf_engine {
   int dev = 0;
+  Knobs knobs;
   // LKF_HOST_PROF=1: wall time of lkf_run's host sections (printed by lkf_destroy)
-  bool hostProf = false;
   double hp[9] = {};  // pre, stage wait, csr build, launches, total, runs, staging copies; ingest total, ingests
-  std::vector<uint32_t> fill;  // event CSR fill cursors
-  std::vector<std::pair<uint32_t, uint32_t>> sortA, sortB;  // control-op radix sort (lane, index)
-  hipStream_t own = nullptr;    // copies, lookups
-  hipStream_t d2hS = nullptr;   // lkf_drain_run_async's device -> host copies (created on first use)
-  hipStream_t prepS = nullptr;  // ingest + batch preparation (high priority)
-  // the ingests' stream (Buffer.calc): the prep stream.  A stream of its own
-  // (ingest n+1 beside batch n's preparation; a run's preparation waits for its
-  // ingest's event, which stays) measured 9 % slower on every step shape, even
-  // those without an ingest: one more high-priority stream than the runtime's
-  // hardware queues, so two of the engine's streams shared one (r5 A/B)
-  hipStream_t ingS = nullptr;
-  hipStream_t decS = nullptr;   // decide stage (high priority)
-  hipStream_t emitS = nullptr;  // emit stage (low priority)
-  hipStream_t sendS = nullptr;  // sender statistics of a decided batch (low priority, beside its emit)
+  CtlCsr csr;         // control-op sort (its scratch is reused from run to run)
+  // The streams come first: members are destroyed in reverse order, so every
+  // graph exec, event and buffer below goes before the streams do (and all of
+  // them after lkf_destroy's final device sync).
+  Stream own;    // copies, lookups
+  Stream d2hS;   // lkf_drain_run_async's device -> host copies (created on first use)
+  Stream prepS;  // ingest + batch preparation (high priority)
+  // the ingests' stream (Buffer.calc): the prep stream (a non-owning view).  A
+  // stream of its own (ingest n+1 beside batch n's preparation; a run's
+  // preparation waits for its ingest's event, which stays) measured 9 % slower
+  // on every step shape, even those without an ingest: one more high-priority
+  // stream than the runtime's hardware queues, so two of the engine's streams
+  // shared one (r5 A/B)
+  Stream ingS;
+  Stream decS;   // decide stage (high priority)
+  Stream emitS;  // emit stage (low priority)
+  Stream sendS;  // sender statistics of a decided batch (low priority, beside its emit)
+  Stream sideS;  // an ingest's NACK queues, beside the rest of the ingest and the run
   // transport-wide sequence numbers (pion TWCC header-extension interceptor,
   // send-side BWE): a counter per transport (DownTracks bound to it count
   // together, in record order) or per unbound DownTrack
   std::vector<int32_t> dtTransport;
-  uint32_t *dTwccCtrD = nullptr, *dTwccCtrT = nullptr, *dTwccTOff = nullptr, *dTwccTList = nullptr;
-  uint32_t twccTCap = 0, twccListCap = 0, nTwccT = 0;
+  DevBuf<uint32_t> dTwccCtrD, dTwccCtrT, dTwccTOff, dTwccTList;
+  uint32_t nTwccT = 0;
   bool anyTwcc = false, twccDirty = false;
-  hipStream_t sideS = nullptr;  // an ingest's NACK queues, beside the rest of the ingest and the run
-  hipEvent_t sideFork = nullptr, sideDone[2] = {nullptr, nullptr};
+  Event sideFork, sideDone[2];
   bool sidePending[2] = {false, false};  // an ingest waits for the NACK queues of the one two back
-  hipEvent_t bktDone[2] = {nullptr, nullptr};
+  Event bktDone[2];
   bool bktPending[2] = {false, false};   // ... and for its bucket copies
-  hipStream_t cur = nullptr;    // caller's stream of the last lkf_run
-  hipEvent_t inEv = nullptr;    // caller-stream work before a run
-  hipEvent_t bktEv = nullptr;   // an ingest's bucket decisions (the sender stream copies after it)
+  hipStream_t cur = nullptr;    // caller's stream of the last lkf_run (not owned)
+  Event inEv;                   // caller-stream work before a run
+  Event bktEv;                  // an ingest's bucket decisions (the sender stream copies after it)
   bool bktStorePending = false; // the next run's context waits for those copies
   lkf_cfg cfg{};
   std::string err;
@@ -218,89 +274,74 @@ struct lkf_engine {
   bool spkDirty = true;
 
   // queued control ops
-  struct Pend {
-    uint32_t dt;
-    DevEvent ev;
-  };
+  using Pend = CtlPend;
   std::vector<Pend> pending;
   // topology epoch: bumped by every change the captured stage graphs depend
   // on (tables, schedule, DD / tracker allocations); a context re-captures
   // its graphs when its epoch is older
   uint64_t epoch = 1;
   uint64_t topoGen = 0;  // bumped by every topology change (tracks, DownTracks, streams, removals, rooms)
-  bool useGraph = true;  // LKF_GRAPH=0: the stages as direct launches (A/B)
-  bool debugDD = false;  // LKF_DEBUG_DD=1: report the DD cursors (diagnostic)
 
   // device: persistent state
-  DevTrack *dTracks = nullptr;
-  DTHot *dHot = nullptr;
-  DTCum *dDTCum = nullptr;  // per DownTrack sendingPacket totals (lkf_downtrack_summaries)
+  DevBuf<DevTrack> dTracks;
+  DevBuf<DTHot> dHot;
+  DevBuf<DTCum> dDTCum;  // per DownTrack sendingPacket totals (lkf_downtrack_summaries)
   // per DownTrack RTPStatsSender (sender_kernels.hip): statistics, gap
   // histogram, snInfo ring; host-listed updates (padding / blank / RTX)
-  SenderStats *dSS = nullptr;
-  uint32_t *dSSGap = nullptr;
-  uint32_t *dSSRing = nullptr;
-  SenderUpd *dSSList = nullptr;
-  uint32_t *dSSGroups = nullptr;
-  uint32_t ssListCap = 0;
+  DevBuf<SenderStats> dSS;
+  DevBuf<uint32_t> dSSGap;
+  DevBuf<uint32_t> dSSRing;
+  DevBuf<SenderUpd> dSSList;
+  DevBuf<uint32_t> dSSGroups;  // (one more than dSSList)
   int64_t rtxNow = 0;  // now_ns of the last lkf_rtx_lookup (the RTX packets' sendingPacket time)
   // sequencer ddBytes (sequencer.go:198-199) of the DownTracks that can forward
   // a dependency descriptor: [ring index][slot] kSeqDDBytes, grown on demand
-  uint8_t *dSeqDD = nullptr;
-  uint32_t *dSeqDDIdx = nullptr;   // per DownTrack: ring index or 0xffffffff
-  uint32_t *dSeqDDList = nullptr;  // ring index -> DownTrack
-  uint32_t nSeqDD = 0, seqDDCap = 0;
+  DevBuf<uint8_t> dSeqDD;
+  DevBuf<uint32_t> dSeqDDIdx;   // per DownTrack: ring index or 0xffffffff
+  DevBuf<uint32_t> dSeqDDList;  // ring index -> DownTrack; its cap() is the rings' capacity
+  uint32_t nSeqDD = 0;
   std::vector<uint32_t> seqDDList;
-  uint8_t *dRtxDD = nullptr;  // lkf_rtx_emit: per record kSeqDDBytes
+  DevBuf<uint8_t> dRtxDD;  // lkf_rtx_emit: per record kSeqDDBytes
   // the cooperative allocation pass: per DownTrack provisional state + call buffers
-  ProvState *dProv = nullptr;
-  lkf_prov_req *dProvReq = nullptr;
-  lkf_alloc_group *dProvGroups = nullptr;
-  uint8_t *dProvOut = nullptr;
-  uint32_t provCap = 0, provGroupCap = 0;
+  DevBuf<ProvState> dProv;
+  DevBuf<lkf_prov_req> dProvReq;
+  DevBuf<lkf_alloc_group> dProvGroups;
+  DevBuf<uint8_t> dProvOut;  // sizeof(lkf_allocation) bytes per request
   // dependency-descriptor stream trackers (lkf_add_stream_tracker_dd)
-  DDTrkState *dDDTrk = nullptr;
-  uint32_t *dTrackDDTrk = nullptr;  // track -> DD tracker (0xffffffff none), max_tracks
+  DevBuf<DDTrkState> dDDTrk;
+  DevBuf<uint32_t> dTrackDDTrk;  // track -> DD tracker (0xffffffff none), max_tracks
   std::vector<int32_t> trackDDTrk;
-  uint32_t nDDTrk = 0, ddTrkCap = 0;
-  int32_t *dDDTrkIds = nullptr;
-  lkf_dd_tracker_status *dDDTrkOut = nullptr;
-  uint64_t ddTrkIdsCap = 0, ddTrkOutCap = 0;
-  uint32_t rtxDDCap = 0;
-  DevDT *dDTs = nullptr;
-  RangeEntry *dRm = nullptr;
-  VP8Cold *dVc = nullptr;
-  SeqMeta *dSeq = nullptr;
-  uint32_t *dSched = nullptr;
-  uint32_t *dWaveTrack = nullptr;
-  uint32_t *dEvOff = nullptr;
-  uint32_t *dPerm = nullptr;  // output position -> DownTrack (track-major)
-  size_t schedCap = 0;
-  DevEvent *dEvents = nullptr;
-  uint64_t evCap = 0;
-  uint64_t *dCum = nullptr;
+  uint32_t nDDTrk = 0;
+  DevBuf<int32_t> dDDTrkIds;
+  DevBuf<lkf_dd_tracker_status> dDDTrkOut;
+  DevBuf<DevDT> dDTs;
+  DevBuf<RangeEntry> dRm;
+  DevBuf<VP8Cold> dVc;
+  DevBuf<SeqMeta> dSeq;
+  DevBuf<uint32_t> dSched;
+  DevBuf<uint32_t> dWaveTrack;  // (one more than dSched)
+  DevBuf<uint32_t> dPerm;  // output position -> DownTrack (track-major)
+  DevBuf<uint64_t> dCum;
   // sticky error word: every batch's decide/emit error bits (bits 0-7) and
   // every ingest's error bits (<< 8) are OR-ed in on the GPU; lkf_sync reports
   // and clears it (per-context error words are reused every kCtx runs)
-  uint32_t *dSticky = nullptr;
+  DevBuf<uint32_t> dSticky;
 
   // dependency-descriptor selector tables (allocated with the first DD track)
   uint32_t nDDTracks = 0;
   bool ddAlloc = false;
-  uint64_t ddArenaCap = 0;
-  uint32_t ddSpillCap = 0;
-  DDStruct *dDDStruct = nullptr;  // [ddIdx * kDDSlots + slot]
-  DDTrack *dDDTrack = nullptr;
-  DDState *dDDState = nullptr;    // per DownTrack
+  DevBuf<DDStruct> dDDStruct;  // [ddIdx * kDDSlots + slot]
+  DevBuf<DDTrack> dDDTrack;
+  DevBuf<DDState> dDDState;    // per DownTrack
   size_t ddStateInit = 0;         // DownTracks whose DDState is zeroed
   uint32_t ddTrackInit = 0;
   std::vector<uint8_t> dtIsDD;    // per DownTrack: SVC (DD selector or VP9), scheduled in k_decide_dt<true>
   uint32_t ddLanes = 0;
   // ingress DependencyDescriptorParser per DD stream (allocated with the first)
   uint32_t nDDStreams = 0, ddStreamInit = 0;
-  DDIngState *dDDIng = nullptr;      // [stream.ddIdx]
-  DDStruct *dDDIngStruct = nullptr;  // [stream.ddIdx * 2 + DI_CUR slot]
-  IngDD *dIngDD = nullptr;           // per datagram of an ingest
+  DevBuf<DDIngState> dDDIng;      // [stream.ddIdx]
+  DevBuf<DDStruct> dDDIngStruct;  // [stream.ddIdx * 2 + DI_CUR slot]
+  DevBuf<IngDD> dIngDD;           // per datagram of an ingest
 
   // batch input for the next run
   const lkf_pkt_dd *curDD = nullptr;
@@ -323,137 +364,114 @@ struct lkf_engine {
   int lastCtx = -1;
   // pinned bounce buffer of the host drains (D2H into caller memory that may
   // be pageable goes through it, on the engine's own stream)
-  uint8_t *bounce = nullptr, *bounceDev = nullptr;
-  size_t bounceCap = 0;
+  PinnedBuf bounce;
 
-  // NACK -> RTX scratch (grown on demand)
-  lkf_nack *dNacks = nullptr;
-  uint32_t *dNackG = nullptr, *dNackValid = nullptr;
-  lkf_rtx *dRtx = nullptr;
-  uint32_t rtxCap = 0;
-  lkf_raw_pkt *dRtxSrc = nullptr;
-  uint32_t *dRtxLen = nullptr;
-  uint64_t *dRtxOff = nullptr;
-  uint8_t *dRtxIn = nullptr, *dRtxOut = nullptr;
-  uint64_t rtxInCap = 0, rtxOutCap = 0;
+  // NACK -> RTX scratch (grown on demand; the first seven together)
+  DevBuf<lkf_nack> dNacks;
+  DevBuf<uint32_t> dNackG, dNackValid;  // (dNackG: one more than the rest)
+  DevBuf<lkf_rtx> dRtx;
+  DevBuf<lkf_raw_pkt> dRtxSrc;
+  DevBuf<uint32_t> dRtxLen;
+  DevBuf<uint64_t> dRtxOff;
+  DevBuf<uint8_t> dRtxIn, dRtxOut;
 
   // stream trackers (lkf_add_stream_tracker): device state, tick scratch
-  TrackerState *dTrk = nullptr;
-  uint32_t nTrk = 0, trkCap = 0;
-  int32_t *dTrkIds = nullptr;
-  lkf_tracker_status *dTrkOut = nullptr;
-  uint64_t trkIdsCap = 0, trkOutCap = 0;
+  DevBuf<TrackerState> dTrk;
+  uint32_t nTrk = 0;
+  DevBuf<int32_t> dTrkIds;
+  DevBuf<lkf_tracker_status> dTrkOut;
   // RED per-track state (lkf_red_encode / lkf_red_decode), allocated at first use
-  RedEncState *dRedEnc = nullptr;
-  RedDecState *dRedDec = nullptr;
+  DevBuf<RedEncState> dRedEnc;
+  DevBuf<RedDecState> dRedDec;
   struct RedScratch {
-    lkf_pkt *in = nullptr, *out = nullptr;
-    uint8_t *inArena = nullptr, *outArena = nullptr;
-    uint32_t *g = nullptr, *cnt = nullptr;
-    int32_t *map = nullptr;
-    uint64_t *off = nullptr;
-    uint64_t inCap = 0, outCap = 0, inArenaCap = 0, outArenaCap = 0, gCap = 0, cntCap = 0, mapCap = 0, offCap = 0;
+    DevBuf<lkf_pkt> in, out;
+    DevBuf<uint8_t> inArena, outArena;
+    DevBuf<uint32_t> g, cnt;
+    DevBuf<int32_t> map;
+    DevBuf<uint64_t> off;
   } red;
   // lastAllocation.BandwidthRequested per DownTrack (lkf_allocate_optimal)
-  lkf_allocation *dLastAlloc = nullptr;  // lastAllocation per DownTrack
-  lkf_alloc_req *dAllocReq = nullptr;
-  int64_t *dAllocCapacity = nullptr;
-  lkf_allocation *dAllocOut = nullptr;
-  uint32_t allocCap = 0;
+  DevBuf<lkf_allocation> dLastAlloc;  // lastAllocation per DownTrack
+  DevBuf<lkf_alloc_req> dAllocReq;
+  DevBuf<int64_t> dAllocCapacity;
+  DevBuf<lkf_allocation> dAllocOut;
   // the sequencers' padding RangeMaps (SeqRM regions) and padding scratch
-  uint8_t *dSrm = nullptr;
+  DevBuf<uint8_t> dSrm;
   uint64_t srmStride = 0;
-  uint32_t srmCap = 0;
-  lkf_pad_req *dPadReq = nullptr;
-  uint64_t *dPadOff = nullptr;  // [2 * cap]: record bases, then arena bases
-  uint32_t *dPadCnt = nullptr;  // [2 * cap]: packets, then bytes
-  uint32_t padCap = 0;
-  lkf_out *dPadOut = nullptr;
-  uint64_t padOutCap = 0;
-  uint8_t *dPadArena = nullptr;
-  uint64_t padArenaCap = 0;
+  uint32_t srmCap = 0;  // (entries of one SeqRM region, a kernel argument: not a buffer's capacity)
+  DevBuf<lkf_pad_req> dPadReq;
+  DevBuf<uint64_t> dPadOff;  // [2 * requests]: record bases, then arena bases
+  DevBuf<uint32_t> dPadCnt;  // [2 * requests]: packets, then bytes
+  DevBuf<lkf_out> dPadOut;
+  DevBuf<uint8_t> dPadArena;
 
   // seq lookup scratch
-  uint16_t *dSns = nullptr;
-  lkf_seq_meta *dSeqOut = nullptr;
-  uint32_t *dSeqN = nullptr;
-  uint32_t seqScratchCap = 0;
+  DevBuf<uint16_t> dSns;
+  DevBuf<lkf_seq_meta> dSeqOut;
+  DevBuf<uint32_t> dSeqN;
 
   // timing ring: [0] decide-stage start, [1] decide kernel start, [2] decide
   // kernel end (decide stream), [3] emit kernel start, [4] emit kernel end
   // (emit stream)
   static constexpr int kRing = 256;
-  hipEvent_t ring[kRing][5] = {};
+  Event ring[kRing][5];
   uint32_t emitGrid = 2048;       // persistent grid-stride launch (LKF_EMIT_PERSISTENT=1)
-  bool emitPersistent = false;
-  uint32_t emitLdsPad = 5900;  // bytes of LDS reserved per emit workgroup of an ingest-fed batch (12 per CU)
-  uint32_t emitCapFanout = 16;  // ... when the batch has fewer DownTracks per track than this
-  uint32_t decideK = 0;  // DownTracks per decide wave (0: from the batch's packets per track)
   // SRTP protect (tables allocated with the first transport or lkf_protect)
   std::vector<lkf_transport_params> transports;
-  lkf_transport_params *dTransports = nullptr;
-  SrtpKeys *dSrtpKeys = nullptr;
-  uint32_t transportCap = 0;
-  uint32_t *dAesTab = nullptr;
-  SrtpDT *dSrtpDT = nullptr;
-  hipEvent_t protRing[256][2] = {};  // k_srtp_roc start / k_srtp_protect end per run (timing)
-  std::vector<uint8_t> protRun;      // per ring slot: that run was protected
+  DevBuf<lkf_transport_params> dTransports;
+  DevBuf<SrtpKeys> dSrtpKeys;
+  DevBuf<uint32_t> dAesTab;
+  DevBuf<SrtpDT> dSrtpDT;
+  Event protRing[256][2];        // k_srtp_roc start / k_srtp_protect end per run (timing)
+  std::vector<uint8_t> protRun;  // per ring slot: that run was protected
   // ingress (one buffer.Buffer per stream) + speakers
   uint32_t maxStreams = 0;
-  DevStream *dStreams = nullptr;
-  StreamHot *dStreamHot = nullptr;
-  uint64_t *dHist = nullptr;
-  uint32_t *dRxGap = nullptr;  // per stream RTPStatsReceiver gap histogram (kGapWords u32)
-  RangeEntry *dStreamRings = nullptr;
-  IngParsed *dParsed = nullptr;
-  lkf_flow *dFlows = nullptr;
-  uint32_t *dTwcc = nullptr;  // per datagram TWCC push word of the last ingest
+  DevBuf<DevStream> dStreams;
+  DevBuf<StreamHot> dStreamHot;
+  DevBuf<uint64_t> dHist;
+  DevBuf<uint32_t> dRxGap;  // per stream RTPStatsReceiver gap histogram (kGapWords u32)
+  DevBuf<RangeEntry> dStreamRings;
+  DevBuf<uint32_t> dTwcc;  // per datagram TWCC push word of the last ingest
   // the receivers' RTX buckets (kernels.h BucketState): per stream state, slot
-  // tags / batch owners / bytes, per datagram slot
-  BucketState *dBkt = nullptr;
-  uint32_t *dBktTag = nullptr;
-  uint64_t *dBktOwner = nullptr;
+  // tags / batch owners / bytes (bktSlots of dBktTag.cap() in use), per datagram slot
+  DevBuf<BucketState> dBkt;
+  DevBuf<uint32_t> dBktTag;
+  DevBuf<uint64_t> dBktOwner;
   uint32_t bktEpoch = 0;
-  uint8_t *dBktRing = nullptr;
-  uint64_t bktSlots = 0, bktCap = 0;
-  int32_t *dBktStream = nullptr;
-  uint16_t *dBktSn = nullptr;
-  uint32_t bktReadCap = 0;
-  uint32_t *dFwdFlag = nullptr;
-  uint64_t *dPos = nullptr, *dIPartA = nullptr, *dIPartB = nullptr, *dITotal = nullptr;
-  uint32_t *dITBegin = nullptr, *dITEnd = nullptr, *dITRuns = nullptr, *dIErr = nullptr;
-  uint32_t *dIList = nullptr, *dIListCnt = nullptr;  // per-stream datagram lists (k_ing_lists)
+  DevBuf<uint8_t> dBktRing;
+  uint64_t bktSlots = 0;
+  DevBuf<int32_t> dBktStream;
+  DevBuf<uint16_t> dBktSn;
+  DevBuf<uint64_t> dPos, dIPartA, dITotal;
+  DevBuf<uint32_t> dITRuns, dIErr;
   // The ingest scratch the NACK queues (side stream) and the bucket copies
   // (sender stream) read after the ingest chain has moved on: two sets,
   // alternating per ingest, so an ingest waits only for the side work of the
-  // ingest two back.  The d* pointers above and below name the last ingest's set.
+  // ingest two back.  ing[ingPar] is the last ingest's set.
   struct IngSet {
-    IngParsed *parsed = nullptr;
-    lkf_flow *flows = nullptr;
-    uint32_t *fwd = nullptr, *tBegin = nullptr, *tEnd = nullptr, *list = nullptr, *listCnt = nullptr;
-    uint32_t *nackInfo = nullptr, *nackPairOff = nullptr, *nackPairCnt = nullptr;
-    lkf_nack_pair *nackPairs = nullptr;
-    NackIn *nackIn = nullptr;  // the NACK kernel's per-datagram input, in list order
+    DevBuf<IngParsed> parsed;
+    DevBuf<lkf_flow> flows;
+    DevBuf<uint32_t> fwd, tBegin, tEnd, list, listCnt;  // (list: per-stream datagram lists, k_ing_lists)
+    // the ingest's RTCP NACKs: per datagram result + bump-allocated pairs
+    DevBuf<uint32_t> nackInfo, nackPairOff, nackPairCnt;
+    DevBuf<lkf_nack_pair> nackPairs;
+    DevBuf<NackIn> nackIn;  // the NACK kernel's per-datagram input, in list order
   } ing[2];
   int ingPar = 0;
-  // NACK queues (allocated with the first stream that has one) and the last
-  // ingest's RTCP NACKs (per datagram result + bump-allocated pairs)
-  NackState *dNack = nullptr;
-  uint32_t *dNackInfo = nullptr, *dNackPairOff = nullptr, *dNackPairCnt = nullptr;
-  lkf_nack_pair *dNackPairs = nullptr;
-  uint32_t nackPairCap = 0;
-  uint64_t *dNackRecPos = nullptr, *dNackPairPos = nullptr, *dNackTot = nullptr;
-  uint64_t *dNackPartA = nullptr, *dNackPartB = nullptr;  // the compaction's scan partials (side stream)
-  lkf_rtcp_nack *dNackOut = nullptr;
-  lkf_nack_pair *dNackPairsOut = nullptr;
+  // NACK queues (allocated with the first stream that has one)
+  DevBuf<NackState> dNack;
+  uint32_t nackPairCap = 0;  // (a kernel argument: the bump-allocated part of IngSet::nackPairs)
+  DevBuf<uint64_t> dNackRecPos, dNackPairPos, dNackTot;
+  DevBuf<uint64_t> dNackPartA;  // the compaction's scan state (side stream)
+  DevBuf<lkf_rtcp_nack> dNackOut;
+  DevBuf<lkf_nack_pair> dNackPairsOut;
   uint32_t lastIngestN = 0;
   const lkf_raw_pkt *ingRaws = nullptr;  // the last ingest's datagram descriptors (device)
   // speaker ranking tables (rebuilt when topology changes)
   uint32_t nRooms = 0;
-  uint32_t *dRoomPartOff = nullptr, *dPartId = nullptr, *dPartMicOff = nullptr, *dMics = nullptr, *dRoomId = nullptr;
-  lkf_speaker *dSpkSlots = nullptr;
-  uint32_t *dSpkCounts = nullptr;
-  size_t spkCap = 0;
+  DevBuf<uint32_t> dRoomPartOff, dPartId, dPartMicOff, dMics, dRoomId;
+  DevBuf<lkf_speaker> dSpkSlots;
+  DevBuf<uint32_t> dSpkCounts;
   std::vector<uint32_t> spkRoomIds;  // host copy of dRoomId
   // lkf_room_summaries_enqueue: the records' layout for (rows, k, s) and the
   // topology it was built for; two events order the caller's stream after the
@@ -461,10 +479,10 @@ struct lkf_engine {
   std::vector<uint32_t> rsRooms;
   uint32_t rsK = 0, rsS = 0;
   uint64_t rsGen = ~0ull;
-  int32_t *dRsRowEng = nullptr;
-  uint32_t *dRsSlotOff = nullptr, *dRsSlotDts = nullptr;
-  int64_t *dRsSlotSub = nullptr;
-  hipEvent_t rsSpk = nullptr, rsDec = nullptr;
+  DevBuf<int32_t> dRsRowEng;
+  DevBuf<uint32_t> dRsSlotOff, dRsSlotDts;
+  DevBuf<int64_t> dRsSlotSub;
+  Event rsSpk, rsDec;
   // device -> host copies refused by the range check (CHKRANGE) since the last
   // lkf_debug_check of this engine (lkf_debug_check folds them in)
   std::atomic<uint64_t> rangeViolations{0};
@@ -486,7 +504,7 @@ struct lkf_engine {
     uint32_t offs[9];
   };
   std::vector<TrackOp> trkOps;
-  uint32_t *dDTOffs = nullptr;  // per DownTrack kDTOffsWords: the offsets its Forwarder reads
+  DevBuf<uint32_t> dDTOffs;  // per DownTrack kDTOffsWords: the offsets its Forwarder reads
   // the current batch's descriptors / DD side array are engine allocations
   // (lkf_submit / lkf_ingest*) rather than the caller's (lkf_submit_device)
   bool curOwned = false, curDDOwned = false;
@@ -500,7 +518,7 @@ static int fail(lkf_engine *e, const char *what, hipError_t r) {
 }
 #define HIPCHK(call, what)                          \
   do {                                              \
-    hipError_t _r = (call);                         \
+    const hipError_t _r = static_cast<hipError_t>(call);                         \
     if (_r != hipSuccess) return fail(e, what, _r); \
   } while (0)
 
@@ -550,36 +568,6 @@ static DevTrack to_dev_track(const lkf_track_params &p, uint32_t ddIdx) {
 }
 
 // Waits for every queued stage (run, own and emit streams).
-template <typename T>
-static hipError_t stage_alloc(T **host, T **dev, size_t n) {
-  const size_t bytes = (n * sizeof(T) + 4095) & ~size_t(4095);
-  void *p = std::aligned_alloc(4096, bytes);
-  if (!p) return hipErrorOutOfMemory;
-  hipError_t r = hipHostRegister(p, bytes, hipHostRegisterMapped);
-  if (r != hipSuccess) {
-    std::free(p);
-    return r;
-  }
-  void *d = nullptr;
-  r = hipHostGetDevicePointer(&d, p, 0);
-  if (r != hipSuccess) {
-    (void)hipHostUnregister(p);
-    std::free(p);
-    return r;
-  }
-  *host = static_cast<T *>(p);
-  *dev = static_cast<T *>(d);
-  return hipSuccess;
-}
-template <typename T>
-static void stage_free(T **host, T **dev) {
-  if (*host) {
-    (void)hipHostUnregister(*host);
-    std::free(*host);
-  }
-  *host = *dev = nullptr;
-}
-
 static int drain_streams(lkf_engine *e) {
   HIPCHK(hipSetDevice(e->dev), "hipSetDevice");
   if (e->cur && e->cur != e->own) HIPCHK(hipStreamSynchronize(e->cur), "sync run stream");
@@ -634,15 +622,12 @@ static int copy_to_host(lkf_engine *e, void *dst, const void *src, size_t n, con
     return LKF_OK;
   }
   (void)hipGetLastError();  // (an unregistered pointer is not an error here)
-  if (!e->bounce) {
-    HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&e->bounce), kChunk, hipHostMallocDefault), "alloc bounce");
-    e->bounceCap = kChunk;
-  }
+  if (!e->bounce.p) HIPCHK(e->bounce.alloc(kChunk), "alloc bounce");
   for (size_t off = 0; off < n; off += kChunk) {
     const size_t k = std::min(kChunk, n - off);
-    HIPCHK(hipMemcpyAsync(e->bounce, static_cast<const uint8_t *>(src) + off, k, hipMemcpyDeviceToHost, e->own), what);
+    HIPCHK(hipMemcpyAsync(e->bounce.p, static_cast<const uint8_t *>(src) + off, k, hipMemcpyDeviceToHost, e->own), what);
     HIPCHK(hipStreamSynchronize(e->own), what);
-    std::memcpy(static_cast<uint8_t *>(dst) + off, e->bounce, k);
+    std::memcpy(static_cast<uint8_t *>(dst) + off, e->bounce.p, k);
   }
   return LKF_OK;
 }
@@ -664,7 +649,7 @@ static int sender_list(lkf_engine *e, std::vector<SenderUpd> &list);
 // sender stream (padding, blank frames, RTX) must come after both, or a
 // queued tick's Update and the call's load/store of the same SenderStats race.
 static int sender_after_queued(lkf_engine *e) {
-  for (hipStream_t s : {e->decS, e->emitS, e->own}) {
+  for (hipStream_t s : {e->decS.get(), e->emitS.get(), e->own.get()}) {
     HIPCHK(hipEventRecord(e->inEv, s), "event");
     HIPCHK(hipStreamWaitEvent(e->sendS, e->inEv, 0), "wait queued stage");
   }
@@ -676,12 +661,12 @@ static int sender_after_queued(lkf_engine *e) {
 static int ensure_dd(lkf_engine *e) {
   const lkf_cfg &c = e->cfg;
   if ((e->nDDTracks || e->nDDStreams) && !e->ctx[0].dDDIn)  // ingest output / lkf_submit_dd input
-    for (auto &x : e->ctx) HIPCHK(dalloc(&x.dDDIn, c.max_batch_pkts), "alloc dd in");
+    for (auto &x : e->ctx) HIPCHK(x.dDDIn.alloc(c.max_batch_pkts), "alloc dd in");
   if (e->nDDStreams && !e->dDDIng) {
-    HIPCHK(dalloc(&e->dDDIng, e->maxStreams), "alloc dd parsers");
-    HIPCHK(dalloc(&e->dDDIngStruct, size_t(e->maxStreams) * 2), "alloc dd parser structures");
+    HIPCHK(e->dDDIng.alloc(e->maxStreams), "alloc dd parsers");
+    HIPCHK(e->dDDIngStruct.alloc(size_t(e->maxStreams) * 2), "alloc dd parser structures");
     HIPCHK(hipMemset(e->dDDIngStruct, 0, size_t(e->maxStreams) * 2 * sizeof(DDStruct)), "dd parser structures reset");
-    HIPCHK(dalloc(&e->dIngDD, c.max_batch_pkts), "alloc ingest dd");
+    HIPCHK(e->dIngDD.alloc(c.max_batch_pkts), "alloc ingest dd");
   }
   if (e->nDDStreams > e->ddStreamInit) {  // a fresh parser per new DD stream
     HIPCHK(hipMemset(e->dDDIng + e->ddStreamInit, 0, size_t(e->nDDStreams - e->ddStreamInit) * sizeof(DDIngState)),
@@ -689,21 +674,21 @@ static int ensure_dd(lkf_engine *e) {
     e->ddStreamInit = e->nDDStreams;
   }
   if (e->ddAlloc || e->nDDTracks == 0) return LKF_OK;
-  HIPCHK(dalloc(&e->dDDStruct, size_t(c.max_tracks) * kDDSlots), "alloc dd structures");
-  HIPCHK(dalloc(&e->dDDTrack, c.max_tracks), "alloc dd tracks");
-  HIPCHK(dalloc(&e->dDDState, c.max_downtracks), "alloc dd state");
+  HIPCHK(e->dDDStruct.alloc(size_t(c.max_tracks) * kDDSlots), "alloc dd structures");
+  HIPCHK(e->dDDTrack.alloc(c.max_tracks), "alloc dd tracks");
+  HIPCHK(e->dDDState.alloc(c.max_downtracks), "alloc dd state");
   HIPCHK(hipMemset(e->dDDTrack, 0, size_t(c.max_tracks) * sizeof(DDTrack)), "dd tracks reset");
   HIPCHK(hipMemset(e->dDDStruct, 0, size_t(c.max_tracks) * kDDSlots * sizeof(DDStruct)), "dd structures reset");
-  e->ddArenaCap = c.max_out_bytes / 4 + (1u << 20);
-  e->ddSpillCap = uint32_t(std::min<uint64_t>(uint64_t(c.max_batch_pkts) * kDDFdInline + 4096, 0x7fffffffu));
+  const uint64_t arenaCap = c.max_out_bytes / 4 + (1u << 20);
+  const uint32_t spillCap = uint32_t(std::min<uint64_t>(uint64_t(c.max_batch_pkts) * kDDFdInline + 4096, 0x7fffffffu));
   for (auto &x : e->ctx) {
-    HIPCHK(dalloc(&x.dDDPkt, c.max_batch_pkts), "alloc dd pkts");
-    HIPCHK(dalloc(&x.dDDArena, e->ddArenaCap), "alloc dd arena");
-    HIPCHK(dalloc(&x.dDDUsed, 2), "alloc dd cursor");
+    HIPCHK(x.dDDPkt.alloc(c.max_batch_pkts), "alloc dd pkts");
+    HIPCHK(x.dDDArena.alloc(arenaCap), "alloc dd arena");
+    HIPCHK(x.dDDUsed.alloc(2), "alloc dd cursor");
     // (zeroed here too: k_layer_index zeroes it per batch, but recycled memory
     // must never be read as a cursor; DESIGN.md §6 round-5 cursor report)
     HIPCHK(hipMemset(x.dDDUsed, 0, 2 * sizeof(uint64_t)), "dd cursor reset");
-    HIPCHK(dalloc(&x.dDDSpill, e->ddSpillCap), "alloc dd spill");
+    HIPCHK(x.dDDSpill.alloc(spillCap), "alloc dd spill");
   }
   e->ddAlloc = true;
   return LKF_OK;
@@ -765,20 +750,19 @@ static int flush_topology(lkf_engine *e) {
         idx.push_back(dd ? e->nSeqDD++ : 0xffffffffu);
         if (dd) e->seqDDList.push_back(d);
       }
-      if (e->nSeqDD > e->seqDDCap) {  // grow (the streams are drained): copy the rings already filled
-        const uint32_t cap = std::max<uint32_t>(e->nSeqDD, 2 * e->seqDDCap);
+      if (e->nSeqDD > e->dSeqDDList.cap()) {  // grow (the streams are drained): copy the rings already filled
+        const uint32_t cap = std::max<uint32_t>(e->nSeqDD, 2 * uint32_t(e->dSeqDDList.cap()));
         const size_t per = size_t(e->cfg.seq_size) * kSeqDDBytes;
-        uint8_t *nr = nullptr;
-        HIPCHK(dalloc(&nr, size_t(cap) * per), "alloc sequencer dd");
+        // (both new buffers first: a failed allocation leaves the old rings and list as they were)
+        DevBuf<uint8_t> nr;
+        DevBuf<uint32_t> nl;
+        HIPCHK(nr.alloc(size_t(cap) * per), "alloc sequencer dd");
+        HIPCHK(nl.alloc(cap), "alloc sequencer dd list");
         HIPCHK(hipMemset(nr, 0, size_t(cap) * per), "sequencer dd reset");
-        if (e->dSeqDD) {
+        if (e->dSeqDD)
           HIPCHK(hipMemcpy(nr, e->dSeqDD, size_t(n0) * per, hipMemcpyDeviceToDevice), "sequencer dd move");
-          HIPCHK(dfree(e->dSeqDD), "free sequencer dd");
-        }
-        if (e->dSeqDDList) HIPCHK(dfree(e->dSeqDDList), "free sequencer dd list");
-        HIPCHK(dalloc(&e->dSeqDDList, cap), "alloc sequencer dd list");
-        e->dSeqDD = nr;
-        e->seqDDCap = cap;
+        e->dSeqDD = std::move(nr);
+        e->dSeqDDList = std::move(nl);
       }
       HIPCHK(hipMemcpy(e->dSeqDDIdx + first, idx.data(), idx.size() * sizeof(uint32_t), hipMemcpyHostToDevice),
              "sequencer dd index");
@@ -803,27 +787,23 @@ static int flush_topology(lkf_engine *e) {
         need += bs[i].maxSteps;
       }
       const uint64_t total = e->bktSlots + need;
-      if (!e->dBkt) HIPCHK(dalloc(&e->dBkt, e->maxStreams), "alloc buckets");
-      if (total > e->bktCap) {
-        const uint64_t cap = std::max<uint64_t>(total, 2 * e->bktCap);
-        uint32_t *tag = nullptr;
-        uint64_t *own = nullptr;
-        uint8_t *ring = nullptr;
-        HIPCHK(dalloc(&tag, cap), "alloc bucket tags");
-        HIPCHK(dalloc(&own, cap), "alloc bucket owners");
+      if (!e->dBkt) HIPCHK(e->dBkt.alloc(e->maxStreams), "alloc buckets");
+      if (total > e->dBktTag.cap()) {  // grow, keeping the slots in use
+        const uint64_t cap = std::max<uint64_t>(total, 2 * e->dBktTag.cap());
+        DevBuf<uint32_t> tag;
+        DevBuf<uint64_t> own;
+        DevBuf<uint8_t> ring;
+        HIPCHK(tag.alloc(cap), "alloc bucket tags");
+        HIPCHK(own.alloc(cap), "alloc bucket owners");
         HIPCHK(hipMemset(own, 0, cap * sizeof(uint64_t)), "bucket owners init");  // (epochs start at 1)
-        HIPCHK(dalloc(&ring, cap * kBktSlot), "alloc bucket ring");
+        HIPCHK(ring.alloc(cap * kBktSlot), "alloc bucket ring");
         if (e->bktSlots) {
           HIPCHK(hipMemcpy(tag, e->dBktTag, e->bktSlots * 4, hipMemcpyDeviceToDevice), "bucket tags copy");
           HIPCHK(hipMemcpy(ring, e->dBktRing, e->bktSlots * kBktSlot, hipMemcpyDeviceToDevice), "bucket ring copy");
         }
-        for (void *p : {static_cast<void *>(e->dBktTag), static_cast<void *>(e->dBktOwner),
-                        static_cast<void *>(e->dBktRing)})
-          if (p) HIPCHK(dfree(p), "free bucket");
-        e->dBktTag = tag;
-        e->dBktOwner = own;
-        e->dBktRing = ring;
-        e->bktCap = cap;
+        e->dBktTag = std::move(tag);
+        e->dBktOwner = std::move(own);
+        e->dBktRing = std::move(ring);
       }
       HIPCHK(hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(e->dBktTag + e->bktSlots), 0xFFFF0000u, need),
              "bucket tags init");  // every slot invalid (NewBucket)
@@ -834,7 +814,7 @@ static int flush_topology(lkf_engine *e) {
     for (const auto &d : e->pendStreams) anyNack = anyNack || d.nack;
     if (anyNack && !e->dNack) {  // nack.NewNACKQueue for the first Buffer with NACK feedback
       const lkf_cfg &c = e->cfg;
-      HIPCHK(dalloc(&e->dNack, e->maxStreams), "alloc nack queues");
+      HIPCHK(e->dNack.alloc(e->maxStreams), "alloc nack queues");
       HIPCHK(hipMemset(e->dNack, 0, size_t(e->maxStreams) * sizeof(NackState)), "nack queues reset");
       e->nackPairCap = uint32_t(std::min<uint64_t>(uint64_t(c.max_batch_pkts) * 8 + 4096, 1u << 30));
       // + every stream's block for the lane-parallel form (kernels.h kNackFastPairs)
@@ -844,26 +824,22 @@ static int flush_topology(lkf_engine *e) {
         return LKF_ENOSPC;
       }
       for (auto &g : e->ing) {
-        HIPCHK(dalloc(&g.nackInfo, c.max_batch_pkts), "alloc nack info");
-        HIPCHK(dalloc(&g.nackPairOff, c.max_batch_pkts), "alloc nack pair offsets");
-        HIPCHK(dalloc(&g.nackPairCnt, 1), "alloc nack pair count");
-        HIPCHK(dalloc(&g.nackPairs, pairsAll), "alloc nack pairs");
-        HIPCHK(dalloc(&g.nackIn, 3 * size_t(c.max_batch_pkts) + 64), "alloc nack inputs");
+        HIPCHK(g.nackInfo.alloc(c.max_batch_pkts), "alloc nack info");
+        HIPCHK(g.nackPairOff.alloc(c.max_batch_pkts), "alloc nack pair offsets");
+        HIPCHK(g.nackPairCnt.alloc(1), "alloc nack pair count");
+        HIPCHK(g.nackPairs.alloc(pairsAll), "alloc nack pairs");
+        HIPCHK(g.nackIn.alloc(3 * size_t(c.max_batch_pkts) + 64), "alloc nack inputs");
         HIPCHK(hipMemset(g.nackInfo, 0, size_t(c.max_batch_pkts) * sizeof(uint32_t)), "nack info reset");
         HIPCHK(hipMemset(g.nackPairCnt, 0, sizeof(uint32_t)), "nack count reset");
       }
-      e->dNackInfo = e->ing[e->ingPar].nackInfo;
-      e->dNackPairOff = e->ing[e->ingPar].nackPairOff;
-      e->dNackPairCnt = e->ing[e->ingPar].nackPairCnt;
-      e->dNackPairs = e->ing[e->ingPar].nackPairs;
-      HIPCHK(dalloc(&e->dNackRecPos, c.max_batch_pkts), "alloc nack positions");
-      HIPCHK(dalloc(&e->dNackPairPos, c.max_batch_pkts), "alloc nack pair positions");
-      HIPCHK(dalloc(&e->dNackTot, 2), "alloc nack totals");
+      HIPCHK(e->dNackRecPos.alloc(c.max_batch_pkts), "alloc nack positions");
+      HIPCHK(e->dNackPairPos.alloc(c.max_batch_pkts), "alloc nack pair positions");
+      HIPCHK(e->dNackTot.alloc(2), "alloc nack totals");
       const size_t npart = scan_state_words(c.max_batch_pkts);  // (the compaction's scan state)
-      HIPCHK(dalloc(&e->dNackPartA, npart), "alloc nack scan state");
+      HIPCHK(e->dNackPartA.alloc(npart), "alloc nack scan state");
       HIPCHK(hipMemset(e->dNackPartA, 0, npart * sizeof(uint64_t)), "nack scan state reset");
-      HIPCHK(dalloc(&e->dNackOut, c.max_batch_pkts), "alloc nack records");
-      HIPCHK(dalloc(&e->dNackPairsOut, pairsAll), "alloc nack pairs out");
+      HIPCHK(e->dNackOut.alloc(c.max_batch_pkts), "alloc nack records");
+      HIPCHK(e->dNackPairsOut.alloc(pairsAll), "alloc nack pairs out");
     }
     if (e->dNack) {  // each new queue: empty, the stream's initial RTT (0: defaultRtt)
       for (size_t i = 0; i < k; i++) {
@@ -906,161 +882,140 @@ lkf_engine *lkf_create(int hip_device, const lkf_cfg *cfg) {
     delete e;
     return nullptr;
   }
+  e->knobs = Knobs::from_env();
+  const Knobs &kn = e->knobs;
   const lkf_cfg &c = e->cfg;
   bool ok = true;
-  auto A = [&](hipError_t r) { ok = ok && (r == hipSuccess); };
+  auto A = [&](int r) { ok = ok && (r == int(hipSuccess)); };  // (a hipError_t, or DevBuf's int status)
   // decide is the batch-to-batch critical path: its waves should win CU slots
   // over the emit stage of the previous batch when both are resident.
   int leastPrio = 0, greatestPrio = 0;
   A(hipDeviceGetStreamPriorityRange(&leastPrio, &greatestPrio));
-  A(hipStreamCreateWithFlags(&e->own, hipStreamNonBlocking));
+  A(hipStreamCreateWithFlags(e->own.put(), hipStreamNonBlocking));
   // LKF_CU_SPLIT=D (A/B): of every 32 CUs, D run the prep/decide streams and the
   // rest the emit stream (hipExtStreamCreateWithCUMask), so the latency-bound
   // decide and the HBM-bound emit of consecutive batches stop competing for
   // the same CUs; 0 (default): all CUs, decide at high priority
-  int cuSplit = 0;
-  if (const char *v = getenv("LKF_CU_SPLIT")) cuSplit = atoi(v);
-  if (cuSplit > 0 && cuSplit < 32) {
-    int ncu = 256;
-    (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, hip_device);
-    const uint32_t words = uint32_t((ncu + 31) / 32);
-    std::vector<uint32_t> mA(words, 0), mB(words, 0);
-    for (int i = 0; i < ncu; i++) ((i % 32) < cuSplit ? mA : mB)[size_t(i / 32)] |= 1u << (i % 32);
-    A(hipExtStreamCreateWithCUMask(&e->decS, words, mA.data()));
-    A(hipExtStreamCreateWithCUMask(&e->prepS, words, mA.data()));
-    e->ingS = e->prepS;
-    A(hipExtStreamCreateWithCUMask(&e->emitS, words, mB.data()));
-    A(hipExtStreamCreateWithCUMask(&e->sendS, words, mB.data()));
+  if (kn.cuSplit > 0 && kn.cuSplit < 32) {
+    auto low = [&](int i) { return i < kn.cuSplit; };
+    auto high = [&](int i) { return i >= kn.cuSplit; };
+    A(cu_mask_stream(e->decS, hip_device, low));
+    A(cu_mask_stream(e->prepS, hip_device, low));
+    A(cu_mask_stream(e->emitS, hip_device, high));
+    A(cu_mask_stream(e->sendS, hip_device, high));
   } else {
     // LKF_PRIO=<decide><prep><emit><sender> (A/B): h(igh) or l(ow) each;
     // default "hhll" (the decide and prep chain ahead of emit for free CU slots)
-    const char *pr = getenv("LKF_PRIO");
-    auto prio = [&](int i, bool hi) { return (pr && int(strlen(pr)) > i) ? (pr[i] == 'h' ? greatestPrio : leastPrio)
-                                                                         : (hi ? greatestPrio : leastPrio); };
-    A(hipStreamCreateWithPriority(&e->decS, hipStreamNonBlocking, prio(0, true)));
-    A(hipStreamCreateWithPriority(&e->prepS, hipStreamNonBlocking, prio(1, true)));
-    e->ingS = e->prepS;
-    A(hipStreamCreateWithPriority(&e->emitS, hipStreamNonBlocking, prio(2, false)));
-    A(hipStreamCreateWithPriority(&e->sendS, hipStreamNonBlocking, prio(3, false)));
+    auto prio = [&](size_t i, bool hi) {
+      return kn.prio.size() > i ? (kn.prio[i] == 'h' ? greatestPrio : leastPrio) : (hi ? greatestPrio : leastPrio);
+    };
+    A(hipStreamCreateWithPriority(e->decS.put(), hipStreamNonBlocking, prio(0, true)));
+    A(hipStreamCreateWithPriority(e->prepS.put(), hipStreamNonBlocking, prio(1, true)));
+    A(hipStreamCreateWithPriority(e->emitS.put(), hipStreamNonBlocking, prio(2, false)));
+    A(hipStreamCreateWithPriority(e->sendS.put(), hipStreamNonBlocking, prio(3, false)));
   }
+  e->ingS.view(e->prepS);
   // LKF_SIDE_CUS=N (A/B): the NACK queues' side stream on N of every 32 CUs
   // (the last N of each XCD's), so its long latency-bound waves leave the
   // other CUs to emit; 0 (default): every CU
-  int sideCus = 0;
-  if (const char *v = getenv("LKF_SIDE_CUS")) sideCus = atoi(v);
-  if (sideCus > 0 && sideCus < 32) {
-    int ncu = 256;
-    (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, hip_device);
-    const uint32_t words = uint32_t((ncu + 31) / 32);
-    std::vector<uint32_t> m(words, 0);
-    for (int i = 0; i < ncu; i++)
-      if ((i % 32) >= 32 - sideCus) m[size_t(i / 32)] |= 1u << (i % 32);
-    A(hipExtStreamCreateWithCUMask(&e->sideS, words, m.data()));
-  } else {
-    A(hipStreamCreateWithFlags(&e->sideS, hipStreamNonBlocking));
-  }
-  A(hipEventCreateWithFlags(&e->inEv, hipEventDisableTiming));
-  A(hipEventCreateWithFlags(&e->bktEv, hipEventDisableTiming));
-  A(hipEventCreateWithFlags(&e->sideFork, hipEventDisableTiming));
+  if (kn.sideCus > 0 && kn.sideCus < 32)
+    A(cu_mask_stream(e->sideS, hip_device, [&](int i) { return i >= 32 - kn.sideCus; }));
+  else
+    A(hipStreamCreateWithFlags(e->sideS.put(), hipStreamNonBlocking));
+  A(e->inEv.create(false));
+  A(e->bktEv.create(false));
+  A(e->sideFork.create(false));
   for (int i = 0; i < 2; i++) {
-    A(hipEventCreateWithFlags(&e->sideDone[i], hipEventDisableTiming));
-    A(hipEventCreateWithFlags(&e->bktDone[i], hipEventDisableTiming));
+    A(e->sideDone[i].create(false));
+    A(e->bktDone[i].create(false));
   }
   e->cur = e->own;
-  A(dalloc(&e->dTracks, c.max_tracks));
-  A(dalloc(&e->dHot, c.max_downtracks));
-  A(dalloc(&e->dDTCum, c.max_downtracks));
-  A(dalloc(&e->dTwccCtrD, c.max_downtracks));
+  A(e->dTracks.alloc(c.max_tracks));
+  A(e->dHot.alloc(c.max_downtracks));
+  A(e->dDTCum.alloc(c.max_downtracks));
+  A(e->dTwccCtrD.alloc(c.max_downtracks));
   if (ok) A(hipMemset(e->dTwccCtrD, 0, size_t(c.max_downtracks) * sizeof(uint32_t)));
-  A(dalloc(&e->dSS, c.max_downtracks));
-  A(dalloc(&e->dSeqDDIdx, c.max_downtracks));
-  A(dalloc(&e->dSSGap, size_t(c.max_downtracks) * kGapWords));
-  A(dalloc(&e->dSSRing, size_t(c.max_downtracks) * kSnInfoSize));
-  A(dalloc(&e->dDTs, c.max_downtracks));
-  A(dalloc(&e->dRm, size_t(c.max_downtracks) * kRangeCap));
-  A(dalloc(&e->dVc, c.max_downtracks));
-  A(dalloc(&e->dSeq, size_t(c.max_downtracks) * c.seq_size));
+  A(e->dSS.alloc(c.max_downtracks));
+  A(e->dSeqDDIdx.alloc(c.max_downtracks));
+  A(e->dSSGap.alloc(size_t(c.max_downtracks) * kGapWords));
+  A(e->dSSRing.alloc(size_t(c.max_downtracks) * kSnInfoSize));
+  A(e->dDTs.alloc(c.max_downtracks));
+  A(e->dRm.alloc(size_t(c.max_downtracks) * kRangeCap));
+  A(e->dVc.alloc(c.max_downtracks));
+  A(e->dSeq.alloc(size_t(c.max_downtracks) * c.seq_size));
   e->srmCap = seqrm_cap(c.seq_size);
   e->srmStride = seqrm_stride(e->srmCap);
-  A(dalloc(&e->dSrm, size_t(c.max_downtracks) * e->srmStride));
-  A(dalloc(&e->dLastAlloc, c.max_downtracks));
-  A(dalloc(&e->dCum, kStatsWords));
-  A(dalloc(&e->dSticky, 4));
-  A(dalloc(&e->dPerm, c.max_downtracks));
-  A(dalloc(&e->dDTOffs, size_t(c.max_downtracks) * kDTOffsWords));
+  A(e->dSrm.alloc(size_t(c.max_downtracks) * e->srmStride));
+  A(e->dLastAlloc.alloc(c.max_downtracks));
+  A(e->dCum.alloc(kStatsWords));
+  A(e->dSticky.alloc(4));
+  A(e->dPerm.alloc(c.max_downtracks));
+  A(e->dDTOffs.alloc(size_t(c.max_downtracks) * kDTOffsWords));
   const size_t nparts = scan_state_words(c.max_downtracks);  // the slot and output scans' state
   for (auto &x : e->ctx) {
-    A(dalloc(&x.dTBegin, c.max_tracks));
-    A(dalloc(&x.dTEnd, c.max_tracks));
-    A(dalloc(&x.dTRuns, c.max_tracks));
-    A(dalloc(&x.dErr, 4));
-    A(dalloc(&x.dSlotBase, c.max_downtracks));
-    A(dalloc(&x.dPartA, nparts));
+    A(x.dTBegin.alloc(c.max_tracks));
+    A(x.dTEnd.alloc(c.max_tracks));
+    A(x.dTRuns.alloc(c.max_tracks));
+    A(x.dErr.alloc(4));
+    A(x.dSlotBase.alloc(c.max_downtracks));
+    A(x.dPartA.alloc(nparts));
     A(hipMemset(x.dPartA, 0, nparts * sizeof(uint64_t)));
-    A(dalloc(&x.dTot, 4));
-    A(dalloc(&x.dRecs, c.max_batch_tuples));
-    A(dalloc(&x.dFBase, c.max_downtracks));
-    A(dalloc(&x.dWide, c.max_batch_tuples));
-    A(dalloc(&x.dFwdCnt, c.max_downtracks));
-    A(dalloc(&x.dFwdBytes, c.max_downtracks));
-    A(dalloc(&x.dRecBase, c.max_downtracks));
-    A(dalloc(&x.dByteBase, c.max_downtracks));
-    A(dalloc(&x.dGFirst, c.max_out_pkts / 64 + 2));
-    A(dalloc(&x.dTwccBase, c.max_downtracks));
-    A(dalloc(&x.dLayerList, 3 * size_t(c.max_batch_pkts) + 64));
-    A(dalloc(&x.dLayerBefore, 3 * size_t(c.max_batch_pkts) + 64));
-    A(dalloc(&x.dLayerCnt, 3 * size_t(c.max_tracks)));
-    A(dalloc(&x.dOut, c.max_out_pkts));
-    A(dalloc(&x.dOutArena, c.max_out_bytes + 64));
-    A(dalloc(&x.dStats, size_t(kStatsWords) * (1 + kStatCopies)));
-    A(dalloc(&x.dPktsOwn, c.max_batch_pkts));
-    A(dalloc(&x.dArenaOwn, c.max_batch_arena + 64));
-    A(dalloc(&x.dRawPkts, c.max_batch_pkts));
-    A(dalloc(&x.dBktStore, c.max_batch_pkts));
-    A(dalloc(&x.dDesc, 1));
-    A(dalloc(&x.dEvents, 4096));
-    A(dalloc(&x.dEvLane, 4096));
-    x.evCap = x.evLaneCap = 4096;
-    A(hipEventCreateWithFlags(&x.decided, hipEventDisableTiming));
-    A(hipEventCreateWithFlags(&x.prepped, hipEventDisableTiming));
-    A(hipEventCreateWithFlags(&x.pulled, hipEventDisableTiming));
-    A(hipEventCreateWithFlags(&x.emitted, hipEventDisableTiming));
-    A(hipEventCreateWithFlags(&x.ingested, hipEventDisableTiming));
-    A(dalloc(&x.dITotal, 2));
-    A(hipEventCreateWithFlags(&x.sent, hipEventDisableTiming));
+    A(x.dTot.alloc(4));
+    A(x.dRecs.alloc(c.max_batch_tuples));
+    A(x.dFBase.alloc(c.max_downtracks));
+    A(x.dWide.alloc(c.max_batch_tuples));
+    A(x.dFwdCnt.alloc(c.max_downtracks));
+    A(x.dFwdBytes.alloc(c.max_downtracks));
+    A(x.dRecBase.alloc(c.max_downtracks));
+    A(x.dByteBase.alloc(c.max_downtracks));
+    A(x.dGFirst.alloc(c.max_out_pkts / 64 + 2));
+    A(x.dTwccBase.alloc(c.max_downtracks));
+    A(x.dLayerList.alloc(3 * size_t(c.max_batch_pkts) + 64));
+    A(x.dLayerBefore.alloc(3 * size_t(c.max_batch_pkts) + 64));
+    A(x.dLayerCnt.alloc(3 * size_t(c.max_tracks)));
+    A(x.dOut.alloc(c.max_out_pkts));
+    A(x.dOutArena.alloc(c.max_out_bytes + 64));
+    A(x.dStats.alloc(size_t(kStatsWords) * (1 + kStatCopies)));
+    A(x.dPktsOwn.alloc(c.max_batch_pkts));
+    A(x.dArenaOwn.alloc(c.max_batch_arena + 64));
+    A(x.dRawPkts.alloc(c.max_batch_pkts));
+    A(x.dBktStore.alloc(c.max_batch_pkts));
+    A(x.dDesc.alloc(1));
+    A(x.dEvents.alloc(4096));
+    A(x.dEvLane.alloc(4096));
+    A(x.decided.create(false));
+    A(x.prepped.create(false));
+    A(x.pulled.create(false));
+    A(x.emitted.create(false));
+    A(x.ingested.create(false));
+    A(x.dITotal.alloc(2));
+    A(x.sent.create(false));
   }
   for (auto &r : e->ring)
-    for (auto &ev : r) A(hipEventCreate(&ev));
+    for (auto &ev : r) A(ev.create(true));
   e->maxStreams = c.max_streams ? c.max_streams : 3 * c.max_tracks;
-  A(dalloc(&e->dStreams, e->maxStreams));
-  A(dalloc(&e->dStreamHot, e->maxStreams));
-  A(dalloc(&e->dHist, size_t(e->maxStreams) * kHistWords));
-  A(dalloc(&e->dRxGap, size_t(e->maxStreams) * kGapWords));
-  A(dalloc(&e->dStreamRings, size_t(e->maxStreams) * kRangeCap));
+  A(e->dStreams.alloc(e->maxStreams));
+  A(e->dStreamHot.alloc(e->maxStreams));
+  A(e->dHist.alloc(size_t(e->maxStreams) * kHistWords));
+  A(e->dRxGap.alloc(size_t(e->maxStreams) * kGapWords));
+  A(e->dStreamRings.alloc(size_t(e->maxStreams) * kRangeCap));
   for (auto &g : e->ing) {
-    A(dalloc(&g.parsed, c.max_batch_pkts));
-    A(dalloc(&g.flows, c.max_batch_pkts));
-    A(dalloc(&g.fwd, c.max_batch_pkts));
-    A(dalloc(&g.tBegin, c.max_tracks));
-    A(dalloc(&g.tEnd, c.max_tracks));
-    A(dalloc(&g.list, 3 * size_t(c.max_batch_pkts) + 64));
-    A(dalloc(&g.listCnt, 3 * size_t(c.max_tracks)));
+    A(g.parsed.alloc(c.max_batch_pkts));
+    A(g.flows.alloc(c.max_batch_pkts));
+    A(g.fwd.alloc(c.max_batch_pkts));
+    A(g.tBegin.alloc(c.max_tracks));
+    A(g.tEnd.alloc(c.max_tracks));
+    A(g.list.alloc(3 * size_t(c.max_batch_pkts) + 64));
+    A(g.listCnt.alloc(3 * size_t(c.max_tracks)));
   }
-  e->dParsed = e->ing[0].parsed;
-  e->dFlows = e->ing[0].flows;
-  A(dalloc(&e->dTwcc, c.max_batch_pkts));
-  e->dFwdFlag = e->ing[0].fwd;
-  A(dalloc(&e->dPos, c.max_batch_pkts));
+  A(e->dTwcc.alloc(c.max_batch_pkts));
+  A(e->dPos.alloc(c.max_batch_pkts));
   const size_t ipart = scan_state_words(c.max_batch_pkts);  // the ingest scan's state
-  A(dalloc(&e->dIPartA, ipart));
+  A(e->dIPartA.alloc(ipart));
   A(hipMemset(e->dIPartA, 0, ipart * sizeof(uint64_t)));
-  A(dalloc(&e->dITotal, 2));
-  e->dITBegin = e->ing[0].tBegin;
-  e->dITEnd = e->ing[0].tEnd;
-  A(dalloc(&e->dITRuns, c.max_tracks));
-  A(dalloc(&e->dIErr, 4));
-  e->dIList = e->ing[0].list;
-  e->dIListCnt = e->ing[0].listCnt;
+  A(e->dITotal.alloc(2));
+  A(e->dITRuns.alloc(c.max_tracks));
+  A(e->dIErr.alloc(4));
   if (ok) {
     A(hipMemset(e->dSeq, 0, size_t(c.max_downtracks) * c.seq_size * sizeof(SeqMeta)));
     // Every persistent table starts zeroed: hipMalloc hands back memory an
@@ -1106,27 +1061,18 @@ lkf_engine *lkf_create(int hip_device, const lkf_cfg *cfg) {
   (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, hip_device);
   // emit is grid-stride with one-wave workgroups: 24 waves per CU saturate
   // HBM and leave wave slots for the next batch's decide stage.
-  int perCU = 24;
-  if (const char *v = getenv("LKF_EMIT_WG_PER_CU")) perCU = std::max(1, atoi(v));
-  if (const char *v = getenv("LKF_EMIT_PERSISTENT")) e->emitPersistent = atoi(v) != 0;
-  if (const char *v = getenv("LKF_EMIT_LDS")) e->emitLdsPad = uint32_t(std::max(0, atoi(v)));  // (A/B)
-  if (const char *v = getenv("LKF_EMIT_CAP_FANOUT")) e->emitCapFanout = uint32_t(std::max(0, atoi(v)));
-  if (const char *v = getenv("LKF_DECIDE_K")) e->decideK = uint32_t(std::min(8, std::max(0, atoi(v))));
-  e->emitGrid = uint32_t(cus) * uint32_t(perCU);
-  if (const char *v = getenv("LKF_HOST_PROF")) e->hostProf = atoi(v) != 0;
-  if (const char *v = getenv("LKF_GRAPH")) e->useGraph = atoi(v) != 0;
-  if (const char *v = getenv("LKF_DEBUG_DD")) e->debugDD = atoi(v) != 0;
+  e->emitGrid = uint32_t(cus) * uint32_t(kn.emitWgPerCU);
   return e;
 }
 
 void lkf_destroy(lkf_engine *e) {
   if (!e) return;
-  if (e->hostProf && e->hp[5] > 0)
+  if (e->knobs.hostProf && e->hp[5] > 0)
     fprintf(stderr,
             "lkf host ms/run: pre %.4f stage-wait %.4f csr %.4f copies %.4f launches %.4f total %.4f (%d runs)\n",
             e->hp[0] / e->hp[5], e->hp[1] / e->hp[5], e->hp[2] / e->hp[5], e->hp[6] / e->hp[5],
             e->hp[3] / e->hp[5], e->hp[4] / e->hp[5], int(e->hp[5]));
-  if (e->hostProf && e->hp[8] > 0)
+  if (e->knobs.hostProf && e->hp[8] > 0)
     fprintf(stderr, "lkf host ms/ingest: %.4f (%d ingests: the launches of the Buffer.calc chain, no host wait)\n",
             e->hp[7] / e->hp[8], int(e->hp[8]));
   (void)hipSetDevice(e->dev);
@@ -1140,100 +1086,7 @@ void lkf_destroy(lkf_engine *e) {
   if (e->sideS) (void)hipStreamSynchronize(e->sideS);  // (NACK queues)
   if (e->d2hS) (void)hipStreamSynchronize(e->d2hS);    // (asynchronous drains)
   (void)hipDeviceSynchronize();                        // (anything else queued before the buffers go)
-  for (void *p : {static_cast<void *>(e->dNacks), static_cast<void *>(e->dNackG), static_cast<void *>(e->dNackValid),
-                  static_cast<void *>(e->dRtx), static_cast<void *>(e->dRtxSrc), static_cast<void *>(e->dRtxLen),
-                  static_cast<void *>(e->dRtxOff), static_cast<void *>(e->dRtxIn), static_cast<void *>(e->dRtxOut),
-                  static_cast<void *>(e->dSrm), static_cast<void *>(e->dPadReq), static_cast<void *>(e->dPadOff),
-                  static_cast<void *>(e->dPadCnt), static_cast<void *>(e->dPadOut), static_cast<void *>(e->dPadArena),
-                  static_cast<void *>(e->dLastAlloc), static_cast<void *>(e->dAllocReq), static_cast<void *>(e->dAllocCapacity),
-                  static_cast<void *>(e->dRedEnc), static_cast<void *>(e->dRedDec), static_cast<void *>(e->dTrk),
-                  static_cast<void *>(e->dTrkIds), static_cast<void *>(e->dTrkOut),
-                  static_cast<void *>(e->red.in), static_cast<void *>(e->red.out), static_cast<void *>(e->red.inArena),
-                  static_cast<void *>(e->red.outArena), static_cast<void *>(e->red.g), static_cast<void *>(e->red.cnt),
-                  static_cast<void *>(e->red.map), static_cast<void *>(e->red.off),
-                  static_cast<void *>(e->dAllocOut)})
-    if (p) (void)dfree(p);
-  void *ptrs[] = {e->dTracks,  e->dHot,  e->dDTCum, e->dDTs,    e->dRm,  e->dVc,  e->dSeq,    e->dSched,
-                  e->dWaveTrack, e->dCum, e->dSticky, e->dSns, e->dSeqOut, e->dSeqN, e->dPerm, e->dDTOffs,
-                  e->dStreams, e->dStreamHot, e->dHist, e->dRxGap, e->dStreamRings,
-                  e->dTwcc, e->dBkt, e->dBktTag, e->dBktOwner, e->dBktRing, e->dBktStream, e->dBktSn,
-                  e->dPos, e->dIPartA, e->dIPartB, e->dITotal, e->dITRuns, e->dIErr,
-                  e->dRoomPartOff, e->dPartId, e->dPartMicOff, e->dMics, e->dRoomId, e->dSpkSlots,
-                  e->dSpkCounts, e->dNack, e->dRsRowEng, e->dRsSlotOff, e->dRsSlotDts, e->dRsSlotSub,
-                  e->dNackRecPos, e->dNackPairPos, e->dNackTot, e->dNackOut, e->dNackPairsOut, e->dNackPartA,
-                  e->dNackPartB,
-                  e->dSS, e->dSSGap, e->dSSRing, e->dSSList, e->dSSGroups, e->dSeqDD, e->dSeqDDIdx,
-                  e->dSeqDDList, e->dRtxDD, e->dProv, e->dProvReq, e->dProvGroups, e->dProvOut,
-                  e->dDDTrk, e->dTrackDDTrk, e->dDDTrkIds, e->dDDTrkOut, e->dTwccCtrD,
-                  e->dTwccCtrT, e->dTwccTOff, e->dTwccTList};
-  for (void *p : ptrs)
-    if (p) (void)dfree(p);
-  for (void *p : {static_cast<void *>(e->dDDStruct), static_cast<void *>(e->dDDTrack),
-                  static_cast<void *>(e->dDDState), static_cast<void *>(e->dDDIng),
-                  static_cast<void *>(e->dDDIngStruct), static_cast<void *>(e->dIngDD)})
-    if (p) (void)dfree(p);
-  for (auto &r : e->protRing)
-    for (auto &ev : r)
-      if (ev) (void)hipEventDestroy(ev);
-  for (void *p : {static_cast<void *>(e->dTransports), static_cast<void *>(e->dSrtpKeys),
-                  static_cast<void *>(e->dAesTab), static_cast<void *>(e->dSrtpDT)})
-    if (p) (void)dfree(p);
-  for (auto &x : e->ctx) {
-    if (x.dProt) (void)dfree(x.dProt);
-    for (void *p : {static_cast<void *>(x.dDDIn), static_cast<void *>(x.dDDPkt), static_cast<void *>(x.dDDArena),
-                    static_cast<void *>(x.dDDUsed), static_cast<void *>(x.dDDSpill)})
-      if (p) (void)dfree(p);
-    void *q[] = {x.dTBegin, x.dTEnd,     x.dTRuns,   x.dErr,      x.dSlotBase, x.dPartA,
-                 x.dPartB,  x.dTot,      x.dRecs,  x.dFBase,  x.dWide,  x.dFwdCnt,   x.dFwdBytes, x.dRecBase,
-                 x.dByteBase, x.dOut,    x.dOutArena, x.dStats,   x.dPktsOwn,  x.dArenaOwn,
-                 x.dRawPkts, x.dBktStore, x.dGFirst, x.dLayerList, x.dLayerBefore, x.dLayerCnt, x.dEvents, x.dEvOff, x.dEvLane, x.dTwccBase};
-    for (void *p : q)
-      if (p) (void)dfree(p);
-    if (x.decided) (void)hipEventDestroy(x.decided);
-    if (x.prepped) (void)hipEventDestroy(x.prepped);
-    if (x.pulled) (void)hipEventDestroy(x.pulled);
-    if (x.emitted) (void)hipEventDestroy(x.emitted);
-    if (x.ingested) (void)hipEventDestroy(x.ingested);
-    if (x.dITotal) (void)dfree(x.dITotal);
-    if (x.sent) (void)hipEventDestroy(x.sent);
-  }
-  for (auto &r : e->ring)
-    for (auto &ev : r)
-      if (ev) (void)hipEventDestroy(ev);
-  for (auto &x : e->ctx) {
-    stage_free(&x.stage, &x.stageDev);
-    for (auto &g : x.gPrep)
-      if (g) (void)hipGraphExecDestroy(g);
-    if (x.gCtl) (void)hipGraphExecDestroy(x.gCtl);
-    if (x.gScan) (void)hipGraphExecDestroy(x.gScan);
-    if (x.dDesc) (void)dfree(x.dDesc);
-  }
-  if (e->bounce) (void)hipHostFree(e->bounce);
-  if (e->inEv) (void)hipEventDestroy(e->inEv);
-  if (e->bktEv) (void)hipEventDestroy(e->bktEv);
-  for (hipEvent_t ev : {e->rsSpk, e->rsDec})
-    if (ev) (void)hipEventDestroy(ev);
-  if (e->sideFork) (void)hipEventDestroy(e->sideFork);
-  for (int i = 0; i < 2; i++) {
-    if (e->sideDone[i]) (void)hipEventDestroy(e->sideDone[i]);
-    if (e->bktDone[i]) (void)hipEventDestroy(e->bktDone[i]);
-  }
-  for (auto &g : e->ing)
-    for (void *p : {static_cast<void *>(g.parsed), static_cast<void *>(g.flows), static_cast<void *>(g.fwd),
-                    static_cast<void *>(g.tBegin), static_cast<void *>(g.tEnd), static_cast<void *>(g.list),
-                    static_cast<void *>(g.listCnt), static_cast<void *>(g.nackInfo), static_cast<void *>(g.nackPairOff),
-                    static_cast<void *>(g.nackPairCnt), static_cast<void *>(g.nackPairs),
-                    static_cast<void *>(g.nackIn)})
-      if (p) (void)dfree(p);
-  if (e->sideS && e->sideS != e->sendS) (void)hipStreamDestroy(e->sideS);
-  if (e->emitS) (void)hipStreamDestroy(e->emitS);
-  if (e->sendS) (void)hipStreamDestroy(e->sendS);
-  if (e->decS) (void)hipStreamDestroy(e->decS);
-  if (e->prepS) (void)hipStreamDestroy(e->prepS);
-  if (e->ingS && e->ingS != e->prepS) (void)hipStreamDestroy(e->ingS);
-  if (e->own) (void)hipStreamDestroy(e->own);
-  if (e->d2hS) (void)hipStreamDestroy(e->d2hS);
-  delete e;
+  delete e;  // the members release every buffer, event, graph exec and stream (streams last)
 }
 
 int32_t lkf_add_track(lkf_engine *e, const lkf_track_params *p) {
@@ -1565,12 +1418,10 @@ static int rebuild_sched(lkf_engine *e) {
   const size_t nl = e->sched.size();
   int rc = drain_streams(e);  // queued runs still read the previous schedule
   if (rc) return rc;
-  if (nl + 1 > e->schedCap) {
-    if (e->dSched) HIPCHK(dfree(e->dSched), "free sched");
-    if (e->dWaveTrack) HIPCHK(dfree(e->dWaveTrack), "free wavetrack");
-    e->schedCap = nl + 1 + 4096;
-    HIPCHK(dalloc(&e->dSched, e->schedCap), "alloc sched");
-    HIPCHK(dalloc(&e->dWaveTrack, e->schedCap + 1), "alloc wavetrack");
+  if (nl + 1 > e->dSched.cap() || nl + 2 > e->dWaveTrack.cap()) {
+    release_all(e->dSched, e->dWaveTrack);
+    HIPCHK(e->dSched.alloc(nl + 1 + 4096), "alloc sched");
+    HIPCHK(e->dWaveTrack.alloc(nl + 2 + 4096), "alloc wavetrack");
   }
   // output order: by track, then DownTrack handle (every DownTrack, active or not)
   {
@@ -1612,27 +1463,22 @@ static int rebuild_twcc(lkf_engine *e) {
     flat.insert(flat.end(), lst[t].begin(), lst[t].end());
   }
   off[nt] = uint32_t(flat.size());
-  if (nt > e->twccTCap || !e->dTwccCtrT) {  // grow the transport counters (first: before any transport), keeping the old ones
-    const uint32_t cap = std::max<uint32_t>(nt, 2 * e->twccTCap + 64);
-    uint32_t *c = nullptr, *o = nullptr;
-    HIPCHK(dalloc(&c, cap), "alloc twcc counters");
+  // grow the transport counters (first: before any transport), keeping the old ones
+  // (both new buffers first: a failed allocation leaves the old counters and offsets as they were)
+  if (nt > e->dTwccCtrT.cap() || !e->dTwccCtrT) {
+    const uint32_t old = uint32_t(e->dTwccCtrT.cap());
+    const uint32_t cap = std::max<uint32_t>(nt, 2 * old + 64);
+    DevBuf<uint32_t> c, o;
+    HIPCHK(c.alloc(cap), "alloc twcc counters");
+    HIPCHK(o.alloc(cap + 1), "alloc twcc offsets");
     HIPCHK(hipMemset(c, 0, size_t(cap) * sizeof(uint32_t)), "twcc counters reset");
-    if (e->dTwccCtrT) {
-      HIPCHK(hipMemcpy(c, e->dTwccCtrT, size_t(e->twccTCap) * sizeof(uint32_t), hipMemcpyDeviceToDevice),
+    if (e->dTwccCtrT)
+      HIPCHK(hipMemcpy(c, e->dTwccCtrT, size_t(old) * sizeof(uint32_t), hipMemcpyDeviceToDevice),
              "twcc counters move");
-      HIPCHK(dfree(e->dTwccCtrT), "free twcc counters");
-    }
-    if (e->dTwccTOff) HIPCHK(dfree(e->dTwccTOff), "free twcc offsets");
-    HIPCHK(dalloc(&o, cap + 1), "alloc twcc offsets");
-    e->dTwccCtrT = c;
-    e->dTwccTOff = o;
-    e->twccTCap = cap;
+    e->dTwccCtrT = std::move(c);
+    e->dTwccTOff = std::move(o);
   }
-  if (flat.size() > e->twccListCap || !e->dTwccTList) {
-    if (e->dTwccTList) HIPCHK(dfree(e->dTwccTList), "free twcc lists");
-    e->twccListCap = uint32_t(std::max<size_t>(flat.size(), 1024));
-    HIPCHK(dalloc(&e->dTwccTList, e->twccListCap), "alloc twcc lists");
-  }
+  HIPCHK(e->dTwccTList.reserve(std::max<size_t>(flat.size(), 1), 1024), "alloc twcc lists");  // (allocated even when empty)
   HIPCHK(hipMemcpy(e->dTwccTOff, off.data(), off.size() * sizeof(uint32_t), hipMemcpyHostToDevice), "twcc offsets");
   if (!flat.empty())
     HIPCHK(hipMemcpy(e->dTwccTList, flat.data(), flat.size() * sizeof(uint32_t), hipMemcpyHostToDevice), "twcc lists");
@@ -1725,52 +1571,28 @@ int lkf_run(lkf_engine *e, void *stream) {
     }
     e->trkOps.clear();
   }
-  auto &ka = e->sortA, &kb = e->sortB;  // (lane, pending index)
-  ka.clear();
-  for (uint32_t i = 0; i < uint32_t(e->pending.size()); i++) {
-    const int l = e->dtLane[e->pending[i].dt];
-    if (l >= 0) ka.push_back({uint32_t(l), i});  // ops for removed DownTracks are dropped
-  }
-  const size_t nev = ka.size();
-  kb.resize(nev);
-  for (uint32_t shift = 0; shift < 32 && (nl >> shift) > 0; shift += 8) {  // stable LSD passes
-    uint32_t cnt[257] = {0};
-    for (auto &k : ka) cnt[((k.first >> shift) & 0xff) + 1]++;
-    for (int d = 0; d < 256; d++) cnt[d + 1] += cnt[d];
-    for (auto &k : ka) kb[cnt[(k.first >> shift) & 0xff]++] = k;
-    ka.swap(kb);
-  }
-  if (nev > x.stageCap || !x.stage) {  // (graphs captured with the old staging are re-captured)
+  const size_t nev = e->csr.sort(e->pending.data(), e->pending.size(), e->dtLane.data(), nl);  // (ctl_csr.h)
+  if (nev > x.stageCap || !x.stage.host) {  // (graphs captured with the old staging are re-captured)
     // the queued pull of this context's previous run may still read the old
     // staging, and its graphs are destroyed when re-captured: drain first
-    if (x.stage) {
+    if (x.stage.host) {
       if (int rc = drain_streams(e)) return rc;
     }
-    stage_free(&x.stage, &x.stageDev);
-    x.stageCap = uint32_t(std::max<size_t>(2 * nev, 4096));
-    HIPCHK(stage_alloc(&x.stage, &x.stageDev, sizeof(RunDesc) + size_t(x.stageCap) * (sizeof(DevEvent) + 4)),
-           "alloc stage");
+    x.stage.reset();
+    x.stageCap = 0;  // (set once the allocation has succeeded: a failed one is retried by the next run)
+    const uint32_t cap = uint32_t(std::max<size_t>(2 * nev, 4096));
+    HIPCHK(x.stage.alloc(sizeof(RunDesc) + size_t(cap) * (sizeof(DevEvent) + 4)), "alloc stage");
+    x.stageCap = cap;
     x.gPrepEpoch[0] = x.gPrepEpoch[1] = 0;
     x.gCtlEpoch = 0;
   }
-  DevEvent *evs = reinterpret_cast<DevEvent *>(x.stage + sizeof(RunDesc));
-  uint32_t *lanes = reinterpret_cast<uint32_t *>(x.stage + sizeof(RunDesc) + size_t(x.stageCap) * sizeof(DevEvent));
-  for (size_t i = 0; i < nev; i++) {
-    evs[i] = e->pending[ka[i].second].ev;
-    lanes[i] = ka[i].first;
-    if (i && ka[i - 1].first == ka[i].first && evs[i].at < evs[i - 1].at) {
-      const DevEvent v = evs[i];  // queued out of at_pkt order: stable insertion within the lane
-      size_t j = i;
-      while (j > 0 && lanes[j - 1] == ka[i].first && evs[j - 1].at > v.at) {
-        evs[j] = evs[j - 1];
-        j--;
-      }
-      evs[j] = v;
-    }
-  }
+  DevEvent *evs = reinterpret_cast<DevEvent *>(x.stage.host + sizeof(RunDesc));
+  uint32_t *lanes =
+      reinterpret_cast<uint32_t *>(x.stage.host + sizeof(RunDesc) + size_t(x.stageCap) * sizeof(DevEvent));
+  e->csr.emit(e->pending.data(), evs, lanes);
   e->pending.clear();
   {
-    RunDesc &h = *reinterpret_cast<RunDesc *>(x.stage);
+    RunDesc &h = *reinterpret_cast<RunDesc *>(x.stage.host);
     std::memset(&h, 0, sizeof(h));
     h.pkts = reinterpret_cast<uint64_t>(e->curPkts);
     h.arena = reinterpret_cast<uint64_t>(e->curArena);
@@ -1781,7 +1603,7 @@ int lkf_run(lkf_engine *e, void *stream) {
     h.evCap = x.stageCap;
   }
   const auto tp25 = clk::now();
-  if (nev > x.evCap || size_t(nl) + 1 > x.evOffCap || nev > x.evLaneCap) {
+  if (nev > x.dEvents.cap() || size_t(nl) + 1 > x.dEvOff.cap() || nev > x.dEvLane.cap()) {
     // this context's op buffers: its previous run (n-3) must be done with them.
     // ps waits on that run's "emitted" event above, so draining ps covers its
     // prep, decide and emit stages (the lane list is read by k_ev_offsets on ps,
@@ -1789,21 +1611,9 @@ int lkf_run(lkf_engine *e, void *stream) {
     // (every stream: the pull graph on the engine's own stream reads them too,
     // and the graphs captured with them are destroyed below)
     if (int rc = drain_streams(e)) return rc;
-    if (nev > x.evCap) {
-      if (x.dEvents) HIPCHK(dfree(x.dEvents), "free events");
-      x.evCap = std::max<uint64_t>(2 * nev, 4096);
-      HIPCHK(dalloc(&x.dEvents, x.evCap), "alloc events");
-    }
-    if (size_t(nl) + 1 > x.evOffCap) {
-      if (x.dEvOff) HIPCHK(dfree(x.dEvOff), "free evoff");
-      x.evOffCap = size_t(nl) + 1 + 4096;
-      HIPCHK(dalloc(&x.dEvOff, x.evOffCap), "alloc evoff");
-    }
-    if (nev > x.evLaneCap) {
-      if (x.dEvLane) HIPCHK(dfree(x.dEvLane), "free evlane");
-      x.evLaneCap = std::max<uint64_t>(2 * nev, 4096);
-      HIPCHK(dalloc(&x.dEvLane, x.evLaneCap), "alloc evlane");
-    }
+    if (nev > x.dEvents.cap()) HIPCHK(x.dEvents.reserve(2 * nev, 4096), "alloc events");
+    if (size_t(nl) + 1 > x.dEvOff.cap()) HIPCHK(x.dEvOff.alloc(size_t(nl) + 1 + 4096), "alloc evoff");
+    if (nev > x.dEvLane.cap()) HIPCHK(x.dEvLane.reserve(2 * nev, 4096), "alloc evlane");
     x.gPrepEpoch[0] = x.gPrepEpoch[1] = 0;
     x.gCtlEpoch = 0;
   }
@@ -1811,7 +1621,7 @@ int lkf_run(lkf_engine *e, void *stream) {
 
   // ---- prep stage (prep stream): the pull, per-batch init, track ranges,
   // slot scan, layer index, tracker observe, DD decode
-  hipEvent_t *rg = e->ring[e->nRuns % lkf_engine::kRing];
+  Event *rg = e->ring[e->nRuns % lkf_engine::kRing];
   if (!e->ingestStarted) HIPCHK(hipEventRecord(rg[0], ps), "event");  // else: recorded ahead of the ingest
   e->ingestStarted = false;
   // the control-op pull (k_h2d: the run descriptor and the ops from the
@@ -1821,7 +1631,7 @@ int lkf_run(lkf_engine *e, void *stream) {
   hipStream_t cs = e->own;
   if (x.used) HIPCHK(hipStreamWaitEvent(cs, x.emitted, 0), "wait emit (pull)");
   auto ctl = [&]() -> int {
-    HIPCHK(launch_h2d(cs, x.stageDev, x.dDesc, x.dEvents, x.dEvLane), "event pull");
+    HIPCHK(launch_h2d(cs, x.stage.dev, x.dDesc, x.dEvents, x.dEvLane), "event pull");
     HIPCHK(launch_ev_offsets(cs, x.dEvLane, x.dDesc, nl, x.dEvOff), "event offsets");
     return LKF_OK;
   };
@@ -1833,7 +1643,7 @@ int lkf_run(lkf_engine *e, void *stream) {
       HIPCHK(launch_track_ranges(ps, x.dDesc, e->cfg.max_batch_pkts, nt, x.dTBegin, x.dTEnd, x.dTRuns, x.dErr),
              "track_ranges");
     }
-    HIPCHK(launch_scan(ps, 0, e->dDTs, x.dTBegin, x.dTEnd, nullptr, nullptr, nd, x.dPartA, x.dPartB, x.dSlotBase,
+    HIPCHK(launch_scan(ps, 0, e->dDTs, x.dTBegin, x.dTEnd, nullptr, nullptr, nd, x.dPartA, nullptr, x.dSlotBase,
                        nullptr, x.dTot + 0, nullptr, nullptr),
            "slot scan");
     HIPCHK(launch_layer_index(ps, x.dDesc, x.dTBegin, x.dTEnd, nt, e->cfg.max_batch_pkts, x.dLayerList,
@@ -1844,7 +1654,7 @@ int lkf_run(lkf_engine *e, void *stream) {
     if (e->ddAlloc) {  // dependency descriptors of this batch (track structure rings advance in order)
       HIPCHK(launch_dd_decode(ps, x.dDesc, x.dTBegin, x.dTEnd, e->dTracks, nt, e->dDDStruct, e->dDDTrack, x.dDDPkt,
                               x.dErr, e->nDDTrk ? e->dTrackDDTrk : nullptr, e->dDDTrk, x.dDDSpill,
-                              reinterpret_cast<uint32_t *>(x.dDDUsed + 1), e->ddSpillCap),
+                              reinterpret_cast<uint32_t *>(x.dDDUsed + 1), uint32_t(x.dDDSpill.cap())),
              "dd decode");
     }
     return LKF_OK;
@@ -1854,33 +1664,32 @@ int lkf_run(lkf_engine *e, void *stream) {
     // on the low-priority emit stream these small kernels queued behind the
     // next batch's decide waves and were on the emit chain's critical path
     HIPCHK(launch_stats_reduce(st, x.dStats), "stats reduce");
-    HIPCHK(launch_scan(st, 1, e->dDTs, nullptr, nullptr, x.dFwdCnt, x.dFwdBytes, nd, x.dPartA, x.dPartB, x.dRecBase,
+    HIPCHK(launch_scan(st, 1, e->dDTs, nullptr, nullptr, x.dFwdCnt, x.dFwdBytes, nd, x.dPartA, nullptr, x.dRecBase,
                        x.dByteBase, x.dTot + 2, x.dTot + 3, e->dPerm, x.dGFirst, e->cfg.max_out_pkts),
            "out scan");
     return LKF_OK;
   };
   // (re)captures a stage as a graph on stream st: the captured launches are the
   // same as the direct ones
-  auto capture = [&](hipStream_t st, hipGraphExec_t &g, auto body) -> int {
+  auto capture = [&](hipStream_t st, GraphExec &g, auto body) -> int {
     // an exec is destroyed only once its last launch (on st, this context's
     // previous run) has finished: HIP may release its kernel arguments at once
     if (g) {
       HIPCHK(hipStreamSynchronize(st), "graph idle");
-      HIPCHK(hipGraphExecDestroy(g), "graph destroy");
+      HIPCHK(g.destroy(), "graph destroy");
     }
-    g = nullptr;
     HIPCHK(hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed), "begin capture");
     const int rc = body();
     hipGraph_t graph = nullptr;
     const hipError_t r = hipStreamEndCapture(st, &graph);
     if (rc) return rc;
     HIPCHK(r, "end capture");
-    const hipError_t ri = hipGraphInstantiate(&g, graph, nullptr, nullptr, 0);
+    const hipError_t ri = hipGraphInstantiate(&g.h, graph, nullptr, nullptr, 0);
     (void)hipGraphDestroy(graph);
     HIPCHK(ri, "graph instantiate");
     return LKF_OK;
   };
-  if (e->useGraph) {
+  if (e->knobs.useGraph) {
     if (x.gCtlEpoch != e->epoch || !x.gCtl) {
       const int rc = capture(cs, x.gCtl, ctl);
       if (rc) return rc;
@@ -1893,7 +1702,7 @@ int lkf_run(lkf_engine *e, void *stream) {
   }
   HIPCHK(hipEventRecord(x.pulled, cs), "event");
   HIPCHK(hipStreamWaitEvent(ps, x.pulled, 0), "wait pull");
-  if (e->useGraph) {
+  if (e->knobs.useGraph) {
     const int fi = prepDone ? 1 : 0;
     if (x.gPrepEpoch[fi] != e->epoch || !x.gPrep[fi]) {
       const int rc = capture(ps, x.gPrep[fi], prep);
@@ -1906,12 +1715,12 @@ int lkf_run(lkf_engine *e, void *stream) {
     if (rc) return rc;
   }
   HIPCHK(hipEventRecord(x.prepped, ps), "event");
-  if (e->debugDD && e->ddAlloc) {  // LKF_DEBUG_DD=1 (diagnostic): the context's DD cursor after its prep
+  if (e->knobs.debugDD && e->ddAlloc) {  // LKF_DEBUG_DD=1 (diagnostic): the context's DD cursor after its prep
     HIPCHK(hipStreamSynchronize(ps), "debug sync");
     uint64_t u[2] = {0, 0};
     HIPCHK(hipMemcpy(u, x.dDDUsed, sizeof(u), hipMemcpyDeviceToHost), "debug copy");
     fprintf(stderr, "[lkf dd] run %llu ctx %d after prep: cursor %llu spill %llu graph %d epoch %llu/%llu\n",
-            (unsigned long long)e->nRuns, ci, (unsigned long long)u[0], (unsigned long long)u[1], int(e->useGraph),
+            (unsigned long long)e->nRuns, ci, (unsigned long long)u[0], (unsigned long long)u[1], int(e->knobs.useGraph),
             (unsigned long long)x.gPrepEpoch[prepDone ? 1 : 0], (unsigned long long)e->epoch);
   }
   HIPCHK(hipStreamWaitEvent(s, x.prepped, 0), "wait prep");
@@ -1956,8 +1765,8 @@ int lkf_run(lkf_engine *e, void *stream) {
   // Several DownTracks per decide wave when the batch is short (a 10-20 ms
   // tick has a few packets per track): the per-DownTrack prologue then
   // dominates and one workgroup per DownTrack is dispatch-rate bound.
-  if (e->decideK) {
-    d.perWave = e->decideK;
+  if (e->knobs.decideK) {
+    d.perWave = e->knobs.decideK;
   } else {
     // (round 6: 2 below 48 packets per track — 4 at the shortest ticks measured
     // slower since the stream wave and the NACK queues changed: 10-ms ticks at
@@ -1978,7 +1787,7 @@ int lkf_run(lkf_engine *e, void *stream) {
   d.ddArena = x.dDDArena;
   d.ddUsed = x.dDDUsed;
   d.ddSpill = e->ddAlloc ? x.dDDSpill : nullptr;
-  d.ddCap = e->ddArenaCap;
+  d.ddCap = x.dDDArena.cap();
   d.maxDts = e->cfg.max_downtracks;
   d.maxTracks = e->cfg.max_tracks;
   d.npkts = e->curN;  // (an ingest-produced batch: the launch bound)
@@ -1986,7 +1795,7 @@ int lkf_run(lkf_engine *e, void *stream) {
   HIPCHK(hipEventRecord(rg[1], s), "event");
   HIPCHK(launch_decide(s, d), "decide");
   HIPCHK(hipEventRecord(rg[2], s), "event");
-  if (e->useGraph) {
+  if (e->knobs.useGraph) {
     if (x.gScanEpoch != e->epoch || !x.gScan) {
       const int rc = capture(s, x.gScan, [&]() { return scanTail(s); });
       if (rc) return rc;
@@ -2053,14 +1862,14 @@ int lkf_run(lkf_engine *e, void *stream) {
   m.npkts = e->curN;
   m.tupleCap = e->cfg.max_batch_tuples;
   m.arenaLen = e->curArenaLen;
-  m.ddCap = e->ddArenaCap;
+  m.ddCap = x.dDDArena.cap();
   m.twccBase = e->anyTwcc ? x.dTwccBase : nullptr;
   m.gCap = e->cfg.max_out_pkts / 64 + 2;
   // One workgroup per 64-record group (grid = the capacity bound; workgroups
   // past the batch's records exit at once).  Short-lived workgroups free their
   // slots as they finish, so the next batch's decide stage (higher-priority
   // stream) interleaves with this emit instead of waiting for a persistent grid.
-  m.grid = e->emitPersistent ? e->emitGrid
+  m.grid = e->knobs.emitPersistent ? e->emitGrid
                              : uint32_t(((e->cfg.max_out_pkts + 63) / 64 + 7) / 8 * 8);
   // An ingest-fed batch's emit runs beside the next ingest chain: at a low
   // fan-out (fewer than emitCapFanout DownTracks per track) its workgroups are
@@ -2070,7 +1879,7 @@ int lkf_run(lkf_engine *e, void *stream) {
   // high fan-out, is most of the step and runs uncapped (the cap: ExtPacket
   // configs[1] 0.455 -> 0.54 ms, configs[2] 2.51 -> 2.83 ms, configs[3] 3.35 ->
   // 3.47 ms; profiles/r6_ab_runs.txt).
-  m.ldsPad = (ingestFed && uint64_t(nd) < uint64_t(e->emitCapFanout) * std::max<uint32_t>(1, nt)) ? e->emitLdsPad : 0;
+  m.ldsPad = (ingestFed && uint64_t(nd) < uint64_t(e->knobs.emitCapFanout) * std::max<uint32_t>(1, nt)) ? e->knobs.emitLdsPad : 0;
   if (nd) HIPCHK(launch_emit(e->emitS, m), "emit");
   HIPCHK(hipEventRecord(rg[4], e->emitS), "event");
   HIPCHK(launch_accumulate(e->emitS, x.dStats, x.dTot, e->dCum, x.dErr, e->dSticky), "accumulate");
@@ -2083,7 +1892,7 @@ int lkf_run(lkf_engine *e, void *stream) {
   }
   e->bktStorePending = false;
   HIPCHK(hipEventRecord(x.emitted, e->emitS), "event");
-  if (e->hostProf && e->nRuns >= 3) {  // steady state: skip the first runs (initial control ops, first touch)
+  if (e->knobs.hostProf && e->nRuns >= 3) {  // steady state: skip the first runs (initial control ops, first touch)
     e->hp[0] += std::chrono::duration<double, std::milli>(tp1 - tp0).count();
     e->hp[1] += std::chrono::duration<double, std::milli>(tp2 - tp1).count();
     e->hp[2] += std::chrono::duration<double, std::milli>(tp25 - tp2).count();
@@ -2111,7 +1920,7 @@ int lkf_sync(lkf_engine *e) {
   if (rc) return rc;
   uint32_t acc = 0;
   D2H(&acc, e->dSticky, sizeof(acc), "err copy");
-  if (e->debugDD && e->ddAlloc) {
+  if (e->knobs.debugDD && e->ddAlloc) {
     for (int c = 0; c < lkf_engine::kCtx; c++) {
       uint64_t u[2] = {0, 0};
       if (hipMemcpy(u, e->ctx[c].dDDUsed, sizeof(u), hipMemcpyDeviceToHost) == hipSuccess)
@@ -2155,13 +1964,13 @@ int lkf_sync(lkf_engine *e) {
         uint64_t u[2] = {0, 0};
         if (x.dDDUsed && hipMemcpy(u, x.dDDUsed, sizeof(u), hipMemcpyDeviceToHost) == hipSuccess && o < sizeof(buf))
           o += size_t(snprintf(buf + o, sizeof(buf) - o, " %llu/%llu", (unsigned long long)u[0],
-                               (unsigned long long)e->ddArenaCap));
+                               (unsigned long long)x.dDDArena.cap()));
       }
       e->err += " used/cap:";
       e->err += buf;
       // (diagnostic) the live allocations around context 0's cursor, and the
       // contexts' small buffers by name
-      const uintptr_t c0 = reinterpret_cast<uintptr_t>(e->ctx[0].dDDUsed);
+      const uintptr_t c0 = reinterpret_cast<uintptr_t>(e->ctx[0].dDDUsed.get());
       {
         std::lock_guard<std::mutex> g(dreg().m);
         for (auto it = dreg().a.lower_bound(c0 > (1u << 20) ? c0 - (1u << 20) : 0);
@@ -2292,7 +2101,7 @@ int lkf_drain_run_async(lkf_engine *e, uint32_t age, lkf_out *out, uint64_t cap,
                         uint64_t *n_out, uint64_t *arena_len) {
   if (!e || age >= uint32_t(lkf_engine::kCtx) || uint64_t(age) >= e->nRuns) return LKF_EINVAL;
   HIPCHK(hipSetDevice(e->dev), "hipSetDevice");
-  if (!e->d2hS) HIPCHK(hipStreamCreateWithFlags(&e->d2hS, hipStreamNonBlocking), "copy stream");
+  if (!e->d2hS) HIPCHK(hipStreamCreateWithFlags(e->d2hS.put(), hipStreamNonBlocking), "copy stream");
   BatchCtx &x = e->ctx[(e->nRuns - 1 - age) % lkf_engine::kCtx];
   HIPCHK(hipEventSynchronize(x.emitted), "wait emitted");
   uint64_t tot[4];
@@ -2327,13 +2136,13 @@ int lkf_drain_wait(lkf_engine *e) {
 static int srtp_init(lkf_engine *e) {
   if (e->dAesTab) return LKF_OK;
   HIPCHK(hipSetDevice(e->dev), "hipSetDevice");
-  HIPCHK(dalloc(&e->dAesTab, 256 + 64), "alloc aes tables");
-  HIPCHK(dalloc(&e->dSrtpDT, e->cfg.max_downtracks), "alloc srtp dt");
+  HIPCHK(e->dAesTab.alloc(256 + 64), "alloc aes tables");
+  HIPCHK(e->dSrtpDT.alloc(e->cfg.max_downtracks), "alloc srtp dt");
   HIPCHK(hipMemsetAsync(e->dSrtpDT, 0, sizeof(SrtpDT) * e->cfg.max_downtracks, e->own), "srtp dt init");
   HIPCHK(launch_aes_tables(e->own, e->dAesTab), "aes tables");
   HIPCHK(hipStreamSynchronize(e->own), "srtp init sync");
   for (auto &r : e->protRing)
-    for (auto &ev : r) HIPCHK(hipEventCreate(&ev), "protect event");
+    for (auto &ev : r) HIPCHK(ev.create(true), "protect event");
   e->protRun.assign(256, 0);
   return LKF_OK;
 }
@@ -2344,23 +2153,21 @@ int32_t lkf_add_transport(lkf_engine *e, const lkf_transport_params *p) {
   int rc = srtp_init(e);
   if (rc) return rc;
   const uint32_t t = uint32_t(e->transports.size());
-  if (t + 1 > e->transportCap) {  // grow; queued protect stages read the keys
+  if (t + 1 > e->dTransports.cap()) {  // grow, keeping the old ones; queued protect stages read the keys
     rc = drain_streams(e);
     if (rc) return rc;
-    const uint32_t cap = std::max<uint32_t>(64, 2 * e->transportCap);
-    lkf_transport_params *np = nullptr;
-    SrtpKeys *nk = nullptr;
-    HIPCHK(dalloc(&np, cap), "alloc transports");
-    HIPCHK(dalloc(&nk, cap), "alloc srtp keys");
+    const uint32_t cap = std::max<uint32_t>(64, 2 * uint32_t(e->dTransports.cap()));
+    DevBuf<lkf_transport_params> np;
+    DevBuf<SrtpKeys> nk;
+    HIPCHK(np.alloc(cap), "alloc transports");
+    HIPCHK(nk.alloc(cap), "alloc srtp keys");
     if (t) {
-      HIPCHK(hipMemcpy(np, e->dTransports, t * sizeof(*np), hipMemcpyDeviceToDevice), "copy transports");
-      HIPCHK(hipMemcpy(nk, e->dSrtpKeys, t * sizeof(*nk), hipMemcpyDeviceToDevice), "copy keys");
+      HIPCHK(hipMemcpy(np, e->dTransports, t * sizeof(lkf_transport_params), hipMemcpyDeviceToDevice),
+             "copy transports");
+      HIPCHK(hipMemcpy(nk, e->dSrtpKeys, t * sizeof(SrtpKeys), hipMemcpyDeviceToDevice), "copy keys");
     }
-    if (e->dTransports) HIPCHK(dfree(e->dTransports), "free transports");
-    if (e->dSrtpKeys) HIPCHK(dfree(e->dSrtpKeys), "free keys");
-    e->dTransports = np;
-    e->dSrtpKeys = nk;
-    e->transportCap = cap;
+    e->dTransports = std::move(np);
+    e->dSrtpKeys = std::move(nk);
   }
   e->transports.push_back(*p);
   HIPCHK(hipMemcpyAsync(e->dTransports + t, &e->transports.back(), sizeof(*p), hipMemcpyHostToDevice, e->own),
@@ -2405,7 +2212,7 @@ int lkf_protect(lkf_engine *e, int64_t send_time_ns) {
   if (rc) return rc;
   BatchCtx &x = e->ctx[e->lastCtx];
   if (!x.dProt)
-    HIPCHK(dalloc(&x.dProt, e->cfg.max_out_bytes + 16 * uint64_t(e->cfg.max_out_pkts)), "alloc protected arena");
+    HIPCHK(x.dProt.alloc(e->cfg.max_out_bytes + 16 * uint64_t(e->cfg.max_out_pkts)), "alloc protected arena");
   SrtpProtectArgs a;
   a.tab = e->dAesTab;
   a.totals = x.dTot + 2;
@@ -2614,14 +2421,12 @@ int lkf_seq_lookup(lkf_engine *e, int32_t dt, const uint16_t *sns, uint32_t n, i
   if (rc) return rc;
   rc = drain_streams(e);
   if (rc) return rc;
-  if (n > e->seqScratchCap) {
-    if (e->dSns) (void)dfree(e->dSns);
-    if (e->dSeqOut) (void)dfree(e->dSeqOut);
-    e->seqScratchCap = std::max<uint32_t>(n, 256);
-    HIPCHK(dalloc(&e->dSns, e->seqScratchCap), "alloc");
-    HIPCHK(dalloc(&e->dSeqOut, e->seqScratchCap), "alloc");
+  if (n > e->dSns.cap() || n > e->dSeqOut.cap()) {
+    release_all(e->dSns, e->dSeqOut);
+    HIPCHK(e->dSns.reserve(n, 256), "alloc");
+    HIPCHK(e->dSeqOut.reserve(n, 256), "alloc");
   }
-  if (!e->dSeqN) HIPCHK(dalloc(&e->dSeqN, 1), "alloc");
+  if (!e->dSeqN) HIPCHK(e->dSeqN.alloc(1), "alloc");
   if (n) HIPCHK(hipMemcpy(e->dSns, sns, n * sizeof(uint16_t), hipMemcpyHostToDevice), "sns copy");
   rc = upload_done(e);
   if (rc) return rc;
@@ -2637,20 +2442,19 @@ int lkf_seq_lookup(lkf_engine *e, int32_t dt, const uint16_t *sns, uint32_t n, i
   return LKF_OK;
 }
 
+// The seven NACK -> RTX buffers grow together, dRtxOff last: its capacity is
+// what all of them hold (0 after a failed grow, which the next call retries).
+static uint64_t rtx_cap(const lkf_engine *e) { return e->dRtxOff.cap(); }
 static int rtx_reserve(lkf_engine *e, uint32_t n) {
-  if (n <= e->rtxCap) return LKF_OK;
-  for (void *p : {static_cast<void *>(e->dNacks), static_cast<void *>(e->dNackG), static_cast<void *>(e->dNackValid),
-                  static_cast<void *>(e->dRtx), static_cast<void *>(e->dRtxSrc), static_cast<void *>(e->dRtxLen),
-                  static_cast<void *>(e->dRtxOff)})
-    if (p) (void)dfree(p);
-  e->rtxCap = std::max<uint32_t>(n, 1024);
-  HIPCHK(dalloc(&e->dNacks, e->rtxCap), "alloc nacks");
-  HIPCHK(dalloc(&e->dNackG, e->rtxCap + 1), "alloc nack groups");
-  HIPCHK(dalloc(&e->dNackValid, e->rtxCap), "alloc nack valid");
-  HIPCHK(dalloc(&e->dRtx, e->rtxCap), "alloc rtx");
-  HIPCHK(dalloc(&e->dRtxSrc, e->rtxCap), "alloc rtx src");
-  HIPCHK(dalloc(&e->dRtxLen, e->rtxCap), "alloc rtx len");
-  HIPCHK(dalloc(&e->dRtxOff, e->rtxCap), "alloc rtx off");
+  if (n <= rtx_cap(e)) return LKF_OK;
+  release_all(e->dNacks, e->dNackG, e->dNackValid, e->dRtx, e->dRtxSrc, e->dRtxLen, e->dRtxOff);
+  HIPCHK(e->dNacks.reserve(n, 1024), "alloc nacks");
+  HIPCHK(e->dNackG.reserve(uint64_t(n) + 1, 1025), "alloc nack groups");
+  HIPCHK(e->dNackValid.reserve(n, 1024), "alloc nack valid");
+  HIPCHK(e->dRtx.reserve(n, 1024), "alloc rtx");
+  HIPCHK(e->dRtxSrc.reserve(n, 1024), "alloc rtx src");
+  HIPCHK(e->dRtxLen.reserve(n, 1024), "alloc rtx len");
+  HIPCHK(e->dRtxOff.reserve(n, 1024), "alloc rtx off");
   return LKF_OK;
 }
 
@@ -2692,7 +2496,7 @@ int lkf_rtx_lookup(lkf_engine *e, const lkf_nack *nacks, uint32_t n, int64_t now
   // allocation calls.
   hipStream_t s = e->decS;
   HIPCHK(hipSetDevice(e->dev), "hipSetDevice");
-  if (m > e->rtxCap) HIPCHK(hipStreamSynchronize(s), "sync decide stream");  // (rtx_reserve reallocates)
+  if (m > rtx_cap(e)) HIPCHK(hipStreamSynchronize(s), "sync decide stream");  // (rtx_reserve reallocates)
   rc = rtx_reserve(e, m);
   if (rc) return rc;
   HIPCHK(hipEventRecord(e->inEv, e->own), "event");
@@ -2755,11 +2559,7 @@ int lkf_rtx_emit(lkf_engine *e, const lkf_rtx *rtx, uint32_t n, const lkf_raw_pk
   if (rc) return rc;
   rc = rtx_order(e, n);
   if (rc) return rc;
-  if (src_len + 64 > e->rtxInCap) {
-    if (e->dRtxIn) (void)dfree(e->dRtxIn);
-    e->rtxInCap = std::max<uint64_t>(src_len + 64, 1 << 20);
-    HIPCHK(dalloc(&e->dRtxIn, e->rtxInCap), "alloc rtx in");
-  }
+  HIPCHK(e->dRtxIn.reserve(src_len + 64, 1 << 20), "alloc rtx in");
   // uploads ordered on the sender stream ahead of the kernels that read them
   // (a pageable hipMemcpy may return before its DMA lands, and the engine's
   // streams do not order against the null stream)
@@ -2787,11 +2587,7 @@ static int rtx_emit_common(lkf_engine *e, const lkf_rtx *rtx, uint32_t n, const 
   int rc = LKF_OK;
   const uint8_t *rtxDD = nullptr;
   if (e->nSeqDD) {  // epm.ddBytes of each record (its sequencer slot)
-    if (n > e->rtxDDCap) {
-      if (e->dRtxDD) (void)dfree(e->dRtxDD);
-      e->rtxDDCap = std::max<uint32_t>(n, 1024);
-      HIPCHK(dalloc(&e->dRtxDD, size_t(e->rtxDDCap) * kSeqDDBytes), "alloc rtx dd");
-    }
+    HIPCHK(e->dRtxDD.reserve(size_t(n) * kSeqDDBytes, 1024 * kSeqDDBytes), "alloc rtx dd");
     HIPCHK(launch_rtx_dd(e->sendS, n, e->dRtx, e->dDTs, e->dSeq, e->cfg.seq_size, e->dSeqDDIdx, e->dSeqDD,
                          e->dRtxDD),
            "rtx dd");
@@ -2817,11 +2613,7 @@ static int rtx_emit_common(lkf_engine *e, const lkf_rtx *rtx, uint32_t n, const 
   *n_out = k;
   *out_len = tot;
   if (tot > out_cap || (k && (!out || !out_arena))) return LKF_ENOSPC;
-  if (tot + 64 > e->rtxOutCap) {
-    if (e->dRtxOut) (void)dfree(e->dRtxOut);
-    e->rtxOutCap = std::max<uint64_t>(tot + 64, 1 << 20);
-    HIPCHK(dalloc(&e->dRtxOut, e->rtxOutCap), "alloc rtx out");
-  }
+  HIPCHK(e->dRtxOut.reserve(tot + 64, 1 << 20), "alloc rtx out");
   HIPCHK(hipMemcpyAsync(e->dRtxOff, off.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice, e->sendS), "off copy");
   HIPCHK(launch_rtx_emit(e->sendS, true, n, e->dRtx, e->dRtxSrc, srcArena, e->dDTs, e->dTracks, e->dRtxLen,
                          e->dRtxOff, e->dRtxOut, rtxDD),
@@ -2911,12 +2703,10 @@ int lkf_rtx_emit_bucket(lkf_engine *e, const lkf_rtx *rtx, uint32_t n, lkf_out *
     }
   }
   if (!e->bktSlots) std::fill(sid.begin(), sid.end(), -1);
-  if (n > e->bktReadCap) {
-    if (e->dBktStream) (void)dfree(e->dBktStream);
-    if (e->dBktSn) (void)dfree(e->dBktSn);
-    e->bktReadCap = std::max<uint32_t>(n, 1024);
-    HIPCHK(dalloc(&e->dBktStream, e->bktReadCap), "alloc bucket reads");
-    HIPCHK(dalloc(&e->dBktSn, e->bktReadCap), "alloc bucket read sns");
+  if (n > e->dBktStream.cap() || n > e->dBktSn.cap()) {
+    release_all(e->dBktStream, e->dBktSn);
+    HIPCHK(e->dBktStream.reserve(n, 1024), "alloc bucket reads");
+    HIPCHK(e->dBktSn.reserve(n, 1024), "alloc bucket read sns");
   }
   // (uploads on the sender stream, ahead of k_bkt_read / k_rtx: see lkf_rtx_emit)
   HIPCHK(hipMemcpyAsync(e->dRtx, rtx, n * sizeof(lkf_rtx), hipMemcpyHostToDevice, e->sendS), "rtx copy");
@@ -2924,11 +2714,7 @@ int lkf_rtx_emit_bucket(lkf_engine *e, const lkf_rtx *rtx, uint32_t n, lkf_out *
          "bucket read copy");
   HIPCHK(hipMemcpyAsync(e->dBktSn, sn.data(), n * sizeof(uint16_t), hipMemcpyHostToDevice, e->sendS),
          "bucket sn copy");
-  if (uint64_t(n) * kBktSlot + 64 > e->rtxInCap) {
-    if (e->dRtxIn) (void)dfree(e->dRtxIn);
-    e->rtxInCap = std::max<uint64_t>(uint64_t(n) * kBktSlot + 64, 1 << 20);
-    HIPCHK(dalloc(&e->dRtxIn, e->rtxInCap), "alloc rtx in");
-  }
+  HIPCHK(e->dRtxIn.reserve(uint64_t(n) * kBktSlot + 64, 1 << 20), "alloc rtx in");
   HIPCHK(launch_bucket_read(e->sendS, n, e->dBktStream, e->dBktSn, e->dBkt, e->dBktTag, e->dBktRing, e->dRtxIn,
                             e->dRtxSrc),
          "bucket read");
@@ -2956,12 +2742,10 @@ static int sender_list(lkf_engine *e, std::vector<SenderUpd> &list) {
   for (uint32_t i = 0; i < list.size(); i++)
     if (i == 0 || list[i].dt != list[i - 1].dt) g.push_back(i);
   g.push_back(uint32_t(list.size()));
-  if (list.size() > e->ssListCap || g.size() > e->ssListCap + 1) {
-    if (e->dSSList) (void)dfree(e->dSSList);
-    if (e->dSSGroups) (void)dfree(e->dSSGroups);
-    e->ssListCap = uint32_t(std::max<size_t>(2 * list.size(), 4096));
-    HIPCHK(dalloc(&e->dSSList, e->ssListCap), "alloc sender list");
-    HIPCHK(dalloc(&e->dSSGroups, e->ssListCap + 1), "alloc sender groups");
+  if (list.size() > e->dSSList.cap() || g.size() > e->dSSGroups.cap()) {
+    release_all(e->dSSList, e->dSSGroups);
+    HIPCHK(e->dSSList.reserve(2 * list.size(), 4096), "alloc sender list");
+    HIPCHK(e->dSSGroups.reserve(2 * list.size() + 1, 4097), "alloc sender groups");
   }
   // on the sender stream, after the queued runs' sender statistics (sender or
   // emit stream), which update the same DownTracks' RTPStatsSender
@@ -3025,24 +2809,14 @@ static int pad_common(lkf_engine *e, int blank, const lkf_pad_req *reqs, uint32_
   // the sender stream (sender_list)
   const hipStream_t ds = e->decS;
   HIPCHK(hipSetDevice(e->dev), "hipSetDevice");
-  if (n > e->padCap) {
-    for (void *p : {static_cast<void *>(e->dPadReq), static_cast<void *>(e->dPadOff), static_cast<void *>(e->dPadCnt)})
-      if (p) (void)dfree(p);
-    e->padCap = std::max<uint32_t>(n, 1024);
-    HIPCHK(dalloc(&e->dPadReq, e->padCap), "alloc pad reqs");
-    HIPCHK(dalloc(&e->dPadOff, 2 * size_t(e->padCap)), "alloc pad offsets");
-    HIPCHK(dalloc(&e->dPadCnt, 2 * size_t(e->padCap)), "alloc pad counts");
+  if (n > e->dPadReq.cap() || 2 * uint64_t(n) > e->dPadOff.cap() || 2 * uint64_t(n) > e->dPadCnt.cap()) {
+    release_all(e->dPadReq, e->dPadOff, e->dPadCnt);
+    HIPCHK(e->dPadReq.reserve(n, 1024), "alloc pad reqs");
+    HIPCHK(e->dPadOff.reserve(2 * uint64_t(n), 2048), "alloc pad offsets");
+    HIPCHK(e->dPadCnt.reserve(2 * uint64_t(n), 2048), "alloc pad counts");
   }
-  if (recs > e->padOutCap) {
-    if (e->dPadOut) (void)dfree(e->dPadOut);
-    e->padOutCap = std::max<uint64_t>(recs, 4096);
-    HIPCHK(dalloc(&e->dPadOut, e->padOutCap), "alloc pad out");
-  }
-  if (bytes > e->padArenaCap) {
-    if (e->dPadArena) (void)dfree(e->dPadArena);
-    e->padArenaCap = std::max<uint64_t>(bytes, 1 << 20);
-    HIPCHK(dalloc(&e->dPadArena, e->padArenaCap), "alloc pad arena");
-  }
+  HIPCHK(e->dPadOut.reserve(recs, 4096), "alloc pad out");
+  HIPCHK(e->dPadArena.reserve(bytes, 1 << 20), "alloc pad arena");
   // a removed DownTrack sends nothing: its request is dropped before the kernel
   std::vector<lkf_pad_req> q(reqs, reqs + n);
   std::vector<uint32_t> live;
@@ -3159,17 +2933,14 @@ int32_t lkf_add_stream_tracker_dd(lkf_engine *e, int32_t track) {
   rc = drain_streams(e);
   if (rc) return rc;
   if (!e->dTrackDDTrk) {
-    HIPCHK(dalloc(&e->dTrackDDTrk, e->cfg.max_tracks), "alloc track dd trackers");
+    HIPCHK(e->dTrackDDTrk.alloc(e->cfg.max_tracks), "alloc track dd trackers");
     HIPCHK(hipMemset(e->dTrackDDTrk, 0xff, size_t(e->cfg.max_tracks) * sizeof(uint32_t)), "track dd trackers reset");
   }
-  if (e->nDDTrk + 1 > e->ddTrkCap) {
-    const uint32_t cap = std::max<uint32_t>(2 * e->ddTrkCap, 256);
-    DDTrkState *n = nullptr;
-    HIPCHK(dalloc(&n, cap), "alloc dd trackers");
+  if (e->nDDTrk + 1 > e->dDDTrk.cap()) {  // grow, keeping the trackers
+    DevBuf<DDTrkState> n;
+    HIPCHK(n.alloc(std::max<uint32_t>(2 * uint32_t(e->dDDTrk.cap()), 256)), "alloc dd trackers");
     if (e->nDDTrk) HIPCHK(hipMemcpy(n, e->dDDTrk, e->nDDTrk * sizeof(DDTrkState), hipMemcpyDeviceToDevice), "dd trackers move");
-    if (e->dDDTrk) HIPCHK(dfree(e->dDDTrk), "free dd trackers");
-    e->dDDTrk = n;
-    e->ddTrkCap = cap;
+    e->dDDTrk = std::move(n);
   }
   DDTrkState t;
   std::memset(&t, 0, sizeof(t));
@@ -3221,8 +2992,8 @@ int lkf_dd_trackers_tick(lkf_engine *e, const int32_t *trackers, uint32_t n, int
   if (!n) return LKF_OK;
   int rc = drain_streams(e);
   if (rc) return rc;
-  HIPCHK(grow(&e->dDDTrkIds, e->ddTrkIdsCap, n), "alloc dd tracker ids");
-  HIPCHK(grow(&e->dDDTrkOut, e->ddTrkOutCap, n), "alloc dd tracker out");
+  HIPCHK(e->dDDTrkIds.reserve(n, 1024), "alloc dd tracker ids");
+  HIPCHK(e->dDDTrkOut.reserve(n, 1024), "alloc dd tracker out");
   HIPCHK(hipMemcpy(e->dDDTrkIds, trackers, n * sizeof(int32_t), hipMemcpyHostToDevice), "dd tracker ids copy");
   rc = upload_done(e);
   if (rc) return rc;
@@ -3238,14 +3009,11 @@ int32_t lkf_add_stream_tracker(lkf_engine *e, int32_t track, int32_t layer, uint
   if (!e || track < 0 || track >= int32_t(e->tracks.size()) || layer < 0) return LKF_EINVAL;
   int rc = drain_streams(e);
   if (rc) return rc;
-  if (e->nTrk + 1 > e->trkCap) {
-    const uint32_t cap = std::max<uint32_t>(2 * e->trkCap, 1024);
-    TrackerState *n = nullptr;
-    HIPCHK(dalloc(&n, cap), "alloc trackers");
+  if (e->nTrk + 1 > e->dTrk.cap()) {  // grow, keeping the trackers
+    DevBuf<TrackerState> n;
+    HIPCHK(n.alloc(std::max<uint32_t>(2 * uint32_t(e->dTrk.cap()), 1024)), "alloc trackers");
     if (e->nTrk) HIPCHK(hipMemcpy(n, e->dTrk, e->nTrk * sizeof(TrackerState), hipMemcpyDeviceToDevice), "trackers move");
-    if (e->dTrk) HIPCHK(dfree(e->dTrk), "free trackers");
-    e->dTrk = n;
-    e->trkCap = cap;
+    e->dTrk = std::move(n);
   }
   e->epoch++;  // the prep graph observes every tracker
   TrackerState t = {};
@@ -3345,8 +3113,8 @@ int lkf_stream_trackers_tick_at(lkf_engine *e, const int32_t *trackers, uint32_t
   }
   int rc = drain_streams(e);
   if (rc) return rc;
-  HIPCHK(grow(&e->dTrkIds, e->trkIdsCap, n), "alloc tracker ids");
-  HIPCHK(grow(&e->dTrkOut, e->trkOutCap, n), "alloc tracker out");
+  HIPCHK(e->dTrkIds.reserve(n, 1024), "alloc tracker ids");
+  HIPCHK(e->dTrkOut.reserve(n, 1024), "alloc tracker out");
   HIPCHK(hipMemcpy(e->dTrkIds, trackers, n * sizeof(int32_t), hipMemcpyHostToDevice), "tracker ids copy");
   rc = upload_done(e);
   if (rc) return rc;
@@ -3401,21 +3169,21 @@ static int red_common(lkf_engine *e, bool decode, const lkf_pkt *pkts, uint32_t 
   if (!gb.empty()) {
     auto &r = e->red;
     if (decode && !e->dRedDec) {
-      HIPCHK(dalloc(&e->dRedDec, e->cfg.max_tracks), "alloc red dec");
+      HIPCHK(e->dRedDec.alloc(e->cfg.max_tracks), "alloc red dec");
       HIPCHK(hipMemset(e->dRedDec, 0, size_t(e->cfg.max_tracks) * sizeof(RedDecState)), "red dec reset");
     }
     if (!decode && !e->dRedEnc) {
-      HIPCHK(dalloc(&e->dRedEnc, e->cfg.max_tracks), "alloc red enc");
+      HIPCHK(e->dRedEnc.alloc(e->cfg.max_tracks), "alloc red enc");
       HIPCHK(hipMemset(e->dRedEnc, 0, size_t(e->cfg.max_tracks) * sizeof(RedEncState)), "red enc reset");
     }
-    HIPCHK(grow(&r.in, r.inCap, n), "alloc red in");
-    HIPCHK(grow(&r.inArena, r.inArenaCap, arena_len + 64), "alloc red in arena");
-    HIPCHK(grow(&r.out, r.outCap, recs), "alloc red out");
-    HIPCHK(grow(&r.outArena, r.outArenaCap, bytes), "alloc red out arena");
-    HIPCHK(grow(&r.g, r.gCap, 2 * gb.size()), "alloc red groups");
-    HIPCHK(grow(&r.cnt, r.cntCap, n), "alloc red counts");
-    HIPCHK(grow(&r.map, r.mapCap, nt), "alloc red map");
-    HIPCHK(grow(&r.off, r.offCap, 2 * uint64_t(n) + 1), "alloc red offsets");
+    HIPCHK(r.in.reserve(n, 1024), "alloc red in");
+    HIPCHK(r.inArena.reserve(arena_len + 64, 1024), "alloc red in arena");
+    HIPCHK(r.out.reserve(recs, 1024), "alloc red out");
+    HIPCHK(r.outArena.reserve(bytes, 1024), "alloc red out arena");
+    HIPCHK(r.g.reserve(2 * gb.size(), 1024), "alloc red groups");
+    HIPCHK(r.cnt.reserve(n, 1024), "alloc red counts");
+    HIPCHK(r.map.reserve(nt, 1024), "alloc red map");
+    HIPCHK(r.off.reserve(2 * uint64_t(n) + 1, 1024), "alloc red offsets");
     std::vector<int32_t> mp(nt, -1);
     for (uint32_t t = 0; t < map_len; t++) mp[t] = map[t];
     std::vector<uint32_t> g(gb);
@@ -3493,6 +3261,11 @@ int lkf_red_decode(lkf_engine *e, const lkf_pkt *pkts, uint32_t n, const uint8_t
 // ---- Forwarder allocation: AllocateOptimal (forwarder.go:591-725),
 // AllocateNextHigher (:1107-1217), GetNextHigherTransition (:1219-1306),
 // Pause (:1308-1351) ------------------------------------------------------
+// The allocation calls' three buffers grow together, dAllocCapacity last (its
+// capacity is what all of them hold; 0 after a failed grow); likewise the
+// provisional pass's request and result buffers, dProvOut (bytes) last.
+static uint64_t alloc_cap(const lkf_engine *e) { return e->dAllocCapacity.cap(); }
+static uint64_t prov_cap(const lkf_engine *e) { return e->dProvOut.cap() / sizeof(lkf_allocation); }
 static int alloc_common(lkf_engine *e, int mode, const lkf_alloc_req *reqs, const int64_t *capacity, uint32_t n,
                         void *out, size_t outSize) {
   if (!e || (n && (!reqs || !out || (mode == ALLOC_NEXT_HIGHER && !capacity)))) return LKF_EINVAL;
@@ -3516,15 +3289,12 @@ static int alloc_common(lkf_engine *e, int mode, const lkf_alloc_req *reqs, cons
   // (those keep overlapping the call).
   hipStream_t s = e->decS;
   HIPCHK(hipSetDevice(e->dev), "hipSetDevice");
-  if (n > e->allocCap) {
+  if (n > alloc_cap(e)) {
     HIPCHK(hipStreamSynchronize(s), "sync before alloc buffers realloc");
-    if (e->dAllocReq) (void)dfree(e->dAllocReq);
-    if (e->dAllocOut) (void)dfree(e->dAllocOut);
-    if (e->dAllocCapacity) (void)dfree(e->dAllocCapacity);
-    e->allocCap = std::max<uint32_t>(n, 1024);
-    HIPCHK(dalloc(&e->dAllocReq, e->allocCap), "alloc alloc reqs");
-    HIPCHK(dalloc(&e->dAllocOut, e->allocCap), "alloc alloc out");
-    HIPCHK(dalloc(&e->dAllocCapacity, e->allocCap), "alloc alloc capacity");
+    release_all(e->dAllocReq, e->dAllocOut, e->dAllocCapacity);
+    HIPCHK(e->dAllocReq.reserve(n, 1024), "alloc alloc reqs");
+    HIPCHK(e->dAllocOut.reserve(n, 1024), "alloc alloc out");
+    HIPCHK(e->dAllocCapacity.reserve(n, 1024), "alloc alloc capacity");
   }
   static_assert(sizeof(lkf_video_transition) <= sizeof(lkf_allocation), "transition fits the out buffer");
   // (the engine's own stream: anything an earlier control call left there)
@@ -3574,28 +3344,19 @@ static int prov_check(lkf_engine *e, const int32_t *dts, uint32_t n, size_t stri
 static int prov_reserve(lkf_engine *e, uint32_t n, uint32_t ngroups) {
   const lkf_cfg &c = e->cfg;
   if (!e->dProv) {
-    HIPCHK(dalloc(&e->dProv, c.max_downtracks), "alloc provisional");
+    HIPCHK(e->dProv.alloc(c.max_downtracks), "alloc provisional");
     HIPCHK(hipMemset(e->dProv, 0, size_t(c.max_downtracks) * sizeof(ProvState)), "provisional reset");
   }
-  if (n > e->provCap) {
-    if (e->dProvReq) (void)dfree(e->dProvReq);
-    if (e->dProvOut) (void)dfree(e->dProvOut);
-    if (e->dAllocReq) (void)dfree(e->dAllocReq);
-    if (e->dAllocOut) (void)dfree(e->dAllocOut);
-    if (e->dAllocCapacity) (void)dfree(e->dAllocCapacity);
-    e->provCap = std::max<uint32_t>(n, 1024);
-    e->allocCap = std::max<uint32_t>(e->allocCap, e->provCap);
-    HIPCHK(dalloc(&e->dProvReq, e->provCap), "alloc prov reqs");
-    HIPCHK(dalloc(&e->dProvOut, size_t(e->provCap) * sizeof(lkf_allocation)), "alloc prov out");
-    HIPCHK(dalloc(&e->dAllocReq, e->allocCap), "alloc alloc reqs");
-    HIPCHK(dalloc(&e->dAllocOut, e->allocCap), "alloc alloc out");
-    HIPCHK(dalloc(&e->dAllocCapacity, e->allocCap), "alloc alloc capacity");
+  if (n > prov_cap(e) || n > alloc_cap(e)) {  // (the allocation calls' buffers: at least as large)
+    const uint64_t pc = std::max<uint32_t>(n, 1024), ac = std::max<uint64_t>(alloc_cap(e), pc);
+    release_all(e->dProvReq, e->dProvOut, e->dAllocReq, e->dAllocOut, e->dAllocCapacity);
+    HIPCHK(e->dProvReq.alloc(pc), "alloc prov reqs");
+    HIPCHK(e->dProvOut.alloc(pc * sizeof(lkf_allocation)), "alloc prov out");
+    HIPCHK(e->dAllocReq.alloc(ac), "alloc alloc reqs");
+    HIPCHK(e->dAllocOut.alloc(ac), "alloc alloc out");
+    HIPCHK(e->dAllocCapacity.alloc(ac), "alloc alloc capacity");
   }
-  if (ngroups > e->provGroupCap) {
-    if (e->dProvGroups) (void)dfree(e->dProvGroups);
-    e->provGroupCap = std::max<uint32_t>(ngroups, 256);
-    HIPCHK(dalloc(&e->dProvGroups, e->provGroupCap), "alloc prov groups");
-  }
+  HIPCHK(e->dProvGroups.reserve(ngroups, 256), "alloc prov groups");
   return LKF_OK;
 }
 static int prov_common(lkf_engine *e, int mode, const lkf_prov_req *reqs, const lkf_alloc_req *alloc, uint32_t n,
@@ -3683,7 +3444,7 @@ int lkf_allocate_all(lkf_engine *e, const lkf_alloc_group *groups, uint32_t ngro
   rc = upload_done(e);
   if (rc) return rc;
   HIPCHK(launch_allocate_all(e->own, e->dProvGroups, ngroups, e->dAllocReq, e->dHot, e->dDTs, e->dTracks,
-                             e->dLastAlloc, e->dProv, reinterpret_cast<lkf_allocation *>(e->dProvOut)),
+                             e->dLastAlloc, e->dProv, reinterpret_cast<lkf_allocation *>(e->dProvOut.get())),
          "allocate all");
   HIPCHK(hipStreamSynchronize(e->own), "sync");
   D2H(out, e->dProvOut, n * sizeof(lkf_allocation), "alloc out copy");
@@ -3712,7 +3473,7 @@ int lkf_timing_window(lkf_engine *e, uint32_t n, float *decide_ms, float *emit_m
   float sa = 0, sb = 0;
   const uint64_t first = e->nRuns - n;
   for (uint64_t r = first; r < e->nRuns; r++) {
-    hipEvent_t *rg = e->ring[r % lkf_engine::kRing];
+    Event *rg = e->ring[r % lkf_engine::kRing];
     HIPCHK(hipEventSynchronize(rg[4]), "evsync");
     float a = 0, b = 0;
     HIPCHK(hipEventElapsedTime(&a, rg[1], rg[2]), "elapsed");
@@ -3765,23 +3526,6 @@ int32_t lkf_add_stream(lkf_engine *e, const lkf_stream_params *p) {
 
 // Enqueued on the decide stream ahead of the batch's decide stage (no host
 // sync): the ExtPacket count stays on the device (k_track_ranges reads it).
-// the d* names of the ingest scratch point at set `par` (the last ingest's)
-static void IngSetSelect(lkf_engine *e, int par) {
-  const lkf_engine::IngSet &g = e->ing[par];
-  e->ingPar = par;
-  e->dParsed = g.parsed;
-  e->dFlows = g.flows;
-  e->dFwdFlag = g.fwd;
-  e->dITBegin = g.tBegin;
-  e->dITEnd = g.tEnd;
-  e->dIList = g.list;
-  e->dIListCnt = g.listCnt;
-  e->dNackInfo = g.nackInfo;
-  e->dNackPairOff = g.nackPairOff;
-  e->dNackPairCnt = g.nackPairCnt;
-  e->dNackPairs = g.nackPairs;
-}
-
 static int ingest_common(lkf_engine *e, BatchCtx &x, const lkf_raw_pkt *dRaws, uint32_t n, const uint8_t *dRaw,
                          uint64_t rawLen) {
   const uint32_t nt = uint32_t(e->tracks.size());
@@ -3792,7 +3536,8 @@ static int ingest_common(lkf_engine *e, BatchCtx &x, const lkf_raw_pkt *dRaws, u
   // this ingest's scratch set: the ingest two back used it, and its NACK
   // queues (side stream) and bucket copies (sender stream) read it
   const int par = e->ingPar ^ 1;
-  IngSetSelect(e, par);
+  e->ingPar = par;
+  const lkf_engine::IngSet &g = e->ing[par];
   if (e->sidePending[par]) HIPCHK(hipStreamWaitEvent(s, e->sideDone[par], 0), "wait nack queues");
   e->sidePending[par] = false;
   if (e->bktPending[par]) HIPCHK(hipStreamWaitEvent(s, e->bktDone[par], 0), "wait bucket copies");
@@ -3808,29 +3553,30 @@ static int ingest_common(lkf_engine *e, BatchCtx &x, const lkf_raw_pkt *dRaws, u
   a.hist = e->dHist;
   a.rxGap = e->dRxGap;
   a.rings = e->dStreamRings;
-  a.parsed = e->dParsed;
-  a.tBegin = e->dITBegin;
-  a.tEnd = e->dITEnd;
+  a.parsed = g.parsed;
+  a.tBegin = g.tBegin;
+  a.tEnd = g.tEnd;
   a.tRuns = e->dITRuns;
   a.err = e->dIErr;
-  a.flows = e->dFlows;
-  a.fwd = e->dFwdFlag;
+  a.flows = g.flows;
+  a.fwd = g.fwd;
   a.twcc = e->dTwcc;
   a.pos = e->dPos;
   a.partA = e->dIPartA;
-  a.partB = e->dIPartB;
+  a.partB = nullptr;
   a.total = x.dITotal;
   a.out = x.dPktsOwn;
-  a.list = e->dIList;
-  a.listCnt = e->dIListCnt;
+  a.list = g.list;
+  a.listCnt = g.listCnt;
   a.listStride = e->cfg.max_batch_pkts;
   a.nack = e->dNack;
-  a.nackInfo = e->dNackInfo;
-  a.nackPairOff = e->dNackPairOff;
-  a.nackPairCnt = e->dNackPairCnt;
-  a.nackPairs = e->dNackPairs;
+  a.nackInfo = g.nackInfo;
+  a.nackPairOff = g.nackPairOff;
+  a.nackPairCnt = g.nackPairCnt;
+  a.nackPairs = g.nackPairs;
   a.nackPairCap = e->nackPairCap;
-  a.nackIn = e->ing[e->ingPar].nackIn;
+  a.nackIn = g.nackIn;
+  a.nackAlone = e->knobs.nackAlone;
   BucketLaunch bl;
   if (e->bktSlots && e->bktStorePending) {  // a second ingest before lkf_run: the first one's copies read this
                                             // context's store list first
@@ -3843,13 +3589,13 @@ static int ingest_common(lkf_engine *e, BatchCtx &x, const lkf_raw_pkt *dRaws, u
     bl.n = n;
     bl.streams = e->dStreams;
     bl.nstreams = uint32_t(e->streams.size());
-    bl.tBegin = e->dITBegin;
-    bl.tEnd = e->dITEnd;
-    bl.list = e->dIList;
-    bl.listCnt = e->dIListCnt;
+    bl.tBegin = g.tBegin;
+    bl.tEnd = g.tEnd;
+    bl.list = g.list;
+    bl.listCnt = g.listCnt;
     bl.listStride = e->cfg.max_batch_pkts;
-    bl.flows = e->dFlows;
-    bl.fwd = e->dFwdFlag;
+    bl.flows = g.flows;
+    bl.fwd = g.fwd;
     bl.state = e->dBkt;
     bl.tag = e->dBktTag;
     bl.owner = e->dBktOwner;
@@ -3881,11 +3627,8 @@ static int ingest_common(lkf_engine *e, BatchCtx &x, const lkf_raw_pkt *dRaws, u
                         // batch context counts as done only after it, like the sender statistics)
     HIPCHK(hipEventRecord(e->bktEv, s), "event");
     HIPCHK(hipStreamWaitEvent(e->sendS, e->bktEv, 0), "wait ingest (bucket store)");
-    static const bool skipStore = [] {  // (measurement only: LKF_SKIP_BKT_STORE=1 leaves the rings stale)
-      const char *v = getenv("LKF_SKIP_BKT_STORE");
-      return v && atoi(v) != 0;
-    }();
-    if (!skipStore) HIPCHK(launch_bucket_store(e->sendS, bl), "bucket store");
+    // (measurement only: LKF_SKIP_BKT_STORE=1 leaves the rings stale)
+    if (!e->knobs.skipBktStore) HIPCHK(launch_bucket_store(e->sendS, bl), "bucket store");
     HIPCHK(hipEventRecord(e->bktDone[par], e->sendS), "event");
     e->bktPending[par] = true;
     e->bktStorePending = true;
@@ -3946,7 +3689,7 @@ int lkf_ingest_device(lkf_engine *e, const lkf_raw_pkt *d_pkts, uint32_t n, cons
   BatchCtx &x = e->ctx[e->nRuns % lkf_engine::kCtx];
   if (x.used) HIPCHK(hipStreamWaitEvent(e->ingS, x.emitted, 0), "wait emit");
   rc = ingest_common(e, x, d_pkts, n, d_raw, raw_len);
-  if (e->hostProf) {
+  if (e->knobs.hostProf) {
     e->hp[7] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     e->hp[8] += 1;
   }
@@ -3960,7 +3703,7 @@ int lkf_ingest_flows(lkf_engine *e, lkf_flow *out, uint32_t cap, uint32_t *n_out
   HIPCHK(hipSetDevice(e->dev), "hipSetDevice");
   HIPCHK(hipStreamSynchronize(e->ingS), "sync");
   if (e->lastIngestN)
-    D2H(out, e->dFlows, size_t(e->lastIngestN) * sizeof(lkf_flow), "flows");
+    D2H(out, e->ing[e->ingPar].flows, size_t(e->lastIngestN) * sizeof(lkf_flow), "flows");
   return LKF_OK;
 }
 
@@ -4068,8 +3811,9 @@ int lkf_ingest_nacks(lkf_engine *e, lkf_rtcp_nack *out, uint32_t cap, lkf_nack_p
   if (!e->dNack || !e->lastIngestN) return LKF_OK;
   const uint32_t n = e->lastIngestN;
   hipStream_t ps = e->sideS;  // after the NACK queues of the ingest that produced them (same stream)
-  HIPCHK(launch_nack_compact(ps, n, e->ingRaws, e->dStreams, e->dNackInfo, e->dNackPairOff, e->dNackPairs,
-                             e->dNackPartA, e->dNackPartB, e->dNackRecPos, e->dNackPairPos, e->dNackTot, e->dNackOut, e->dNackPairsOut),
+  const lkf_engine::IngSet &g = e->ing[e->ingPar];  // the last ingest's set
+  HIPCHK(launch_nack_compact(ps, n, e->ingRaws, e->dStreams, g.nackInfo, g.nackPairOff, g.nackPairs,
+                             e->dNackPartA, nullptr, e->dNackRecPos, e->dNackPairPos, e->dNackTot, e->dNackOut, e->dNackPairsOut),
          "nack compact");
   uint64_t tot[2] = {0, 0};
   CHKRANGE(e->dNackTot, sizeof(tot), "async d2h");
@@ -4137,21 +3881,19 @@ static int rebuild_speakers(lkf_engine *e) {
   e->nRooms = uint32_t(roomId.size());
   e->spkRoomIds = roomId;
   e->topoGen++;
-  uint32_t **bufs[] = {&e->dRoomPartOff, &e->dPartId, &e->dPartMicOff, &e->dMics, &e->dRoomId};
+  DevBuf<uint32_t> *bufs[] = {&e->dRoomPartOff, &e->dPartId, &e->dPartMicOff, &e->dMics, &e->dRoomId};
   const std::vector<uint32_t> *src[] = {&roomOff, &partId, &partMicOff, &mics, &roomId};
   for (int i = 0; i < 5; i++) {
-    if (*bufs[i]) HIPCHK(dfree(*bufs[i]), "free");
-    HIPCHK(dalloc(bufs[i], std::max<size_t>(src[i]->size(), 1)), "alloc speakers table");
+    HIPCHK(bufs[i]->alloc(std::max<size_t>(src[i]->size(), 1)), "alloc speakers table");
     if (!src[i]->empty())
       HIPCHK(hipMemcpy(*bufs[i], src[i]->data(), src[i]->size() * sizeof(uint32_t), hipMemcpyHostToDevice),
              "speakers table copy");
   }
-  if (e->spkCap < size_t(e->nRooms) * 64) {
-    if (e->dSpkSlots) HIPCHK(dfree(e->dSpkSlots), "free");
-    if (e->dSpkCounts) HIPCHK(dfree(e->dSpkCounts), "free");
-    e->spkCap = std::max<size_t>(size_t(e->nRooms) * 64, 64);
-    HIPCHK(dalloc(&e->dSpkSlots, e->spkCap), "alloc slots");
-    HIPCHK(dalloc(&e->dSpkCounts, e->spkCap / 64 + 1), "alloc counts");
+  const size_t slots = size_t(e->nRooms) * 64;
+  if (e->dSpkSlots.cap() < slots || (slots && e->dSpkCounts.cap() < slots / 64 + 1)) {
+    release_all(e->dSpkSlots, e->dSpkCounts);
+    HIPCHK(e->dSpkSlots.alloc(std::max<size_t>(slots, 64)), "alloc slots");
+    HIPCHK(e->dSpkCounts.alloc(std::max<size_t>(slots, 64) / 64 + 1), "alloc counts");
   }
   e->spkDirty = false;
   return LKF_OK;
@@ -4257,8 +3999,8 @@ int lkf_room_summaries_enqueue(lkf_engine *e, int64_t now_ns, const uint32_t *ro
   }
   HIPCHK(hipSetDevice(e->dev), "hipSetDevice");
   if (!e->rsSpk) {
-    HIPCHK(hipEventCreateWithFlags(&e->rsSpk, hipEventDisableTiming), "event");
-    HIPCHK(hipEventCreateWithFlags(&e->rsDec, hipEventDisableTiming), "event");
+    HIPCHK(e->rsSpk.create(false), "event");
+    HIPCHK(e->rsDec.create(false), "event");
   }
   const uint32_t nd = uint32_t(e->dtp.size());
   if (rows != e->rsRooms.size() || !std::equal(room_ids, room_ids + rows, e->rsRooms.begin()) || k != e->rsK ||
@@ -4329,13 +4071,11 @@ int lkf_room_summaries_enqueue(lkf_engine *e, int64_t now_ns, const uint32_t *ro
     }
     HIPCHK(hipStreamSynchronize(e->ingS), "sync ingest stream");  // (a queued pack may read the old layout)
     HIPCHK(hipStreamSynchronize(e->decS), "sync decide stream");
-    for (void *p : {static_cast<void *>(e->dRsRowEng), static_cast<void *>(e->dRsSlotOff),
-                    static_cast<void *>(e->dRsSlotDts), static_cast<void *>(e->dRsSlotSub)})
-      if (p) HIPCHK(dfree(p), "free");
-    HIPCHK(dalloc(&e->dRsRowEng, rowEng.size()), "alloc");
-    HIPCHK(dalloc(&e->dRsSlotOff, off.size()), "alloc");
-    HIPCHK(dalloc(&e->dRsSlotDts, dts.size()), "alloc");
-    HIPCHK(dalloc(&e->dRsSlotSub, sub.size()), "alloc");
+    release_all(e->dRsRowEng, e->dRsSlotOff, e->dRsSlotDts, e->dRsSlotSub);
+    HIPCHK(e->dRsRowEng.alloc(rowEng.size()), "alloc");
+    HIPCHK(e->dRsSlotOff.alloc(off.size()), "alloc");
+    HIPCHK(e->dRsSlotDts.alloc(dts.size()), "alloc");
+    HIPCHK(e->dRsSlotSub.alloc(sub.size()), "alloc");
     HIPCHK(hipMemcpy(e->dRsRowEng, rowEng.data(), rowEng.size() * 4, hipMemcpyHostToDevice), "copy");
     HIPCHK(hipMemcpy(e->dRsSlotOff, off.data(), off.size() * 4, hipMemcpyHostToDevice), "copy");
     HIPCHK(hipMemcpy(e->dRsSlotDts, dts.data(), dts.size() * 4, hipMemcpyHostToDevice), "copy");
@@ -4439,7 +4179,7 @@ int lkf_debug_dd_cursors(lkf_engine *e, uint64_t out[7]) {
     out[2 * c] = u[0];
     out[2 * c + 1] = u[1] & 0xffffffffu;
   }
-  out[6] = e->ddArenaCap;
+  out[6] = e->ctx[0].dDDArena.cap();
   return LKF_OK;
 }
 

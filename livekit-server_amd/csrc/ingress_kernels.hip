@@ -2899,13 +2899,8 @@ hipError_t launch_ingest(hipStream_t st, const IngestLaunch &a, hipStream_t side
     r = hipEventRecord(sideDone, side);
     if (r != hipSuccess) return r;
     *sideUsed = true;
-    // (measurement: LKF_NACK_ALONE=1 orders the rest of the ingest after the
-    // NACK queues, so a kernel trace times k_ing_nack with the GPU to itself)
-    static const bool alone = [] {
-      const char *v = getenv("LKF_NACK_ALONE");
-      return v && atoi(v) != 0;
-    }();
-    if (alone && (r = hipStreamWaitEvent(st, sideDone, 0)) != hipSuccess) return r;
+    // (measurement: the rest of the ingest after the NACK queues; kernels.h nackAlone)
+    if (a.nackAlone && (r = hipStreamWaitEvent(st, sideDone, 0)) != hipSuccess) return r;
   }
   hipError_t r = launch_scan(st, 2, nullptr, nullptr, nullptr, a.fwd, nullptr, a.n, a.partA, a.partB, a.pos, nullptr,
                              a.total, nullptr, nullptr);

@@ -154,6 +154,9 @@ struct IngestLaunch {
   uint32_t nackPairCap;
   NackIn *nackIn;  // 3 * listStride records (nullptr: the NACK kernel reads the raw arrays)
   const BucketLaunch *bucket = nullptr;  // the RTX buckets (nullptr: none)
+  // (measurement, LKF_NACK_ALONE=1) the rest of the ingest waits for the NACK
+  // queues, so a kernel trace times k_ing_nack with the GPU to itself
+  bool nackAlone = false;
   // the forwarding batch context's preparation, done by k_ing_out (tBegin
   // nullptr: not done): per-track ExtPacket ranges from the ingest's datagram
   // ranges and positions, and the zeroing k_batch_init would do (lkf_run then
