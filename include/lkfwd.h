@@ -468,6 +468,67 @@ int lkf_drain_wait(lkf_engine *e);
 int lkf_output_device(lkf_engine *e, const lkf_out **d_out, uint64_t *n_out, const uint8_t **d_arena,
                       uint64_t *arena_len);
 
+/* ---- prefix egress ------------------------------------------------------
+ * For a host that sends through pion, which takes header and payload
+ * separately (WriteStream.WriteRTP(&p.Header, p.Payload), pacer/base.go:59)
+ * and already holds the payload bytes it submitted: in prefix mode a run
+ * writes, per forwarded tuple, an lkf_pre record and only the bytes the engine
+ * creates — RTP header, CSRCs, extension block and, where the DownTrack's codec
+ * munges it, the VP8 descriptor (downtrack.go:1728-1736).  The rest of the wire
+ * packet is an unchanged slice of the input, named by the record.  The emit
+ * stage then reads the input arena only for the CSRCs of packets with CC > 0
+ * and writes no payload byte.
+ *   tail_src   indexes the arena of lkf_submit* or the raw arena of
+ *              lkf_ingest* (the raw arena is the forwarding arena);
+ *              tail_src + tail_len is the end of the input packet's payload.
+ *   layout     pre_off[i] = sum over j < i of round16(pre_len[j]) in record
+ *              order, arena_len = the sum over all records; the bytes between
+ *              a prefix and the next one are zero.
+ *   bytes      the first pre_len bytes of the wire packet wire mode produces
+ *              (the zero abs-send-time placeholder and the transport-cc
+ *              sequence number included); wire packet = prefix ++ tail.
+ *   capacity   as in wire mode: the prefix arena is the context's output arena
+ *              (round16(pre_len) <= round16(out_len)), and a run whose wire
+ *              totals exceed max_out_pkts or max_out_bytes writes nothing and
+ *              reports LKF_ENOSPC.
+ * Forwarder state, sender statistics, the sequencer, TWCC counters and
+ * lkf_get_stats (arena_bytes keeps describing the wire layout) do not depend on
+ * the mode.  The mode is recorded per run at lkf_run: on a prefix-mode run
+ * lkf_drain, lkf_drain_run, lkf_drain_run_async, lkf_output_device and
+ * lkf_protect return LKF_EINVAL (lkf_last_error says why), and so do the
+ * prefix accessors on a wire-mode run.  RTX, padding and blank frames have
+ * their own arenas and stay whole wire packets.  There is no asynchronous
+ * prefix drain and no SRTP over prefixes (that host protects in pion). */
+#define LKF_EGRESS_WIRE 0   /* default: lkf_out + whole wire packets */
+#define LKF_EGRESS_PREFIX 1
+/* Applies to the next lkf_run and those after it.  LKF_EINVAL for an unknown
+ * mode; the first LKF_EGRESS_PREFIX allocates the record buffers (LKF_ENOMEM). */
+int lkf_set_egress(lkf_engine *e, int mode);
+
+typedef struct lkf_pre {  /* 48 bytes; same order as lkf_out records */
+  uint64_t ext_sn, ext_ts; /* as lkf_out */
+  uint64_t pre_off;        /* offset of the prefix in the prefix arena (16-B aligned) */
+  uint32_t dt, pkt;        /* as lkf_out */
+  uint16_t out_len;        /* wire length = pre_len + tail_len */
+  uint8_t flags;           /* as lkf_out */
+  int8_t layer;
+  uint16_t pre_len;        /* header + CSRC + extension block (+ munged VP8 descriptor) */
+  uint16_t tail_len;
+  uint32_t tail_src;       /* offset of the tail's first byte in the batch's input arena */
+  uint32_t reserved;       /* 0 */
+} lkf_pre;
+
+/* The last run's records and prefix arena (waits like lkf_drain). */
+int lkf_drain_prefix(lkf_engine *e, lkf_pre *out, uint64_t cap, uint8_t *arena, uint64_t arena_cap, uint64_t *n_out,
+                     uint64_t *arena_len);
+/* The run `age` runs before the last one, once its emit stage has finished
+ * (as lkf_drain_run). */
+int lkf_drain_prefix_run(lkf_engine *e, uint32_t age, lkf_pre *out, uint64_t cap, uint8_t *arena,
+                         uint64_t arena_cap, uint64_t *n_out, uint64_t *arena_len);
+/* Device pointers of the last run's records and prefix arena. */
+int lkf_output_prefix_device(lkf_engine *e, const lkf_pre **d_out, uint64_t *n_out, const uint8_t **d_arena,
+                             uint64_t *arena_len);
+
 /* ---- state (Forwarder.GetState / SeedState forwarder.go:340-375) -------- */
 int lkf_get_state(lkf_engine *e, int32_t dt, lkf_fwd_state *out);
 int lkf_seed_state(lkf_engine *e, int32_t dt, const lkf_fwd_state *in);

@@ -322,6 +322,42 @@ class Engine:
         self.lib.lkf_drain_wait.argtypes = [C.c_void_p]
         self._chk(self.lib.lkf_drain_wait(self.h), "drain_wait")
 
+    def set_egress(self, mode):
+        """lkf_set_egress: abi.LKF_EGRESS_WIRE (whole wire packets, the default)
+        or abi.LKF_EGRESS_PREFIX (lkf_pre records + created bytes only) for the
+        next runs."""
+        self._chk(self.api["set_egress"](self.h, mode), "set_egress")
+
+    def drain_prefix(self):
+        """lkf_drain_prefix -> (records PRE_DTYPE, prefix arena) of the last run."""
+        n = C.c_uint64()
+        alen = C.c_uint64()
+        rc = self.api["drain_prefix"](self.h, None, 0, None, 0, C.byref(n), C.byref(alen))
+        if rc not in (0, -28):  # -28: ENOSPC for the size probe
+            self._chk(rc, "drain_prefix probe")
+        recs = np.zeros(n.value, dtype=abi.PRE_DTYPE)
+        arena = np.zeros(alen.value, dtype=np.uint8)
+        self._chk(self.api["drain_prefix"](self.h, recs.ctypes.data, n.value, arena.ctypes.data, alen.value,
+                                           C.byref(n), C.byref(alen)), "drain_prefix")
+        return recs, arena
+
+    def drain_prefix_run_into(self, age, out_ptr, cap, arena_ptr, arena_cap):
+        """lkf_drain_prefix_run into caller buffers (e.g. pinned host memory) -> (records, bytes)."""
+        n = C.c_uint64()
+        alen = C.c_uint64()
+        self._chk(self.api["drain_prefix_run"](self.h, age, out_ptr, cap, arena_ptr, arena_cap, C.byref(n),
+                                               C.byref(alen)), "drain_prefix_run")
+        return n.value, alen.value
+
+    def output_prefix_device(self):
+        d_out = C.c_void_p()
+        d_ar = C.c_void_p()
+        n = C.c_uint64()
+        alen = C.c_uint64()
+        self._chk(self.api["output_prefix_device"](self.h, C.byref(d_out), C.byref(n), C.byref(d_ar), C.byref(alen)),
+                  "output_prefix_device")
+        return d_out.value, n.value, d_ar.value, alen.value
+
     def output_device(self):
         d_out = C.c_void_p()
         d_ar = C.c_void_p()

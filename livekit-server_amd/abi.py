@@ -268,6 +268,24 @@ class lkf_out(C.Structure):
     ]
 
 
+class lkf_pre(C.Structure):  # prefix egress record (lkf_set_egress(LKF_EGRESS_PREFIX))
+    _fields_ = [
+        ("ext_sn", C.c_uint64),
+        ("ext_ts", C.c_uint64),
+        ("pre_off", C.c_uint64),
+        ("dt", C.c_uint32),
+        ("pkt", C.c_uint32),
+        ("out_len", C.c_uint16),
+        ("flags", C.c_uint8),
+        ("layer", C.c_int8),
+        ("pre_len", C.c_uint16),
+        ("tail_len", C.c_uint16),
+        ("tail_src", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
+LKF_EGRESS_WIRE, LKF_EGRESS_PREFIX = 0, 1
 LKF_DROP_NREASONS = 11
 LKF_KIND_AUDIO, LKF_KIND_VIDEO = 0, 1  # enum lkf_kind
 LKF_CTL_MUTE, LKF_CTL_PUBMUTE, LKF_CTL_SET_MAX_SPATIAL, LKF_CTL_SET_MAX_TEMPORAL = 1, 2, 3, 4
@@ -397,6 +415,12 @@ OUT_DTYPE = np.dtype(
      ("out_len", "<u2"), ("flags", "u1"), ("layer", "i1"), ("reserved", "<u4")]
 )
 assert OUT_DTYPE.itemsize == 40
+PRE_DTYPE = np.dtype(
+    [("ext_sn", "<u8"), ("ext_ts", "<u8"), ("pre_off", "<u8"), ("dt", "<u4"), ("pkt", "<u4"),
+     ("out_len", "<u2"), ("flags", "u1"), ("layer", "i1"), ("pre_len", "<u2"), ("tail_len", "<u2"),
+     ("tail_src", "<u4"), ("reserved", "<u4")]
+)
+assert C.sizeof(lkf_pre) == 48 == PRE_DTYPE.itemsize, (C.sizeof(lkf_pre), PRE_DTYPE.itemsize)
 
 
 def _bind(lib, name, restype, argtypes):
@@ -430,6 +454,15 @@ def bind_engine_api(lib, prefix):
         api["last_error"] = _bind(lib, prefix + "last_error", C.c_char_p, [e])
     api["drain"] = _bind(lib, prefix + "drain", C.c_int,
                          [e, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, P(C.c_uint64), P(C.c_uint64)])
+    if hasattr(lib, prefix + "set_egress"):  # engine only: prefix egress (the oracle emits whole wire packets)
+        api["set_egress"] = _bind(lib, prefix + "set_egress", C.c_int, [e, C.c_int])
+        api["drain_prefix"] = _bind(lib, prefix + "drain_prefix", C.c_int,
+                                    [e, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, P(C.c_uint64), P(C.c_uint64)])
+        api["drain_prefix_run"] = _bind(lib, prefix + "drain_prefix_run", C.c_int,
+                                        [e, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
+                                         P(C.c_uint64), P(C.c_uint64)])
+        api["output_prefix_device"] = _bind(lib, prefix + "output_prefix_device", C.c_int,
+                                            [e, P(C.c_void_p), P(C.c_uint64), P(C.c_void_p), P(C.c_uint64)])
     api["get_state"] = _bind(lib, prefix + "get_state", C.c_int, [e, C.c_int32, P(lkf_fwd_state)])
     api["seed_state"] = _bind(lib, prefix + "seed_state", C.c_int, [e, C.c_int32, P(lkf_fwd_state)])
     api["seq_lookup"] = _bind(lib, prefix + "seq_lookup", C.c_int,

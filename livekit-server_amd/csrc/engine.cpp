@@ -159,7 +159,13 @@ struct BatchCtx {
   DevBuf<uint32_t> dTwccBase;  // per DownTrack: the batch's first transport-wide sequence number
   DevBuf<uint32_t> dLayerList, dLayerBefore, dLayerCnt;  // k_layer_index
   DevBuf<lkf_out> dOut;
-  DevBuf<uint8_t> dOutArena;
+  DevBuf<uint8_t> dOutArena;  // wire packets, or the prefixes of a prefix-mode run
+  // prefix egress (allocated by the first lkf_set_egress(LKF_EGRESS_PREFIX)):
+  // the records, the 64-record groups' prefix byte sums and bases, the total
+  int egress = LKF_EGRESS_WIRE;  // the mode this context's run was enqueued in
+  DevBuf<lkf_pre> dPre;
+  DevBuf<uint32_t> dPreGSum;
+  DevBuf<uint64_t> dPreGBase, dPreTot;
   DevBuf<uint64_t> dStats;
   DevBuf<lkf_pkt> dPktsOwn;  // lkf_submit copies land here
   DevBuf<uint8_t> dArenaOwn;
@@ -249,6 +255,7 @@ struct lkf_engine {
   Event bktEv;                  // an ingest's bucket decisions (the sender stream copies after it)
   bool bktStorePending = false; // the next run's context waits for those copies
   lkf_cfg cfg{};
+  int egress = LKF_EGRESS_WIRE;  // lkf_set_egress: the mode of the next runs
   std::string err;
 
   // topology (host mirror)
@@ -1880,7 +1887,20 @@ int lkf_run(lkf_engine *e, void *stream) {
   // configs[1] 0.455 -> 0.54 ms, configs[2] 2.51 -> 2.83 ms, configs[3] 3.35 ->
   // 3.47 ms; profiles/r6_ab_runs.txt).
   m.ldsPad = (ingestFed && uint64_t(nd) < uint64_t(e->knobs.emitCapFanout) * std::max<uint32_t>(1, nt)) ? e->knobs.emitLdsPad : 0;
-  if (nd) HIPCHK(launch_emit(e->emitS, m), "emit");
+  x.egress = e->egress;
+  if (x.egress == LKF_EGRESS_PREFIX) {  // records + prefixes only (three launches, no payload traffic)
+    EmitPrefixLaunch q;
+    q.pre = x.dPre;
+    q.gSum = x.dPreGSum;
+    q.gBase = x.dPreGBase;
+    q.total = x.dPreTot;
+    if (nd)
+      HIPCHK(launch_emit_prefix(e->emitS, m, q), "emit prefix");
+    else
+      HIPCHK(hipMemsetAsync(x.dPreTot, 0, sizeof(uint64_t), e->emitS), "emit prefix");
+  } else if (nd) {
+    HIPCHK(launch_emit(e->emitS, m), "emit");
+  }
   HIPCHK(hipEventRecord(rg[4], e->emitS), "event");
   HIPCHK(launch_accumulate(e->emitS, x.dStats, x.dTot, e->dCum, x.dErr, e->dSticky), "accumulate");
   // (sendingPacket -> RTPStatsSender.Update of every forwarded tuple runs inside
@@ -2024,6 +2044,115 @@ int lkf_get_stats(lkf_engine *e, lkf_stats *out) {
   return rc;
 }
 
+// The accessors of one egress mode refuse a run enqueued in the other.
+static int egress_is(lkf_engine *e, const BatchCtx &x, int mode) {
+  if (x.egress == mode) return LKF_OK;
+  e->err = mode == LKF_EGRESS_WIRE
+               ? "the run was enqueued in prefix egress mode: read it with lkf_drain_prefix* / lkf_output_prefix_device"
+               : "the run was enqueued in wire egress mode: read it with lkf_drain* / lkf_output_device";
+  return LKF_EINVAL;
+}
+
+int lkf_set_egress(lkf_engine *e, int mode) {
+  if (!e) return LKF_EINVAL;
+  if (mode != LKF_EGRESS_WIRE && mode != LKF_EGRESS_PREFIX) {
+    e->err = "unknown egress mode";
+    return LKF_EINVAL;
+  }
+  if (mode == LKF_EGRESS_PREFIX) {
+    HIPCHK(hipSetDevice(e->dev), "hipSetDevice");
+    const uint64_t groups = e->cfg.max_out_pkts / 64 + 2;
+    for (auto &x : e->ctx) {
+      const bool ok = (x.dPre || !x.dPre.alloc(e->cfg.max_out_pkts)) && (x.dPreGSum || !x.dPreGSum.alloc(groups)) &&
+                      (x.dPreGBase || !x.dPreGBase.alloc(groups)) && (x.dPreTot || !x.dPreTot.alloc(1));
+      if (!ok) {
+        (void)hipGetLastError();
+        e->err = "prefix egress: out of device memory for the record buffers";
+        return LKF_ENOMEM;
+      }
+    }
+  }
+  e->egress = mode;
+  return LKF_OK;
+}
+
+// The prefix accessors' common part: the run of context x was a prefix-mode
+// run within the engine's capacity -> its record count and prefix arena bytes.
+static int prefix_totals(lkf_engine *e, BatchCtx &x, uint64_t *n_out, uint64_t *arena_len) {
+  const int rc = egress_is(e, x, LKF_EGRESS_PREFIX);
+  if (rc) return rc;
+  uint64_t tot[4], pre = 0;
+  D2H(tot, x.dTot, sizeof(tot), "tot copy");
+  D2H(&pre, x.dPreTot, sizeof(pre), "prefix tot copy");
+  if (n_out) *n_out = tot[2];
+  if (arena_len) *arena_len = pre;
+  // a batch over the wire capacities wrote nothing (see lkf_output_device); the
+  // prefix arena never needs more than the wire arena
+  if (tot[2] > e->cfg.max_out_pkts || tot[3] > e->cfg.max_out_bytes || pre > e->cfg.max_out_bytes) {
+    e->err = "output or tuple capacity exceeded";
+    return LKF_ENOSPC;
+  }
+  return LKF_OK;
+}
+static int prefix_copy(lkf_engine *e, BatchCtx &x, lkf_pre *out, uint64_t cap, uint8_t *arena, uint64_t arena_cap,
+                       uint64_t *n_out, uint64_t *arena_len) {
+  uint64_t n = 0, len = 0;
+  const int rc = prefix_totals(e, x, &n, &len);
+  if (n_out) *n_out = n;
+  if (arena_len) *arena_len = len;
+  if (rc) return rc;
+  if (n > cap || len > arena_cap) return LKF_ENOSPC;
+  if (out && n) {
+    const int r = copy_to_host(e, out, x.dPre, n * sizeof(lkf_pre), "drain prefix recs");
+    if (r) return r;
+  }
+  if (arena && len) return copy_to_host(e, arena, x.dOutArena, len, "drain prefix bytes");
+  return LKF_OK;
+}
+
+int lkf_output_prefix_device(lkf_engine *e, const lkf_pre **d_out, uint64_t *n_out, const uint8_t **d_arena,
+                             uint64_t *arena_len) {
+  if (!e) return LKF_EINVAL;
+  int rc = lkf_sync(e);
+  if (rc) return rc;
+  if (n_out) *n_out = 0;
+  if (arena_len) *arena_len = 0;
+  if (e->lastCtx < 0) {
+    if (d_out) *d_out = e->ctx[0].dPre;
+    if (d_arena) *d_arena = e->ctx[0].dOutArena;
+    return LKF_OK;
+  }
+  BatchCtx &x = e->ctx[e->lastCtx];
+  rc = prefix_totals(e, x, n_out, arena_len);
+  if (rc) return rc;
+  if (d_out) *d_out = x.dPre;
+  if (d_arena) *d_arena = x.dOutArena;
+  return LKF_OK;
+}
+
+int lkf_drain_prefix(lkf_engine *e, lkf_pre *out, uint64_t cap, uint8_t *arena, uint64_t arena_cap, uint64_t *n_out,
+                     uint64_t *arena_len) {
+  if (!e) return LKF_EINVAL;
+  const int rc = lkf_sync(e);
+  if (rc) return rc;
+  if (e->lastCtx < 0) {
+    if (n_out) *n_out = 0;
+    if (arena_len) *arena_len = 0;
+    return LKF_OK;
+  }
+  return prefix_copy(e, e->ctx[e->lastCtx], out, cap, arena, arena_cap, n_out, arena_len);
+}
+
+int lkf_drain_prefix_run(lkf_engine *e, uint32_t age, lkf_pre *out, uint64_t cap, uint8_t *arena, uint64_t arena_cap,
+                         uint64_t *n_out, uint64_t *arena_len) {
+  if (!e || age >= uint32_t(lkf_engine::kCtx) || uint64_t(age) >= e->nRuns) return LKF_EINVAL;
+  HIPCHK(hipSetDevice(e->dev), "hipSetDevice");
+  BatchCtx &x = e->ctx[(e->nRuns - 1 - age) % lkf_engine::kCtx];
+  if (const int rc = egress_is(e, x, LKF_EGRESS_PREFIX)) return rc;
+  HIPCHK(hipEventSynchronize(x.emitted), "wait emitted");
+  return prefix_copy(e, x, out, cap, arena, arena_cap, n_out, arena_len);
+}
+
 int lkf_output_device(lkf_engine *e, const lkf_out **d_out, uint64_t *n_out, const uint8_t **d_arena,
                       uint64_t *arena_len) {
   if (!e) return LKF_EINVAL;
@@ -2037,6 +2166,8 @@ int lkf_output_device(lkf_engine *e, const lkf_out **d_out, uint64_t *n_out, con
     return LKF_OK;
   }
   BatchCtx &x = e->ctx[e->lastCtx];
+  rc = egress_is(e, x, LKF_EGRESS_WIRE);
+  if (rc) return rc;
   uint64_t tot[4];
   D2H(tot, x.dTot, sizeof(tot), "tot copy");
   // a batch whose output exceeded the engine's capacity wrote nothing (k_emit
@@ -2076,6 +2207,7 @@ int lkf_drain_run(lkf_engine *e, uint32_t age, lkf_out *out, uint64_t cap, uint8
   if (!e || age >= uint32_t(lkf_engine::kCtx) || uint64_t(age) >= e->nRuns) return LKF_EINVAL;
   HIPCHK(hipSetDevice(e->dev), "hipSetDevice");
   BatchCtx &x = e->ctx[(e->nRuns - 1 - age) % lkf_engine::kCtx];
+  if (const int rc = egress_is(e, x, LKF_EGRESS_WIRE)) return rc;
   HIPCHK(hipEventSynchronize(x.emitted), "wait emitted");
   uint64_t tot[4];
   D2H(tot, x.dTot, sizeof(tot), "tot copy");
@@ -2103,6 +2235,7 @@ int lkf_drain_run_async(lkf_engine *e, uint32_t age, lkf_out *out, uint64_t cap,
   HIPCHK(hipSetDevice(e->dev), "hipSetDevice");
   if (!e->d2hS) HIPCHK(hipStreamCreateWithFlags(e->d2hS.put(), hipStreamNonBlocking), "copy stream");
   BatchCtx &x = e->ctx[(e->nRuns - 1 - age) % lkf_engine::kCtx];
+  if (const int rc = egress_is(e, x, LKF_EGRESS_WIRE)) return rc;
   HIPCHK(hipEventSynchronize(x.emitted), "wait emitted");
   uint64_t tot[4];
   D2H(tot, x.dTot, sizeof(tot), "tot copy");
@@ -2211,6 +2344,8 @@ int lkf_protect(lkf_engine *e, int64_t send_time_ns) {
   int rc = srtp_init(e);
   if (rc) return rc;
   BatchCtx &x = e->ctx[e->lastCtx];
+  rc = egress_is(e, x, LKF_EGRESS_WIRE);  // (no SRTP over prefixes: that host protects in pion)
+  if (rc) return rc;
   if (!x.dProt)
     HIPCHK(x.dProt.alloc(e->cfg.max_out_bytes + 16 * uint64_t(e->cfg.max_out_pkts)), "alloc protected arena");
   SrtpProtectArgs a;

@@ -17,6 +17,10 @@
 //                   extension block + munged VP8 descriptor from LDS, payload
 //                   copied byte-shifted from the input arena (coalesced
 //                   dwordx4 loads/stores); one lkf_out record per tuple.
+//   k_emit_prelen / k_emit_prescan / k_emit_prefix
+//                   instead of k_emit in prefix egress mode: one lkf_pre record
+//                   per tuple and only the bytes k_emit takes from LDS; the
+//                   payload is referenced in the input arena, not copied.
 //
 // No MFMA: nothing here is a contraction.  The emit kernel is HBM-bound
 // (writes ~ out bytes, input payload re-reads served from L2/MALL).
@@ -3663,6 +3667,193 @@ __device__ __forceinline__ void store16(u8 *p, uint4 v) {
   __builtin_nontemporal_store(v.w, reinterpret_cast<u32 *>(p) + 3);
 }
 
+// ---------------------------------------------------------------------------
+// The prefix builder (lane = record), shared by k_emit, the prefix egress's
+// length pass and k_emit_prefix: emit_locate finds the record's owner and loads
+// what its wire packet is made from, emit_marshal writes the bytes the engine
+// creates (RTP header, CSRCs, extension block, munged VP8 descriptor) and
+// returns their count.  WRITE = false only counts (the stores and the loads
+// that feed nothing but them fall away).
+// ---------------------------------------------------------------------------
+struct EmitRec {
+  u64 extSN, extTS;
+  u64 outOff;  // the wire packet's offset in the (wire-layout) output arena
+  u64 src;     // arena offset of the first payload byte the wire packet copies (after a munged VP8 descriptor)
+  u32 d, ord;  // DownTrack, the record's ordinal in the DownTrack's output of this batch
+  u32 pkt, len, flags, ddLen, aux;
+  PktV p;
+  DevDT dt;
+};
+
+__device__ __forceinline__ EmitRec emit_locate(const EmitArgs &A, u64 r, u32 pLo, u32 pHi) {
+  EmitRec q;
+  // position owning record r: last p in [pLo, pHi) with recBase[p] <= r
+  u32 lo = pLo, hi = pHi;
+  while (hi - lo > 1) {
+    const u32 mid = (lo + hi) >> 1;
+    if (A.recBase[mid] <= r)
+      lo = mid;
+    else
+      hi = mid;
+  }
+  CHK(lo < A.ndts, CK_EMIT_POS, lo, A.ndts);
+  const u32 d = A.perm[lo];
+  CHK(d < A.maxDts, CK_EMIT_DT, d, A.maxDts);
+  CHK(A.slotBase[d] + (r - A.recBase[lo]) < A.tupleCap, CK_EMIT_TUPLE, A.slotBase[d] + (r - A.recBase[lo]),
+      A.tupleCap);
+  const FwdRec *rp = A.recs + (A.slotBase[d] + (r - A.recBase[lo]));
+  const U4x8 ra = *reinterpret_cast<const U4x8 *>(rp);  // sn, ts, pkt, rel16
+  const uint2 rb = reinterpret_cast<const uint2 *>(rp)[2];  // outLen | flags | ddLen, aux
+  const u32 tPkt = ra.z, tLen = rb.x & 0xffffu, tFlags = (rb.x >> 16) & 0xffu, tDDLen = rb.x >> 24, tAux = rb.y;
+  CHK(tPkt < A.npkts, CK_EMIT_PKT, tPkt, A.npkts);
+  q.p = load_pkt(A.pkts + tPkt);
+  q.dt = A.dts[d];
+  const FwdBase fb = A.fbase[d];
+  q.outOff = A.byteBase[lo] + (u64(ra.w) << 4);
+  CHK(r < A.outCap, CK_EMIT_OUT, r, A.outCap);
+  CHK(q.outOff + tLen <= A.outByteCap, CK_EMIT_BYTES, q.outOff + tLen, A.outByteCap);
+  CHK(u64(q.p.arenaOff) + q.p.poff + q.p.plen <= A.arenaLen, CK_EMIT_ARENA, u64(q.p.arenaOff) + q.p.poff + q.p.plen,
+      A.arenaLen);
+  CHK(!(tFlags & T_DD) || u64(tAux) + tDDLen <= A.ddCap, CK_EMIT_DD, u64(tAux) + tDDLen, A.ddCap);
+  q.extSN = widen32(fb.sn, ra.x);
+  q.extTS = widen32(fb.ts, ra.y);
+  if (tFlags & T_WIDE) {
+    const FwdBase wv = A.wide[A.slotBase[d] + (r - A.recBase[lo])];
+    q.extSN = wv.sn;
+    q.extTS = wv.ts;
+  }
+  q.d = d;
+  q.ord = u32(r - A.recBase[lo]);
+  q.pkt = tPkt;
+  q.len = tLen;
+  q.flags = tFlags;
+  q.ddLen = tDDLen;
+  q.aux = tAux;
+  // translateVP8PacketTo: the munged descriptor replaces the incoming one
+  q.src = u64(q.p.arenaOff) + q.p.poff + ((tFlags & T_CODEC) ? u32(q.p.vhs) : 0u);
+  return q;
+}
+
+template <int PRE, bool WRITE>
+__device__ __forceinline__ int emit_marshal(const EmitArgs &A, const EmitRec &q, u8 *w) {
+  const PktV &p = q.p;
+  const DevDT &dt = q.dt;
+  const u32 tFlags = q.flags, tAux = q.aux;
+  const int tDDLen = int(q.ddLen);
+  auto put = [&](int i, u8 v) {
+    if (WRITE) w[i] = v;
+  };
+  // RTP header (getTranslatedRTPHeader downtrack.go:1714-1726)
+  const int cc = p.hdr0 & 0xf;
+  const bool playout = tFlags & T_PLAYOUT;
+  const bool ddOn = (PRE == PRE_MAX_DD) && (tFlags & T_DD);
+  const bool hasExt = playout || dt.extAbs || ddOn || dt.extTcc;
+  // pion's TWCC HeaderExtensionInterceptor: the transport's next sequence
+  // number in send order (this record's ordinal in its DownTrack's output
+  // after the DownTrack's base)
+  const u16 tcc = dt.extTcc ? u16(A.twccBase[q.d] + q.ord) : u16(0);
+  put(0, u8((p.hdr0 & 0xe0) | (hasExt ? 0x10 : 0) | cc));  // V, P copied; X per new extensions
+  put(1, u8(((tFlags & LKF_OUT_MARKER) ? 0x80 : 0) | (dt.pt & 0x7f)));
+  const u16 sn = u16(q.extSN);
+  const u32 ts = u32(q.extTS);
+  put(2, u8(sn >> 8));
+  put(3, u8(sn));
+  put(4, u8(ts >> 24));
+  put(5, u8(ts >> 16));
+  put(6, u8(ts >> 8));
+  put(7, u8(ts));
+  put(8, u8(dt.ssrc >> 24));
+  put(9, u8(dt.ssrc >> 16));
+  put(10, u8(dt.ssrc >> 8));
+  put(11, u8(dt.ssrc));
+  int n = 12;
+  if (WRITE) {  // (the only arena bytes a prefix holds: the CSRCs of a packet with CC > 0)
+    const u8 *raw = A.arena + p.arenaOff;
+    for (int i = 0; i < 4 * cc; i++) w[n + i] = raw[12 + i];
+  }
+  n += 4 * cc;
+  if (hasExt && !(ddOn && tDDLen > 16)) {  // pion Header.MarshalTo one-byte profile (RFC 8285)
+    const int eb = (ddOn ? 1 + tDDLen : 0) + (playout ? 4 : 0) + (dt.extAbs ? 4 : 0) + (dt.extTcc ? 3 : 0);
+    const int words = (eb + 3) >> 2;
+    put(n++, 0xBE);
+    put(n++, 0xDE);
+    put(n++, u8(words >> 8));
+    put(n++, u8(words));
+    if (ddOn) {  // the DD element first (pacer/base.go:77-83)
+      put(n++, u8((dt.extDD << 4) | (tDDLen - 1)));
+      if (WRITE)
+        for (int i = 0; i < tDDLen; i++) w[n + i] = A.ddArena[tAux + i];
+      n += tDDLen;
+    }
+    if (playout) {
+      put(n++, u8((dt.extPlayout << 4) | 2));
+      put(n++, dt.playout[0]);
+      put(n++, dt.playout[1]);
+      put(n++, dt.playout[2]);
+    }
+    if (dt.extAbs) {
+      put(n++, u8((dt.extAbs << 4) | 2));
+      put(n++, 0);
+      put(n++, 0);
+      put(n++, 0);
+    }
+    if (dt.extTcc) {  // rtp.TransportCCExtension.Marshal: big-endian u16
+      put(n++, u8((dt.extTcc << 4) | 1));
+      put(n++, u8(tcc >> 8));
+      put(n++, u8(tcc));
+    }
+    for (int i = eb; i < 4 * words; i++) put(n++, 0);
+  } else if (hasExt) {  // two-byte profile 0x1000: a DD element above 16 B
+    const int eb = 2 + tDDLen + (playout ? 5 : 0) + (dt.extAbs ? 5 : 0) + (dt.extTcc ? 4 : 0);
+    const int words = (eb + 3) >> 2;
+    put(n++, 0x10);
+    put(n++, 0x00);
+    put(n++, u8(words >> 8));
+    put(n++, u8(words));
+    put(n++, dt.extDD);
+    put(n++, u8(tDDLen));
+    if (WRITE)
+      for (int i = 0; i < tDDLen; i++) w[n + i] = A.ddArena[tAux + i];
+    n += tDDLen;
+    if (playout) {
+      put(n++, dt.extPlayout);
+      put(n++, 3);
+      put(n++, dt.playout[0]);
+      put(n++, dt.playout[1]);
+      put(n++, dt.playout[2]);
+    }
+    if (dt.extAbs) {
+      put(n++, dt.extAbs);
+      put(n++, 3);
+      put(n++, 0);
+      put(n++, 0);
+      put(n++, 0);
+    }
+    if (dt.extTcc) {
+      put(n++, dt.extTcc);
+      put(n++, 2);
+      put(n++, u8(tcc >> 8));
+      put(n++, u8(tcc));
+    }
+    for (int i = eb; i < 4 * words; i++) put(n++, 0);
+  }
+  if (tFlags & T_CODEC) {  // translateVP8PacketTo downtrack.go:1728-1736: the munged
+                           // descriptor, re-marshalled from its munged fields as decide did
+    const u16 mpid = u16(tAux & 0xffffu);
+    const bool mM = mpid > 127, M = p.vbits & LKF_VP8_M;
+    const int hs = int(p.vhs) + (mM == M ? 0 : (mM ? 1 : -1));
+    u64 cb = 0;
+    const int cl = vp8_marshal(p.vfirst, p.vbits & LKF_VP8_I, mM, mpid, p.vbits & LKF_VP8_L, u8(tAux >> 16),
+                               p.vbits & LKF_VP8_T, p.tid, p.vbits & LKF_VP8_Y, p.vbits & LKF_VP8_K,
+                               u8(tAux >> 24), hs, cb);
+#pragma unroll
+    for (int i = 0; i < 6; i++)
+      if (i < cl) put(n + i, u8(cb >> (8 * i)));
+    n += cl > 0 ? cl : 0;
+  }
+  return n;
+}
+
 #ifndef LKF_EMIT_XCD  // (A/B) the XCD-aware group partition (1) or a plain grid-stride (0)
 #define LKF_EMIT_XCD 1
 #endif
@@ -3708,156 +3899,23 @@ __global__ void __launch_bounds__(EMIT_T) k_emit(EmitArgs A) {
     const u32 pHi = (g + 1 < ngroups) ? A.gFirst[g + 1] + 1 : A.ndts;
     u64 outOff = 0;
     if (lane < nrec) {
-      const u64 r = r0 + lane;
-      // position owning record r: last p in [pLo, pHi) with recBase[p] <= r
-      u32 lo = pLo, hi = pHi;
-      while (hi - lo > 1) {
-        const u32 mid = (lo + hi) >> 1;
-        if (A.recBase[mid] <= r)
-          lo = mid;
-        else
-          hi = mid;
-      }
-      CHK(lo < A.ndts, CK_EMIT_POS, lo, A.ndts);
-      const u32 d = A.perm[lo];
-      CHK(d < A.maxDts, CK_EMIT_DT, d, A.maxDts);
-      CHK(A.slotBase[d] + (r - A.recBase[lo]) < A.tupleCap, CK_EMIT_TUPLE, A.slotBase[d] + (r - A.recBase[lo]),
-          A.tupleCap);
-      const FwdRec *rp = A.recs + (A.slotBase[d] + (r - A.recBase[lo]));
-      const U4x8 ra = *reinterpret_cast<const U4x8 *>(rp);  // sn, ts, pkt, rel16
-      const uint2 rb = reinterpret_cast<const uint2 *>(rp)[2];  // outLen | flags | ddLen, aux
-      const u32 tPkt = ra.z, tLen = rb.x & 0xffffu, tFlags = (rb.x >> 16) & 0xffu, tDDLen = rb.x >> 24, tAux = rb.y;
-      CHK(tPkt < A.npkts, CK_EMIT_PKT, tPkt, A.npkts);
-      const PktV p = load_pkt(A.pkts + tPkt);
-      const DevDT dt = A.dts[d];
-      const FwdBase fb = A.fbase[d];
-      outOff = A.byteBase[lo] + (u64(ra.w) << 4);
-      CHK(r < A.outCap, CK_EMIT_OUT, r, A.outCap);
-      CHK(outOff + tLen <= A.outByteCap, CK_EMIT_BYTES, outOff + tLen, A.outByteCap);
-      CHK(u64(p.arenaOff) + p.poff + p.plen <= A.arenaLen, CK_EMIT_ARENA, u64(p.arenaOff) + p.poff + p.plen,
-          A.arenaLen);
-      CHK(!(tFlags & T_DD) || u64(tAux) + tDDLen <= A.ddCap, CK_EMIT_DD, u64(tAux) + tDDLen, A.ddCap);
-      u64 extSN = widen32(fb.sn, ra.x), extTS = widen32(fb.ts, ra.y);
-      if (tFlags & T_WIDE) {
-        const FwdBase wv = A.wide[A.slotBase[d] + (r - A.recBase[lo])];
-        extSN = wv.sn;
-        extTS = wv.ts;
-      }
+      const EmitRec q = emit_locate(A, r0 + lane, pLo, pHi);
+      const u32 tLen = q.len;
+      outOff = q.outOff;
       lkf_out o;
-      o.ext_sn = extSN;
-      o.ext_ts = extTS;
+      o.ext_sn = q.extSN;
+      o.ext_ts = q.extTS;
       o.out_off = outOff;
-      o.dt = d;
-      o.pkt = tPkt;
+      o.dt = q.d;
+      o.pkt = q.pkt;
       o.out_len = u16(tLen);
-      o.flags = u8(tFlags & 0x0f);  // (the T_* bits stay internal)
-      o.layer = p.layer;
+      o.flags = u8(q.flags & 0x0f);  // (the T_* bits stay internal)
+      o.layer = q.p.layer;
       o.reserved = 0;
-      A.out[r] = o;
-      // prefix: RTP header (getTranslatedRTPHeader downtrack.go:1714-1726)
+      A.out[r0 + lane] = o;
       u8 *w = pre[lane];
-      const int cc = p.hdr0 & 0xf;
-      const bool playout = tFlags & T_PLAYOUT;
-      const bool ddOn = (PRE == PRE_MAX_DD) && (tFlags & T_DD);
-      const bool hasExt = playout || dt.extAbs || ddOn || dt.extTcc;
-      // pion's TWCC HeaderExtensionInterceptor: the transport's next sequence
-      // number in send order (this record's ordinal in its DownTrack's output
-      // after the DownTrack's base)
-      const u16 tcc = dt.extTcc ? u16(A.twccBase[d] + u32(r - A.recBase[lo])) : u16(0);
-      w[0] = u8((p.hdr0 & 0xe0) | (hasExt ? 0x10 : 0) | cc);  // V, P copied; X per new extensions
-      w[1] = u8(((tFlags & LKF_OUT_MARKER) ? 0x80 : 0) | (dt.pt & 0x7f));
-      const u16 sn = u16(extSN);
-      const u32 ts = u32(extTS);
-      w[2] = u8(sn >> 8);
-      w[3] = u8(sn);
-      w[4] = u8(ts >> 24);
-      w[5] = u8(ts >> 16);
-      w[6] = u8(ts >> 8);
-      w[7] = u8(ts);
-      w[8] = u8(dt.ssrc >> 24);
-      w[9] = u8(dt.ssrc >> 16);
-      w[10] = u8(dt.ssrc >> 8);
-      w[11] = u8(dt.ssrc);
-      int n = 12;
-      const u8 *raw = A.arena + p.arenaOff;
-      for (int i = 0; i < 4 * cc; i++) w[n++] = raw[12 + i];
-      if (hasExt && !(ddOn && tDDLen > 16)) {  // pion Header.MarshalTo one-byte profile (RFC 8285)
-        const int eb = (ddOn ? 1 + tDDLen : 0) + (playout ? 4 : 0) + (dt.extAbs ? 4 : 0) + (dt.extTcc ? 3 : 0);
-        const int words = (eb + 3) >> 2;
-        w[n++] = 0xBE;
-        w[n++] = 0xDE;
-        w[n++] = u8(words >> 8);
-        w[n++] = u8(words);
-        if (ddOn) {  // the DD element first (pacer/base.go:77-83)
-          w[n++] = u8((dt.extDD << 4) | (tDDLen - 1));
-          for (int i = 0; i < tDDLen; i++) w[n++] = A.ddArena[tAux + i];
-        }
-        if (playout) {
-          w[n++] = u8((dt.extPlayout << 4) | 2);
-          w[n++] = dt.playout[0];
-          w[n++] = dt.playout[1];
-          w[n++] = dt.playout[2];
-        }
-        if (dt.extAbs) {
-          w[n++] = u8((dt.extAbs << 4) | 2);
-          w[n++] = 0;
-          w[n++] = 0;
-          w[n++] = 0;
-        }
-        if (dt.extTcc) {  // rtp.TransportCCExtension.Marshal: big-endian u16
-          w[n++] = u8((dt.extTcc << 4) | 1);
-          w[n++] = u8(tcc >> 8);
-          w[n++] = u8(tcc);
-        }
-        for (int i = eb; i < 4 * words; i++) w[n++] = 0;
-      } else if (hasExt) {  // two-byte profile 0x1000: a DD element above 16 B
-        const int eb = 2 + tDDLen + (playout ? 5 : 0) + (dt.extAbs ? 5 : 0) + (dt.extTcc ? 4 : 0);
-        const int words = (eb + 3) >> 2;
-        w[n++] = 0x10;
-        w[n++] = 0x00;
-        w[n++] = u8(words >> 8);
-        w[n++] = u8(words);
-        w[n++] = dt.extDD;
-        w[n++] = tDDLen;
-        for (int i = 0; i < tDDLen; i++) w[n++] = A.ddArena[tAux + i];
-        if (playout) {
-          w[n++] = dt.extPlayout;
-          w[n++] = 3;
-          w[n++] = dt.playout[0];
-          w[n++] = dt.playout[1];
-          w[n++] = dt.playout[2];
-        }
-        if (dt.extAbs) {
-          w[n++] = dt.extAbs;
-          w[n++] = 3;
-          w[n++] = 0;
-          w[n++] = 0;
-          w[n++] = 0;
-        }
-        if (dt.extTcc) {
-          w[n++] = dt.extTcc;
-          w[n++] = 2;
-          w[n++] = u8(tcc >> 8);
-          w[n++] = u8(tcc);
-        }
-        for (int i = eb; i < 4 * words; i++) w[n++] = 0;
-      }
-      u64 src = u64(p.arenaOff) + p.poff;
-      if (tFlags & T_CODEC) {  // translateVP8PacketTo downtrack.go:1728-1736: the munged
-                               // descriptor, re-marshalled from its munged fields as decide did
-        const u16 mpid = u16(tAux & 0xffffu);
-        const bool mM = mpid > 127, M = p.vbits & LKF_VP8_M;
-        const int hs = int(p.vhs) + (mM == M ? 0 : (mM ? 1 : -1));
-        u64 cb = 0;
-        const int cl = vp8_marshal(p.vfirst, p.vbits & LKF_VP8_I, mM, mpid, p.vbits & LKF_VP8_L, u8(tAux >> 16),
-                                   p.vbits & LKF_VP8_T, p.tid, p.vbits & LKF_VP8_Y, p.vbits & LKF_VP8_K,
-                                   u8(tAux >> 24), hs, cb);
-#pragma unroll
-        for (int i = 0; i < 6; i++)
-          if (i < cl) w[n + i] = u8(cb >> (8 * i));
-        n += cl > 0 ? cl : 0;
-        src += p.vhs;
-      }
+      const int n = emit_marshal<PRE, true>(A, q, w);
+      const u64 src = q.src;
       // LDS region = prefix rounded up to 16 B, its tail filled from the
       // payload (so every 16-B chunk is either all-LDS or all-payload)
       const int R = (n + 15) & ~15;
@@ -3938,6 +3996,148 @@ __global__ void __launch_bounds__(EMIT_T) k_emit(EmitArgs A) {
       }
       cur += k;
       c0 = wEnd;
+    }
+    __syncthreads();  // LDS reused by the next group
+  }
+}
+
+// ---------------------------------------------------------------------------
+// Prefix egress (LKF_EGRESS_PREFIX): per record an lkf_pre and only the bytes
+// the engine creates; the payload tail stays in the caller's input arena
+// (tail_src).  Prefixes are packed 16-B aligned in record order, so a record's
+// offset depends on every record before it.  Three launches in stream order,
+// no hand-off between workgroups inside a launch:
+//   k_emit_prelen   one wave per 64-record group: the sum of its rounded
+//                   prefix lengths (the builder with WRITE = false);
+//   k_emit_prescan  one workgroup: exclusive scan of the group sums + total;
+//   k_emit_prefix   one wave per group: prefixes in LDS (zero padded), records
+//                   as 16-B stores, then a flat sweep of the group's 16-B
+//                   chunks from LDS to the prefix arena.
+// A batch over the wire capacities writes nothing (as k_emit): the prefix
+// arena is the context's output arena and round16(pre_len) <= round16(out_len).
+// ---------------------------------------------------------------------------
+struct EmitPreArgs {
+  EmitArgs e;       // (e.out unused; e.outArena = the prefix arena)
+  lkf_pre *pre;
+  u32 *gSum;        // [group] sum of round16(pre_len)
+  u64 *gBase;       // [group] exclusive scan of gSum
+  u64 *preTotal;    // prefix arena bytes of the batch (0 for a batch over capacity)
+};
+constexpr int PRESCAN_T = 1024;
+
+__device__ __forceinline__ bool emit_over_capacity(const EmitArgs &A) {
+  return A.totals[0] > A.outCap || A.totals[1] > A.outByteCap;
+}
+
+template <int PRE>
+__global__ void __launch_bounds__(EMIT_T) k_emit_prelen(EmitPreArgs P) {
+  const EmitArgs &A = P.e;
+  const u32 lane = threadIdx.x;
+  const u64 total = A.totals[0];
+  const u64 ngroups = (total + EMIT_G - 1) / EMIT_G;
+  if (emit_over_capacity(A)) return;
+  for (u64 g = blockIdx.x; g < ngroups; g += gridDim.x) {
+    const u64 r0 = g * EMIT_G;
+    const u32 nrec = u32(min(u64(EMIT_G), total - r0));
+    CHK(g + 1 < A.gCap, CK_EMIT_GROUP, g + 1, A.gCap);
+    const u32 pLo = A.gFirst[g];
+    const u32 pHi = (g + 1 < ngroups) ? A.gFirst[g + 1] + 1 : A.ndts;
+    u32 R = 0;
+    if (lane < nrec) {
+      const EmitRec q = emit_locate(A, r0 + lane, pLo, pHi);
+      R = u32(emit_marshal<PRE, false>(A, q, nullptr) + 15) & ~15u;
+    }
+    const u32 s = wave_sum_u32(R);
+    if (lane == 0) P.gSum[g] = s;
+  }
+}
+
+__global__ void __launch_bounds__(PRESCAN_T) k_emit_prescan(EmitPreArgs P) {
+  __shared__ u64 sWave[PRESCAN_T / 64];
+  const EmitArgs &A = P.e;
+  const u32 tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
+  const u64 ngroups = emit_over_capacity(A) ? 0 : (A.totals[0] + EMIT_G - 1) / EMIT_G;
+  u64 carry = 0;  // (the same in every thread)
+  for (u64 b = 0; b < ngroups; b += PRESCAN_T) {
+    const u64 i = b + tid;
+    CHK(i >= ngroups || i < A.gCap, CK_EMIT_GROUP, i, A.gCap);
+    const u32 v = i < ngroups ? P.gSum[i] : 0u;
+    const u32 ex = excl_scan_u32(v, lane);  // (a group's sum is below 2^15, a wave's below 2^21)
+    if (lane == 63) sWave[wv] = u64(ex) + v;
+    __syncthreads();
+    u64 before = 0, tile = 0;
+#pragma unroll
+    for (int k = 0; k < PRESCAN_T / 64; k++) {
+      const u64 x = sWave[k];
+      before += u32(k) < wv ? x : 0;
+      tile += x;
+    }
+    if (i < ngroups) P.gBase[i] = carry + before + ex;
+    carry += tile;
+    __syncthreads();  // sWave is rewritten by the next tile
+  }
+  if (tid == 0) *P.preTotal = carry;
+}
+
+template <int PRE>
+__global__ void __launch_bounds__(EMIT_T) k_emit_prefix(EmitPreArgs P) {
+  __shared__ __attribute__((aligned(16))) u8 pre[EMIT_G][PRE];
+  __shared__ u32 sCs[EMIT_G];  // first chunk of the record, relative to the group (lanes past the group: its chunks)
+  const EmitArgs &A = P.e;
+  const u32 lane = threadIdx.x;
+  const u64 total = A.totals[0];
+  const u64 ngroups = (total + EMIT_G - 1) / EMIT_G;
+  if (emit_over_capacity(A)) {
+    if (blockIdx.x == 0 && lane == 0) atomicOr(A.err, 4u);
+    return;
+  }
+  for (u64 g = blockIdx.x; g < ngroups; g += gridDim.x) {
+    const u64 r0 = g * EMIT_G;
+    const u32 nrec = u32(min(u64(EMIT_G), total - r0));
+    // ---- prefix phase: lane = record
+    CHK(g + 1 < A.gCap, CK_EMIT_GROUP, g + 1, A.gCap);
+    const u32 pLo = A.gFirst[g];
+    const u32 pHi = (g + 1 < ngroups) ? A.gFirst[g + 1] + 1 : A.ndts;
+    const u64 gByte = P.gBase[g];
+    EmitRec q;
+    int n = 0;
+    u32 R = 0;
+    if (lane < nrec) {
+      q = emit_locate(A, r0 + lane, pLo, pHi);
+      u8 *w = pre[lane];
+      n = emit_marshal<PRE, true>(A, q, w);
+      R = u32(n + 15) & ~15u;
+      for (u32 i = u32(n); i < R; i++) w[i] = 0;
+    }
+    const u32 cs = excl_scan_u32(R >> 4, lane);
+    const u32 nchunks = rl32(cs + (R >> 4), 63);
+    sCs[lane] = cs;
+    if (lane < nrec) {  // the 48-B record as three 16-B stores
+      const u64 off = gByte + (u64(cs) << 4);
+      const u32 tailLen = q.len - u32(n);
+      CHK(r0 + lane < A.outCap, CK_EMIT_OUT, r0 + lane, A.outCap);
+      u8 *o = reinterpret_cast<u8 *>(P.pre + (r0 + lane));
+      store16(o, make_uint4(u32(q.extSN), u32(q.extSN >> 32), u32(q.extTS), u32(q.extTS >> 32)));
+      store16(o + 16, make_uint4(u32(off), u32(off >> 32), q.d, q.pkt));
+      store16(o + 32, make_uint4((q.len & 0xffffu) | ((q.flags & 0x0fu) << 16) | (u32(u8(q.p.layer)) << 24),
+                                 u32(n) | (tailLen << 16), u32(q.src), 0u));
+    }
+    __syncthreads();  // one wave: orders the LDS writes above before the cross-lane reads below
+    // ---- copy phase: flat sweep of the group's 16-B chunks, all from LDS
+    u8 *const outG = A.outArena + gByte;
+    for (u32 c = lane; c < nchunks; c += 64) {
+      u32 lo = 0, hi = nrec;  // the chunk's record: last j with sCs[j] <= c
+      while (hi - lo > 1) {
+        const u32 mid = (lo + hi) >> 1;
+        if (sCs[mid] <= c)
+          lo = mid;
+        else
+          hi = mid;
+      }
+      const uint4 v = *reinterpret_cast<const uint4 *>(&pre[lo][(c - sCs[lo]) << 4]);
+      CHK(gByte + (u64(c) << 4) + 16 <= A.outByteCap + 64, CK_EMIT_BYTES, gByte + (u64(c) << 4) + 16,
+          A.outByteCap + 64);
+      store16(outG + (u64(c) << 4), v);
     }
     __syncthreads();  // LDS reused by the next group
   }
@@ -5004,7 +5204,40 @@ hipError_t launch_twcc_stamp(hipStream_t s, const DevDT *dts, uint32_t *ctrD, ui
   return hipGetLastError();
 }
 
+static EmitArgs emit_args(const EmitLaunch &a);
+
 hipError_t launch_emit(hipStream_t s, const EmitLaunch &a) {
+  const EmitArgs A = emit_args(a);
+  if (a.ddArena)
+    hipLaunchKernelGGL(k_emit<PRE_MAX_DD>, dim3(a.grid), dim3(EMIT_T), 0, s, A);
+  else
+    hipLaunchKernelGGL(k_emit<PRE_MAX>, dim3(a.grid), dim3(EMIT_T), a.ldsPad, s, A);
+  return hipGetLastError();
+}
+
+// The prefix egress's three launches (length pass, group-base scan, write
+// pass), in stream order.
+hipError_t launch_emit_prefix(hipStream_t s, const EmitLaunch &a, const EmitPrefixLaunch &x) {
+  EmitPreArgs P;
+  P.e = emit_args(a);
+  P.e.out = nullptr;
+  P.pre = x.pre;
+  P.gSum = x.gSum;
+  P.gBase = x.gBase;
+  P.preTotal = x.total;
+  if (a.ddArena)
+    hipLaunchKernelGGL(k_emit_prelen<PRE_MAX_DD>, dim3(a.grid), dim3(EMIT_T), 0, s, P);
+  else
+    hipLaunchKernelGGL(k_emit_prelen<PRE_MAX>, dim3(a.grid), dim3(EMIT_T), 0, s, P);
+  hipLaunchKernelGGL(k_emit_prescan, dim3(1), dim3(PRESCAN_T), 0, s, P);
+  if (a.ddArena)
+    hipLaunchKernelGGL(k_emit_prefix<PRE_MAX_DD>, dim3(a.grid), dim3(EMIT_T), 0, s, P);
+  else
+    hipLaunchKernelGGL(k_emit_prefix<PRE_MAX>, dim3(a.grid), dim3(EMIT_T), 0, s, P);
+  return hipGetLastError();
+}
+
+static EmitArgs emit_args(const EmitLaunch &a) {
   EmitArgs A;
   A.perm = a.perm;
   A.recBase = a.recBase;
@@ -5032,11 +5265,7 @@ hipError_t launch_emit(hipStream_t s, const EmitLaunch &a) {
   A.arenaLen = a.arenaLen;
   A.ddCap = a.ddCap;
   A.gCap = a.gCap;
-  if (a.ddArena)
-    hipLaunchKernelGGL(k_emit<PRE_MAX_DD>, dim3(a.grid), dim3(EMIT_T), 0, s, A);
-  else
-    hipLaunchKernelGGL(k_emit<PRE_MAX>, dim3(a.grid), dim3(EMIT_T), a.ldsPad, s, A);
-  return hipGetLastError();
+  return A;
 }
 
 // The run's first kernel: pulls the page-locked staging buffer (the host's

@@ -260,6 +260,15 @@ hipError_t launch_layer_index(hipStream_t s, const RunDesc *desc, const uint32_t
                               uint32_t ntracks, uint32_t stride, uint32_t *list, uint32_t *before, uint32_t *cnt,
                               uint64_t *zero2 = nullptr);
 hipError_t launch_emit(hipStream_t s, const EmitLaunch &a);
+// Prefix egress (LKF_EGRESS_PREFIX) of the same batch: a.out is unused and
+// a.outArena takes the prefixes; ldsPad does not apply (no payload re-read).
+struct EmitPrefixLaunch {
+  lkf_pre *pre;      // max_out_pkts records
+  uint32_t *gSum;    // a.gCap group sums of round16(pre_len)
+  uint64_t *gBase;   // a.gCap group bases (their exclusive scan)
+  uint64_t *total;   // one word: the batch's prefix arena bytes
+};
+hipError_t launch_emit_prefix(hipStream_t s, const EmitLaunch &a, const EmitPrefixLaunch &x);
 hipError_t launch_dd_decode(hipStream_t s, const RunDesc *desc, const uint32_t *tBegin, const uint32_t *tEnd,
                             const DevTrack *tracks, uint32_t ntracks, DDStruct *structs, DDTrack *ddTracks, DDPkt *out,
                             uint32_t *err, const uint32_t *trackDDTrk, DDTrkState *ddTrk, uint16_t *spill,
