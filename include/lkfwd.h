@@ -46,11 +46,44 @@ enum lkf_codec {
  * Forwarder/DownTrack method named beside it (pkg/sfu/forwarder.go).
  * at_pkt indexes the ExtPacket batch the next lkf_run forwards.  When that
  * batch comes from lkf_ingest* (Buffer.calc on the GPU), its ExtPackets exist
- * only after the ingest, so a caller cannot in general name a position inside
- * it: such callers queue their ops at 0 (the batch start) or beyond the batch
- * (its end), which is what bench.py's ingress steps do
- * (workload.events_at_batch_start); an ExtPacket batch the caller submits
- * itself (lkf_submit*) takes any index. */
+ * only after the ingest, so a caller cannot name a position inside it as an
+ * ExtPacket index.  Such a caller names it by what it does know (lkf_at_kind,
+ * the *_key entry points): the datagram of its raw batch the call preceded,
+ * or the time of the call on the clock of lkf_pkt.arrival_ns.
+ *
+ * Resolution.  A keyed op resolves, on the device and without a host sync, to
+ * an ExtPacket index r of the batch the next lkf_run forwards; from there the
+ * rule above holds (immediately before the first packet of its track with
+ * index >= r, or at batch end).
+ *   LKF_AT_PKT: the key is at_pkt itself (lkf_ctl, lkf_ctl_batch,
+ *     lkf_sender_report, lkf_set_layer_offsets_at are this kind).
+ *   LKF_AT_DATAGRAM, key d: resolved against the last lkf_ingest* before the
+ *     run (n datagrams).  For d < n, r is the number of datagrams with index
+ *     < d that produced an ExtPacket, so a datagram that yields none
+ *     (duplicate, padding-only, unparsable) maps to the next ExtPacket after
+ *     it; for d >= n, r is the end marker 0xffffffff.  On a batch the caller
+ *     submitted itself (lkf_submit*) the datagram list is the ExtPacket list:
+ *     r = d.  A negative key is LKF_EINVAL at the call.
+ *   LKF_AT_ARRIVAL_NS, key T: r is the first ExtPacket of the DownTrack's
+ *     track with arrival_ns >= T (a lower bound over the track's range of the
+ *     batch; arrivals are nondecreasing within a track by the batch
+ *     contract), or the end marker when there is none or the track has no
+ *     packet in the batch.  The same for ingest-fed and submitted batches,
+ *     and independent of which rooms share the engine.
+ * Order within a DownTrack: by key, ops with equal keys in queue order; two
+ * ops with different keys that resolve to the same ExtPacket stay in key
+ * order.  An LKF_AT_PKT op at 0 sorts below every key, one at 0xffffffff
+ * above every key.
+ * Mixing kinds: one DownTrack may not hold, in one run, in-batch ops of two
+ * different kinds (in-batch: every keyed op, and LKF_AT_PKT with 0 < at_pkt
+ * < 0xffffffff; a track's ops count for each of its DownTracks).  lkf_run
+ * then returns LKF_EINVAL before it enqueues anything, names the DownTrack
+ * in lkf_last_error and drops the queued ops; the batch stays submitted and
+ * the next lkf_run forwards it.
+ * Keyed ops may be queued before or after the lkf_ingest* that makes the
+ * batch, up to lkf_run.  An unknown kind, a bad dt, op or track, or a
+ * negative datagram key is LKF_EINVAL at the call. */
+enum lkf_at_kind { LKF_AT_PKT = 0, LKF_AT_DATAGRAM = 1, LKF_AT_ARRIVAL_NS = 2 };
 enum lkf_ctl_op {
   LKF_CTL_MUTE = 1,              /* Mute(a0 muted, a1 isSubscribeMutable)  :377  */
   LKF_CTL_PUBMUTE = 2,           /* PubMute(a0)                            :422  */
@@ -397,6 +430,12 @@ int lkf_sender_report(lkf_engine *e, int32_t track, int32_t layer, uint64_t ntp_
                       uint32_t at_pkt);
 int lkf_set_layer_offsets_at(lkf_engine *e, int32_t track, const uint32_t offsets[9], uint32_t at_pkt);
 int lkf_set_layer_offsets(lkf_engine *e, int32_t track, const uint32_t offsets[9]);
+/* The same with the position as a key (lkf_at_kind above): the cgo binding of
+ * the RTCP reader has the report's receive time, not a packet index.  The
+ * arrival key is searched in the track's own range. */
+int lkf_sender_report_key(lkf_engine *e, int32_t track, int32_t layer, uint64_t ntp_timestamp,
+                          uint32_t rtp_timestamp, int32_t kind, int64_t key);
+int lkf_set_layer_offsets_key(lkf_engine *e, int32_t track, const uint32_t offsets[9], int32_t kind, int64_t key);
 
 /* ---- control ------------------------------------------------------------ */
 /* Queues a Forwarder control op for the next lkf_run (lkf_ctl_op). */
@@ -412,6 +451,20 @@ typedef struct lkf_ctl_event {
   uint32_t pad;
 } lkf_ctl_event;
 int lkf_ctl_batch(lkf_engine *e, const lkf_ctl_event *evs, uint32_t n);
+
+/* The same ops with the position as a key of `kind` (lkf_at_kind, above
+ * lkf_ctl_op): a datagram index of the raw batch or an arrival time. */
+int lkf_ctl_key(lkf_engine *e, int32_t dt, int32_t op, int64_t a0, int64_t a1, int64_t a2, int64_t a3, int32_t kind,
+                int64_t key);
+typedef struct lkf_ctl_event_key {
+  int32_t dt;
+  int32_t op;
+  int64_t a[4];
+  int64_t key;
+  int32_t kind;
+  uint32_t pad;
+} lkf_ctl_event_key; /* 56 B */
+int lkf_ctl_batch_key(lkf_engine *e, const lkf_ctl_event_key *evs, uint32_t n);
 
 /* ---- data --------------------------------------------------------------- */
 /* Host batch: copies descriptors + arena to HBM (WebRTCReceiver.forwardRTP

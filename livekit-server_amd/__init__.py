@@ -262,6 +262,27 @@ class Engine:
     def run(self, stream=None):
         self._chk(self.lib.lkf_run(self.h, stream), "run")
 
+    def ctl_key(self, dt, op, a0=0, a1=0, a2=0, a3=0, kind=abi.LKF_AT_ARRIVAL_NS, key=0):
+        """lkf_ctl_key: a control op whose position in the next run's batch is
+        a datagram index of the raw batch (abi.LKF_AT_DATAGRAM) or an arrival
+        time (abi.LKF_AT_ARRIVAL_NS), resolved on the device."""
+        self._chk(self.api["ctl_key"](self.h, dt, op, a0, a1, a2, a3, kind, key), "ctl_key")
+
+    def ctl_batch_key(self, events):
+        """lkf_ctl_batch_key: a ctypes array of abi.lkf_ctl_event_key, or a
+        sequence of (dt, op, (a0, a1, a2, a3), kind, key)."""
+        if not isinstance(events, C.Array):
+            arr = (abi.lkf_ctl_event_key * max(1, len(events)))()
+            for i, (dt, op, a, kind, key) in enumerate(events):
+                arr[i].dt, arr[i].op, arr[i].kind, arr[i].key = dt, op, kind, key
+                for j in range(4):
+                    arr[i].a[j] = a[j]
+            n = len(events)
+            events = arr
+        else:
+            n = len(events)
+        self._chk(self.api["ctl_batch_key"](self.h, C.cast(events, C.c_void_p), n), "ctl_batch_key")
+
     def ingest(self, raws, n, raw, raw_len):
         """Buffer.calc over a raw batch; the ExtPackets become the next run's batch."""
         rc = self.api["ingest"](self.h, C.cast(raws, C.c_void_p), n, C.cast(raw, C.c_void_p), raw_len)

@@ -404,6 +404,22 @@ class lkfs_event(C.Structure):
     ]
 
 
+LKF_AT_PKT, LKF_AT_DATAGRAM, LKF_AT_ARRIVAL_NS = 0, 1, 2  # lkf_at_kind: how a control op names its position
+LKF_AT_END = 0xFFFFFFFF  # the ExtPacket index that means "at batch end"
+
+
+class lkf_ctl_event_key(C.Structure):  # lkf_ctl_batch_key: an op with its position as a key of `kind`
+    _fields_ = [
+        ("dt", C.c_int32),
+        ("op", C.c_int32),
+        ("a", C.c_int64 * 4),
+        ("key", C.c_int64),
+        ("kind", C.c_int32),
+        ("pad", C.c_uint32),
+    ]
+
+
+assert C.sizeof(lkf_ctl_event_key) == 56, C.sizeof(lkf_ctl_event_key)
 assert C.sizeof(lkf_pkt) == 64, C.sizeof(lkf_pkt)
 assert C.sizeof(lkf_pkt_dd) == 32, C.sizeof(lkf_pkt_dd)
 assert C.sizeof(lkf_track_params) == 64, C.sizeof(lkf_track_params)
@@ -449,6 +465,15 @@ def bind_engine_api(lib, prefix):
     api["ctl"] = _bind(lib, prefix + "ctl", C.c_int,
                        [e, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_uint32])
     api["ctl_batch"] = _bind(lib, prefix + "ctl_batch", C.c_int, [e, C.c_void_p, C.c_uint32])
+    if hasattr(lib, prefix + "ctl_key"):  # engine only: positions by datagram index or arrival time (lkf_at_kind)
+        api["ctl_key"] = _bind(lib, prefix + "ctl_key", C.c_int,
+                               [e, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int32,
+                                C.c_int64])
+        api["ctl_batch_key"] = _bind(lib, prefix + "ctl_batch_key", C.c_int, [e, C.c_void_p, C.c_uint32])
+        api["sender_report_key"] = _bind(lib, prefix + "sender_report_key", C.c_int,
+                                         [e, C.c_int32, C.c_int32, C.c_uint64, C.c_uint32, C.c_int32, C.c_int64])
+        api["set_layer_offsets_key"] = _bind(lib, prefix + "set_layer_offsets_key", C.c_int,
+                                             [e, C.c_int32, P(C.c_uint32), C.c_int32, C.c_int64])
     api["get_stats"] = _bind(lib, prefix + "get_stats", C.c_int, [e, P(lkf_stats)])
     if hasattr(lib, prefix + "last_error"):
         api["last_error"] = _bind(lib, prefix + "last_error", C.c_char_p, [e])

@@ -195,6 +195,10 @@ struct BatchCtx {
   uint32_t prepNT = 0, prepND = 0;
   DevBuf<uint64_t> dITotal;    // that ingest's ExtPacket count (device; k_track_ranges reads it)
   bool used = false;
+  // this context's last run had keyed ops: its resolver (k_ev_resolve, prep
+  // stream) read their keys from the staging buffer, so the host rewrites the
+  // staging only after that run's "prepped"
+  bool keyed = false;
   // SRTP-protected copy of the output (lkf_protect; allocated on first use)
   DevBuf<uint8_t> dProt;
   bool protectedRun = false;
@@ -283,6 +287,16 @@ struct lkf_engine {
   // queued control ops
   using Pend = CtlPend;
   std::vector<Pend> pending;
+  // a keyed op (lkf_at_kind other than LKF_AT_PKT) is queued: the next run
+  // checks the kinds per DownTrack, stages the keys and launches the resolver
+  bool keyedPending = false;
+  // the pending batch is the last ingest's output (datagram keys go through
+  // its scan, dPos) rather than the caller's own ExtPackets (key = index)
+  bool curFromIngest = false;
+  // dPos is one buffer that the next ingest overwrites: recorded after a
+  // resolver that read it, waited for by the next ingest
+  Event scanRead;
+  bool scanReadPending = false;
   // topology epoch: bumped by every change the captured stage graphs depend
   // on (tables, schedule, DD / tracker allocations); a context re-captures
   // its graphs when its epoch is older
@@ -509,6 +523,8 @@ struct lkf_engine {
   struct TrackOp {
     uint32_t track, at;
     uint32_t offs[9];
+    int32_t kind;  // lkf_at_kind; key: the position of a keyed op
+    int64_t key;
   };
   std::vector<TrackOp> trkOps;
   DevBuf<uint32_t> dDTOffs;  // per DownTrack kDTOffsWords: the offsets its Forwarder reads
@@ -1000,6 +1016,7 @@ lkf_engine *lkf_create(int hip_device, const lkf_cfg *cfg) {
   }
   for (auto &r : e->ring)
     for (auto &ev : r) A(ev.create(true));
+  A(e->scanRead.create(false));
   e->maxStreams = c.max_streams ? c.max_streams : 3 * c.max_tracks;
   A(e->dStreams.alloc(e->maxStreams));
   A(e->dStreamHot.alloc(e->maxStreams));
@@ -1112,15 +1129,30 @@ int32_t lkf_add_track(lkf_engine *e, const lkf_track_params *p) {
   return h;
 }
 
-int lkf_set_layer_offsets_at(lkf_engine *e, int32_t track, const uint32_t offsets[9], uint32_t at_pkt) {
+// an op's position: (LKF_AT_PKT, at_pkt) or a key of another kind
+static bool at_key_valid(int32_t kind, int64_t key) {
+  if (kind == LKF_AT_PKT) return key >= 0 && key <= int64_t(0xffffffffu);
+  if (kind == LKF_AT_DATAGRAM) return key >= 0;
+  return kind == LKF_AT_ARRIVAL_NS;
+}
+
+int lkf_set_layer_offsets_key(lkf_engine *e, int32_t track, const uint32_t offsets[9], int32_t kind, int64_t key) {
   if (!e || !offsets || track < 0 || track >= int32_t(e->tracks.size())) return LKF_EINVAL;
+  if (!at_key_valid(kind, key)) return LKF_EINVAL;
   lkf_engine::TrackOp op;
   op.track = uint32_t(track);
-  op.at = at_pkt;
+  op.at = kind == LKF_AT_PKT ? uint32_t(key) : 0u;
+  op.kind = kind;
+  op.key = key;
   std::memcpy(op.offs, offsets, sizeof(op.offs));
   std::memcpy(e->trkSR[size_t(track)].offs, offsets, sizeof(op.offs));
   e->trkOps.push_back(op);
+  if (kind != LKF_AT_PKT) e->keyedPending = true;
   return LKF_OK;
+}
+
+int lkf_set_layer_offsets_at(lkf_engine *e, int32_t track, const uint32_t offsets[9], uint32_t at_pkt) {
+  return lkf_set_layer_offsets_key(e, track, offsets, LKF_AT_PKT, int64_t(at_pkt));
 }
 
 int lkf_set_layer_offsets(lkf_engine *e, int32_t track, const uint32_t offsets[9]) {
@@ -1154,9 +1186,10 @@ static bool sr_layer_offset(lkf_engine::TrackSR &s, uint32_t clockRate, int ref,
 }
 
 // SetRTCPSenderReportData (streamtrackermanager.go:603-627)
-int lkf_sender_report(lkf_engine *e, int32_t track, int32_t layer, uint64_t ntp_timestamp, uint32_t rtp_timestamp,
-                      uint32_t at_pkt) {
+int lkf_sender_report_key(lkf_engine *e, int32_t track, int32_t layer, uint64_t ntp_timestamp, uint32_t rtp_timestamp,
+                          int32_t kind, int64_t key) {
   if (!e || track < 0 || track >= int32_t(e->tracks.size())) return LKF_EINVAL;
+  if (!at_key_valid(kind, key)) return LKF_EINVAL;
   if (layer < 0 || layer > 2) return LKF_OK;  // (invalid layer: ignored, as the reference)
   lkf_engine::TrackSR &s = e->trkSR[size_t(track)];
   s.ntp[layer] = ntp_timestamp;
@@ -1171,10 +1204,18 @@ int lkf_sender_report(lkf_engine *e, int32_t track, int32_t layer, uint64_t ntp_
   if (!changed) return LKF_OK;
   lkf_engine::TrackOp op;
   op.track = uint32_t(track);
-  op.at = at_pkt;
+  op.at = kind == LKF_AT_PKT ? uint32_t(key) : 0u;
+  op.kind = kind;
+  op.key = key;
   std::memcpy(op.offs, s.offs, sizeof(op.offs));
   e->trkOps.push_back(op);
+  if (kind != LKF_AT_PKT) e->keyedPending = true;
   return LKF_OK;
+}
+
+int lkf_sender_report(lkf_engine *e, int32_t track, int32_t layer, uint64_t ntp_timestamp, uint32_t rtp_timestamp,
+                      uint32_t at_pkt) {
+  return lkf_sender_report_key(e, track, layer, ntp_timestamp, rtp_timestamp, LKF_AT_PKT, int64_t(at_pkt));
 }
 
 int32_t lkf_add_downtrack(lkf_engine *e, const lkf_downtrack_params *p) {
@@ -1254,12 +1295,60 @@ int lkf_remove_track(lkf_engine *e, int32_t track) {
   return upload_done(e);
 }
 
+static_assert(sizeof(lkf_ctl_event_key) == 56, "lkf_ctl_event_key is 56 B");
+
+int lkf_ctl_key(lkf_engine *e, int32_t dt, int32_t op, int64_t a0, int64_t a1, int64_t a2, int64_t a3, int32_t kind,
+                int64_t key) {
+  if (!e || dt < 0 || dt >= int32_t(e->dtp.size())) return LKF_EINVAL;
+  if (op < LKF_CTL_MUTE || op > LKF_CTL_PLAYOUT_ACKED) return LKF_EINVAL;
+  if (!at_key_valid(kind, key)) return LKF_EINVAL;
+  lkf_engine::Pend p;
+  p.dt = uint32_t(dt);
+  std::memset(&p.ev, 0, sizeof(p.ev));
+  p.ev.at = kind == LKF_AT_PKT ? uint32_t(key) : 0u;
+  p.ev.op = op;
+  p.ev.a[0] = a0;
+  p.ev.a[1] = a1;
+  p.ev.a[2] = a2;
+  p.ev.a[3] = a3;
+  p.key = key;
+  p.kind = kind;
+  e->pending.push_back(p);
+  if (kind != LKF_AT_PKT) e->keyedPending = true;
+  return LKF_OK;
+}
+
+int lkf_ctl_batch_key(lkf_engine *e, const lkf_ctl_event_key *evs, uint32_t n) {
+  if (!e || (n && !evs)) return LKF_EINVAL;
+  const int32_t nd = int32_t(e->dtp.size());
+  for (uint32_t i = 0; i < n; i++)
+    if (evs[i].dt < 0 || evs[i].dt >= nd || evs[i].op < LKF_CTL_MUTE || evs[i].op > LKF_CTL_PLAYOUT_ACKED ||
+        !at_key_valid(evs[i].kind, evs[i].key))
+      return LKF_EINVAL;
+  e->pending.reserve(e->pending.size() + n);
+  for (uint32_t i = 0; i < n; i++) {
+    lkf_engine::Pend p;
+    p.dt = uint32_t(evs[i].dt);
+    std::memset(&p.ev, 0, sizeof(p.ev));
+    p.ev.at = evs[i].kind == LKF_AT_PKT ? uint32_t(evs[i].key) : 0u;
+    p.ev.op = evs[i].op;
+    for (int j = 0; j < 4; j++) p.ev.a[j] = evs[i].a[j];
+    p.key = evs[i].key;
+    p.kind = evs[i].kind;
+    e->pending.push_back(p);
+    if (p.kind != LKF_AT_PKT) e->keyedPending = true;
+  }
+  return LKF_OK;
+}
+
 int lkf_ctl(lkf_engine *e, int32_t dt, int32_t op, int64_t a0, int64_t a1, int64_t a2, int64_t a3, uint32_t at_pkt) {
   if (!e || dt < 0 || dt >= int32_t(e->dtp.size())) return LKF_EINVAL;
   if (op < LKF_CTL_MUTE || op > LKF_CTL_PLAYOUT_ACKED) return LKF_EINVAL;
   lkf_engine::Pend p;
   p.dt = uint32_t(dt);
   std::memset(&p.ev, 0, sizeof(p.ev));
+  p.key = 0;
+  p.kind = LKF_AT_PKT;
   p.ev.at = at_pkt;
   p.ev.op = op;
   p.ev.a[0] = a0;
@@ -1281,6 +1370,8 @@ int lkf_ctl_batch(lkf_engine *e, const lkf_ctl_event *evs, uint32_t n) {
     lkf_engine::Pend p;
     p.dt = uint32_t(evs[i].dt);
     std::memset(&p.ev, 0, sizeof(p.ev));
+    p.key = 0;
+    p.kind = LKF_AT_PKT;
     p.ev.at = evs[i].at_pkt;
     p.ev.op = evs[i].op;
     for (int j = 0; j < 4; j++) p.ev.a[j] = evs[i].a[j];
@@ -1306,6 +1397,7 @@ int lkf_submit(lkf_engine *e, const lkf_pkt *pkts, uint32_t n, const uint8_t *ar
   e->curDD = nullptr;
   e->curOwned = true;
   e->curDDOwned = true;
+  e->curFromIngest = false;
   e->ingestStarted = false;
   e->curArenaLen = arena_len;
   e->haveBatch = true;
@@ -1323,6 +1415,7 @@ int lkf_submit_device(lkf_engine *e, const lkf_pkt *d_pkts, uint32_t n, const ui
   e->curDD = nullptr;
   e->curOwned = false;
   e->curDDOwned = true;
+  e->curFromIngest = false;
   e->ingestStarted = false;
   e->curArenaLen = arena_len;
   e->haveBatch = true;
@@ -1518,6 +1611,7 @@ int lkf_run(lkf_engine *e, void *stream) {
     e->curN = 0;
     e->curNDev = nullptr;
     e->curArenaLen = 0;
+    e->curFromIngest = false;
   }
   // The caller's stream orders the batch's inputs; the stages themselves run
   // on the engine's decide/emit streams (completion: lkf_sync).
@@ -1532,11 +1626,61 @@ int lkf_run(lkf_engine *e, void *stream) {
   // decide(n) ends.
   hipStream_t ps = e->prepS;
   hipStream_t s = e->decS;
-  HIPCHK(hipEventRecord(e->inEv, us), "event");
-  HIPCHK(hipStreamWaitEvent(ps, e->inEv, 0), "wait caller stream");
   const uint32_t nt = uint32_t(e->tracks.size());
   const uint32_t nd = uint32_t(e->dtp.size());
   const uint32_t nl = uint32_t(e->sched.size());
+  if (!e->trkOps.empty()) {  // a track's layer-offset changes: one op per active DownTrack of it
+    auto trk_key = [](const lkf_engine::TrackOp &o) {
+      lkf_engine::Pend q;
+      q.ev.at = o.at;
+      q.key = o.key;
+      q.kind = o.kind;
+      return ctl_sort_key(q);
+    };
+    std::stable_sort(e->trkOps.begin(), e->trkOps.end(),
+                     [&](const lkf_engine::TrackOp &a, const lkf_engine::TrackOp &b) {
+                       return a.track != b.track ? a.track < b.track : trk_key(a) < trk_key(b);
+                     });
+    std::vector<std::vector<uint32_t>> byT(nt);
+    for (uint32_t d = 0; d < nd; d++)
+      if (e->active[d]) byT[e->dtp[d].track].push_back(d);
+    for (const auto &op : e->trkOps) {
+      lkf_engine::Pend q;
+      std::memset(&q.ev, 0, sizeof(q.ev));
+      q.ev.at = op.at;
+      q.key = op.key;
+      q.kind = op.kind;
+      q.ev.op = kOpLayerOffsets;
+      for (int k = 0; k < 4; k++) q.ev.a[k] = int64_t(uint64_t(op.offs[2 * k]) | (uint64_t(op.offs[2 * k + 1]) << 32));
+      q.ev.pad = int64_t(op.offs[8]);
+      for (uint32_t d : byT[op.track]) {
+        q.dt = d;
+        e->pending.push_back(q);
+      }
+    }
+  }
+  // Keyed ops: a DownTrack's in-batch ops must all be of one kind (its
+  // positions resolve in one space, and its lane stays sorted by at_pkt).
+  // Nothing of this run is enqueued yet: the ops are dropped, the batch stays.
+  const bool keyed = e->keyedPending;
+  e->keyedPending = false;
+  if (keyed) {
+    const int64_t bad = e->csr.mixed(e->pending.data(), e->pending.size(), e->dtLane.data(), nd);
+    if (bad >= 0) {
+      char buf[160];
+      snprintf(buf, sizeof(buf), "DownTrack %lld: control ops of two position kinds (lkf_at_kind) in one run",
+               (long long)bad);
+      e->err = buf;
+      e->pending.clear();
+      e->trkOps.clear();
+      return LKF_EINVAL;
+    }
+  }
+  for (const auto &op : e->trkOps)
+    std::memcpy(e->tracks[op.track].layer_offsets, op.offs, sizeof(op.offs));  // as of the end of this run
+  e->trkOps.clear();
+  HIPCHK(hipEventRecord(e->inEv, us), "event");
+  HIPCHK(hipStreamWaitEvent(ps, e->inEv, 0), "wait caller stream");
   // this context's previous batch (run n-2) must have finished its emit stage
   if (x.used) HIPCHK(hipStreamWaitEvent(ps, x.emitted, 0), "wait emit");
   if (x.fromIngest && e->haveBatch) HIPCHK(hipStreamWaitEvent(ps, x.ingested, 0), "wait ingest");
@@ -1547,37 +1691,18 @@ int lkf_run(lkf_engine *e, void *stream) {
   x.prepByIngest = false;
 
   // Per-lane control-op CSR (stable: queue order within a lane, then by
-  // at_pkt).  The host sorts only the ops: an LSD radix sort on the lane
-  // (8-bit digits, stable), then a stable insertion by at_pkt inside a lane
-  // with several ops; it stages the run's RunDesc, the sorted ops and their
-  // lanes in this context's page-locked cached buffer.  The prep stage's
+  // key: at_pkt, or a keyed op's datagram index / arrival time).  The host
+  // sorts only the ops: an LSD radix sort on the lane (8-bit digits, stable),
+  // then a stable insertion by key inside a lane with several ops; it stages
+  // the run's RunDesc, the sorted ops, their lanes and — in a run with keyed
+  // ops — their keys in this context's page-locked cached buffer.  The prep stage's
   // first kernel pulls them and k_ev_offsets derives the dense per-lane
   // offsets on the GPU (no host pass over all lanes).
   const auto tp1 = clk::now();
   if (x.used) HIPCHK(hipEventSynchronize(x.pulled), "stage wait");  // run n-3's pull of this staging is done
+  if (x.used && x.keyed) HIPCHK(hipEventSynchronize(x.prepped), "stage wait (keys)");  // ... and its resolver
+  x.keyed = keyed;
   const auto tp2 = clk::now();
-  if (!e->trkOps.empty()) {  // a track's layer-offset changes: one op per active DownTrack of it
-    std::stable_sort(e->trkOps.begin(), e->trkOps.end(), [](const lkf_engine::TrackOp &a, const lkf_engine::TrackOp &b) {
-      return a.track != b.track ? a.track < b.track : a.at < b.at;
-    });
-    std::vector<std::vector<uint32_t>> byT(nt);
-    for (uint32_t d = 0; d < nd; d++)
-      if (e->active[d]) byT[e->dtp[d].track].push_back(d);
-    for (const auto &op : e->trkOps) {
-      lkf_engine::Pend q;
-      std::memset(&q.ev, 0, sizeof(q.ev));
-      q.ev.at = op.at;
-      q.ev.op = kOpLayerOffsets;
-      for (int k = 0; k < 4; k++) q.ev.a[k] = int64_t(uint64_t(op.offs[2 * k]) | (uint64_t(op.offs[2 * k + 1]) << 32));
-      q.ev.pad = int64_t(op.offs[8]);
-      for (uint32_t d : byT[op.track]) {
-        q.dt = d;
-        e->pending.push_back(q);
-      }
-      std::memcpy(e->tracks[op.track].layer_offsets, op.offs, sizeof(op.offs));  // as of the end of this run
-    }
-    e->trkOps.clear();
-  }
   const size_t nev = e->csr.sort(e->pending.data(), e->pending.size(), e->dtLane.data(), nl);  // (ctl_csr.h)
   if (nev > x.stageCap || !x.stage.host) {  // (graphs captured with the old staging are re-captured)
     // the queued pull of this context's previous run may still read the old
@@ -1587,8 +1712,9 @@ int lkf_run(lkf_engine *e, void *stream) {
     }
     x.stage.reset();
     x.stageCap = 0;  // (set once the allocation has succeeded: a failed one is retried by the next run)
-    const uint32_t cap = uint32_t(std::max<size_t>(2 * nev, 4096));
-    HIPCHK(x.stage.alloc(sizeof(RunDesc) + size_t(cap) * (sizeof(DevEvent) + 4)), "alloc stage");
+    // (a multiple of 4 ops: the keys behind the lane list stay 16-B aligned)
+    const uint32_t cap = uint32_t(std::max<size_t>(2 * nev, 4096) + 3) & ~3u;
+    HIPCHK(x.stage.alloc(sizeof(RunDesc) + size_t(cap) * (sizeof(DevEvent) + 4 + sizeof(DevKey))), "alloc stage");
     x.stageCap = cap;
     x.gPrepEpoch[0] = x.gPrepEpoch[1] = 0;
     x.gCtlEpoch = 0;
@@ -1596,7 +1722,10 @@ int lkf_run(lkf_engine *e, void *stream) {
   DevEvent *evs = reinterpret_cast<DevEvent *>(x.stage.host + sizeof(RunDesc));
   uint32_t *lanes =
       reinterpret_cast<uint32_t *>(x.stage.host + sizeof(RunDesc) + size_t(x.stageCap) * sizeof(DevEvent));
-  e->csr.emit(e->pending.data(), evs, lanes);
+  // (the keys of a run with keyed ops: behind the lane list, read in place by k_ev_resolve)
+  const size_t keyOff = sizeof(RunDesc) + size_t(x.stageCap) * (sizeof(DevEvent) + 4);
+  e->csr.emit(e->pending.data(), evs, lanes, keyed ? reinterpret_cast<DevKey *>(x.stage.host + keyOff) : nullptr,
+              e->dtp.data());
   e->pending.clear();
   {
     RunDesc &h = *reinterpret_cast<RunDesc *>(x.stage.host);
@@ -1720,6 +1849,21 @@ int lkf_run(lkf_engine *e, void *stream) {
   } else {
     const int rc = prep();
     if (rc) return rc;
+  }
+  if (keyed && nev) {
+    // Keyed ops -> ExtPacket indices (DevEvent.at), after the pull and the
+    // track ranges, before the decide stage reads the ops.  Launched directly
+    // and only for a run with keyed ops: a run without them enqueues what it
+    // always did.
+    const bool scan = e->curFromIngest && e->curNDev;  // (an empty ingest: every datagram key is past it)
+    HIPCHK(launch_ev_resolve(ps, reinterpret_cast<const DevKey *>(x.stage.dev + keyOff), x.dEvents, x.dEvLane,
+                             uint32_t(nev), e->curPkts, x.dTBegin, x.dTEnd, nt, scan ? e->dPos.get() : nullptr,
+                             e->curFromIngest ? e->lastIngestN : 0xffffffffu),
+           "key resolve");
+    if (scan) {
+      HIPCHK(hipEventRecord(e->scanRead, ps), "event");
+      e->scanReadPending = true;
+    }
   }
   HIPCHK(hipEventRecord(x.prepped, ps), "event");
   if (e->knobs.debugDD && e->ddAlloc) {  // LKF_DEBUG_DD=1 (diagnostic): the context's DD cursor after its prep
@@ -3677,6 +3821,9 @@ static int ingest_common(lkf_engine *e, BatchCtx &x, const lkf_raw_pkt *dRaws, u
   e->sidePending[par] = false;
   if (e->bktPending[par]) HIPCHK(hipStreamWaitEvent(s, e->bktDone[par], 0), "wait bucket copies");
   e->bktPending[par] = false;
+  // the previous run's resolver (datagram keys) still reads the scan this ingest overwrites
+  if (e->scanReadPending) HIPCHK(hipStreamWaitEvent(s, e->scanRead, 0), "wait key resolve");
+  e->scanReadPending = false;
   IngestLaunch a;
   a.raws = dRaws;
   a.n = n;
@@ -3781,6 +3928,7 @@ static int ingest_common(lkf_engine *e, BatchCtx &x, const lkf_raw_pkt *dRaws, u
   // (an empty ingest launches nothing, so dITotal still holds an older
   // ingest's count: the batch is empty, with no device-side count)
   e->curNDev = n ? x.dITotal : nullptr;
+  e->curFromIngest = true;
   e->curDD = a.outDD;  // the ExtPackets' descriptors (nullptr: no DD stream)
   e->curOwned = true;
   e->curDDOwned = true;

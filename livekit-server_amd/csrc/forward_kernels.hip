@@ -101,6 +101,7 @@ enum ChkSite : u32 {
   CK_EMIT_GROUP,      // emit: group index entry < its capacity
   CK_PAD_DT,          // padding: DownTrack handle < max_downtracks
   CK_PAD_SEQ,         // padding: sequencer slot < seq_size
+  CK_EV_ORDER,        // key resolve: a lane's resolved at_pkt >= the op before it (idx = op, cap = that op's at)
 };
 
 // ---------------------------------------------------------------------------
@@ -4743,6 +4744,80 @@ __global__ void k_ev_offsets(const u32 *__restrict__ laneOf, const RunDesc *__re
       hi = mid;
   }
   off[l] = lo;
+}
+
+// k_ev_resolve: keyed control ops (lkf_ctl_key*) -> ExtPacket indices.  One
+// thread per staged op of a run that has keyed ops: the op's key (DevKey,
+// read in place from the run's page-locked staging) becomes DevEvent.at, in
+// the ExtPacket space the decide stage reads.
+//   LKF_AT_DATAGRAM d: pos[d], the ingest's exclusive scan of "this datagram
+//     produced an ExtPacket" (k_ing_out writes datagram d's ExtPacket there);
+//     past the ingest's nRaw datagrams the end marker.  Without a scan (the
+//     caller's own ExtPacket batch) the datagram list is the batch: d itself.
+//   LKF_AT_ARRIVAL_NS T: lower bound of T over arrival_ns in the track's
+//     [tBegin, tEnd) (nondecreasing within a track); none -> the end marker.
+//   LKF_AT_PKT: at as queued.
+// Both are monotone in the key and the host sorted each lane by key, so a
+// lane's at values come out nondecreasing (checked builds test it).
+struct EvResolve {
+  const DevKey *keys;
+  const lkf_pkt *pkts;
+  const u32 *tBegin, *tEnd;
+  const u64 *pos;
+  u32 ntracks, nRaw;
+};
+__device__ __forceinline__ u32 ev_resolve_one(const EvResolve &R, const DevKey k, u32 at) {
+  constexpr u32 kEnd = 0xffffffffu;
+  if (k.kind == LKF_AT_DATAGRAM) {
+    if (k.key < 0 || u64(k.key) >= u64(R.nRaw)) return kEnd;
+    return R.pos ? u32(R.pos[k.key]) : u32(k.key);
+  }
+  if (k.kind == LKF_AT_ARRIVAL_NS) {
+    if (k.track >= R.ntracks) return kEnd;
+    const u32 b = R.tBegin[k.track], e = R.tEnd[k.track];
+    u32 lo = b, hi = e;  // lower_bound(arrival_ns, T) over [b, e)
+    while (lo < hi) {
+      const u32 mid = lo + ((hi - lo) >> 1);
+      if (R.pkts[mid].arrival_ns < k.key)
+        lo = mid + 1;
+      else
+        hi = mid;
+    }
+    return lo < e ? lo : kEnd;
+  }
+  return at;
+}
+__global__ void __launch_bounds__(256) k_ev_resolve(EvResolve R, DevEvent *__restrict__ evs,
+                                                    const u32 *__restrict__ laneOf, u32 nev) {
+  const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nev) return;
+  const u32 at = ev_resolve_one(R, R.keys[i], evs[i].at);
+#if LKF_CHECKED
+  // (the op before it is resolved again here rather than read back: its own
+  // thread may not have stored yet; an LKF_AT_PKT op keeps the at it has)
+  if (i && laneOf[i - 1] == laneOf[i]) {
+    const DevKey kp = R.keys[i - 1];
+    const u32 prev = ev_resolve_one(R, kp, kp.kind == LKF_AT_PKT ? evs[i - 1].at : 0u);
+    CHK(prev <= at, CK_EV_ORDER, i, prev);
+  }
+#endif
+  if (R.keys[i].kind != LKF_AT_PKT) evs[i].at = at;
+}
+
+hipError_t launch_ev_resolve(hipStream_t s, const DevKey *keys, DevEvent *evs, const u32 *laneOf, u32 nev,
+                             const lkf_pkt *pkts, const u32 *tBegin, const u32 *tEnd, u32 ntracks, const u64 *pos,
+                             u32 nRaw) {
+  if (!nev) return hipSuccess;
+  EvResolve R;
+  R.keys = keys;
+  R.pkts = pkts;
+  R.tBegin = tBegin;
+  R.tEnd = tEnd;
+  R.pos = pos;
+  R.ntracks = ntracks;
+  R.nRaw = nRaw;
+  hipLaunchKernelGGL(k_ev_resolve, dim3((nev + 255) / 256), dim3(256), 0, s, R, evs, laneOf, nev);
+  return hipGetLastError();
 }
 
 hipError_t launch_ev_offsets(hipStream_t s, const u32 *laneOf, const RunDesc *desc, u32 nl, u32 *off) {

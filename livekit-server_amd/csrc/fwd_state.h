@@ -514,4 +514,15 @@ struct DevEvent {  // one queued lkf_ctl op (48 B)
   int64_t pad;
 };
 
+// How a keyed op (lkf_ctl_key*) names its position: staged beside the sorted
+// ops of a run that has keyed ops, behind the lane list, and resolved into
+// DevEvent.at on the device (k_ev_resolve).  kind is an lkf_at_kind;
+// LKF_AT_PKT entries keep the at they were queued with.
+struct DevKey {  // 16 B
+  int64_t key;
+  int32_t kind;
+  uint32_t track;  // the DownTrack's track (the arrival key's search range)
+};
+static_assert(sizeof(DevKey) == 16, "DevKey is 16 B");
+
 }  // namespace lkf

@@ -280,6 +280,12 @@ hipError_t launch_h2d(hipStream_t s, const uint8_t *stage, RunDesc *dDesc, DevEv
 hipError_t launch_stats_reduce(hipStream_t s, uint64_t *stats);
 // dense per-lane op offsets from the lane-sorted op list: off[l] = first op with lane >= l
 hipError_t launch_ev_offsets(hipStream_t s, const uint32_t *laneOf, const RunDesc *desc, uint32_t nl, uint32_t *off);
+// keyed control ops -> DevEvent.at (k_ev_resolve): keys beside the nev sorted
+// ops; pos / nRaw the last ingest's scan and datagram count (pos nullptr: a
+// datagram key below nRaw is the ExtPacket index itself)
+hipError_t launch_ev_resolve(hipStream_t s, const DevKey *keys, DevEvent *evs, const uint32_t *laneOf, uint32_t nev,
+                             const lkf_pkt *pkts, const uint32_t *tBegin, const uint32_t *tEnd, uint32_t ntracks,
+                             const uint64_t *pos, uint32_t nRaw);
 hipError_t launch_accumulate(hipStream_t s, const uint64_t *stats, const uint64_t *tot, uint64_t *cum,
                              const uint32_t *err, uint32_t *sticky);
 hipError_t launch_err_fold(hipStream_t s, const uint32_t *err, uint32_t *sticky, uint32_t shift);

@@ -127,12 +127,71 @@ def events_at_batch_start(trace):
     there the index would land on another track's packet, and where it lands
     would depend on which rooms share the engine, so engines holding
     different room sets (bench.py's sharded parity gate and CPU baseline)
-    would not apply the op at the same point."""
+    would not apply the op at the same point.
+
+    New callers use the keyed forms below instead (events_keyed,
+    queue_events_keyed): an arrival-time key names the scripted position
+    itself, inside the batch, and does not depend on the room set either.
+    This function stays for bench.py's ingress steps."""
     for b in range(trace.nbatches):
         ev, n = events_ptr(trace, b)
         if n:
             for e in (abi.lkfs_event * n).from_address(C.cast(ev, C.c_void_p).value):
                 e.at_pkt = 0
+
+
+INT64_MIN, INT64_MAX = -(1 << 63), (1 << 63) - 1
+
+
+def events_keyed(trace, b, kind):
+    """Batch b's scripted control ops as keyed ops (abi.lkf_ctl_event_key
+    array, count): the position named by a datagram index of the raw batch
+    (abi.LKF_AT_DATAGRAM) or by an arrival time (abi.LKF_AT_ARRIVAL_NS)
+    instead of an ExtPacket index.
+
+    For the traces whose raw batch is the packet list one to one (configs 1-3;
+    not config 5), so that the scripted at_pkt is the datagram index.  The
+    arrival key is that datagram's arrival_ns when the datagram belongs to the
+    DownTrack's track; a position before the track's datagrams becomes
+    INT64_MIN and one after them (or any position when the track has none)
+    INT64_MAX.  The ops come out stably sorted by at_pkt, so that ops whose
+    arrival keys tie keep the order their scripted positions gave them."""
+    evs = sorted(trace.events(b), key=lambda e: e.at_pkt)
+    out = (abi.lkf_ctl_event_key * max(1, len(evs)))()
+    if kind == abi.LKF_AT_ARRIVAL_NS and evs:
+        rp, n, _, _ = trace.batch_raw(b)
+        first, last = {}, {}
+        for i in range(n):
+            t = trace.streams[rp[i].stream].track
+            first.setdefault(t, i)
+            last[t] = i
+    for i, e in enumerate(evs):
+        o = out[i]
+        o.dt, o.op, o.kind = e.dt, e.op, kind
+        for j in range(4):
+            o.a[j] = e.a[j]
+        if kind == abi.LKF_AT_DATAGRAM:
+            o.key = e.at_pkt
+        elif kind == abi.LKF_AT_ARRIVAL_NS:
+            t = trace.downtracks[e.dt].track
+            if t not in first or e.at_pkt > last[t]:
+                o.key = INT64_MAX
+            elif e.at_pkt < first[t]:
+                o.key = INT64_MIN
+            else:
+                o.key = rp[e.at_pkt].arrival_ns
+        else:
+            raise ValueError("events_keyed: kind %r" % (kind,))
+    return out, len(evs)
+
+
+def queue_events_keyed(api, eng, trace, b, kind):
+    """Queues batch b's scripted control ops as keyed ops (events_keyed)."""
+    ev, n = events_keyed(trace, b, kind)
+    if n:
+        rc = api["ctl_batch_key"](eng, C.cast(ev, C.c_void_p), n)
+        if rc != 0:
+            raise RuntimeError("ctl_batch_key failed rc=%d" % rc)
 
 
 def queue_events(api, eng, trace, b):
