@@ -214,8 +214,10 @@ struct BatchCtx {
   // (two prep graphs: [1] with the ingest's prep fused in — k_batch_init /
   // k_track_ranges left out — [0] without; a context alternating between an
   // ingest-prepared batch and another replays both instead of re-capturing)
-  GraphExec gPrep[2], gScan, gCtl;
-  uint64_t gPrepEpoch[2] = {0, 0}, gScanEpoch = 0, gCtlEpoch = 0;
+  StageGraph gPrep[2], gScan, gCtl;
+  // the staging or the op buffers moved: the graphs that hold their addresses
+  // are re-captured by the next run (the scan tail reads neither)
+  void forget_pull_graphs() { gPrep[0].epoch = gPrep[1].epoch = gCtl.epoch = 0; }
 };
 
 }  // namespace
@@ -1587,123 +1589,105 @@ static int rebuild_twcc(lkf_engine *e) {
   return upload_done(e);
 }
 
-int lkf_run(lkf_engine *e, void *stream) {
-  if (!e) return LKF_EINVAL;
-  HIPCHK(hipSetDevice(e->dev), "hipSetDevice");
-  {
-    int rc = flush_topology(e);
-    if (rc) return rc;
-  }
-  if (e->schedDirty) {
-    int rc = rebuild_sched(e);
-    if (rc) return rc;
-  }
-  if (e->twccDirty) {
-    int rc = rebuild_twcc(e);
-    if (rc) return rc;
-  }
-  const int ci = int(e->nRuns % lkf_engine::kCtx);
-  BatchCtx &x = e->ctx[ci];
-  if (!e->haveBatch) {  // control-only run: an empty batch applies queued ops
-    e->curPkts = x.dPktsOwn;
-    e->curArena = x.dArenaOwn;
-    e->curOwned = e->curDDOwned = true;
-    e->curN = 0;
-    e->curNDev = nullptr;
-    e->curArenaLen = 0;
-    e->curFromIngest = false;
-  }
-  // The caller's stream orders the batch's inputs; the stages themselves run
-  // on the engine's decide/emit streams (completion: lkf_sync).
-  using clk = std::chrono::steady_clock;
-  const auto tp0 = clk::now();
-  auto ms_since = [](clk::time_point a) { return std::chrono::duration<double, std::milli>(clk::now() - a).count(); };
-  hipStream_t us = stream ? reinterpret_cast<hipStream_t>(stream) : e->own;
-  e->cur = us;
-  // prep stream: control-op CSR, per-batch init, track ranges, slot scan,
-  // layer index (and, before lkf_run, the ingest).  It runs ahead: batch n+1
-  // is prepared while batch n decides, so decide(n+1) starts as soon as
-  // decide(n) ends.
-  hipStream_t ps = e->prepS;
-  hipStream_t s = e->decS;
-  const uint32_t nt = uint32_t(e->tracks.size());
-  const uint32_t nd = uint32_t(e->dtp.size());
-  const uint32_t nl = uint32_t(e->sched.size());
-  if (!e->trkOps.empty()) {  // a track's layer-offset changes: one op per active DownTrack of it
-    auto trk_key = [](const lkf_engine::TrackOp &o) {
-      lkf_engine::Pend q;
-      q.ev.at = o.at;
-      q.key = o.key;
-      q.kind = o.kind;
-      return ctl_sort_key(q);
-    };
-    std::stable_sort(e->trkOps.begin(), e->trkOps.end(),
-                     [&](const lkf_engine::TrackOp &a, const lkf_engine::TrackOp &b) {
-                       return a.track != b.track ? a.track < b.track : trk_key(a) < trk_key(b);
-                     });
-    std::vector<std::vector<uint32_t>> byT(nt);
-    for (uint32_t d = 0; d < nd; d++)
-      if (e->active[d]) byT[e->dtp[d].track].push_back(d);
-    for (const auto &op : e->trkOps) {
-      lkf_engine::Pend q;
-      std::memset(&q.ev, 0, sizeof(q.ev));
-      q.ev.at = op.at;
-      q.key = op.key;
-      q.kind = op.kind;
-      q.ev.op = kOpLayerOffsets;
-      for (int k = 0; k < 4; k++) q.ev.a[k] = int64_t(uint64_t(op.offs[2 * k]) | (uint64_t(op.offs[2 * k + 1]) << 32));
-      q.ev.pad = int64_t(op.offs[8]);
-      for (uint32_t d : byT[op.track]) {
-        q.dt = d;
-        e->pending.push_back(q);
-      }
+// ---- lkf_run: its stages in the order they run -----------------------------
+using clk = std::chrono::steady_clock;
+static double ms_between(clk::time_point a, clk::time_point b) {
+  return std::chrono::duration<double, std::milli>(b - a).count();
+}
+static double ms_since(clk::time_point a) { return ms_between(a, clk::now()); }
+
+// What the stages of one lkf_run share.
+struct RunCtx {
+  int ci;               // the batch context's index
+  uint32_t nt, nd, nl;  // tracks, DownTracks, schedule lanes
+  Event *rg;            // this run's timing events
+  bool keyed;           // the run has keyed control ops
+  bool prepDone;        // an ingest's k_ing_out prepared the batch (no k_batch_init / k_track_ranges)
+  bool ingestFed;       // the batch is an ingest's output (emit's residency)
+  size_t nev;           // control ops staged
+  clk::time_point tp0, tp1, tp2, tp25, tp3;  // LKF_HOST_PROF sections
+};
+
+// A track's layer-offset changes: one op per active DownTrack of it.
+static void expand_track_ops(lkf_engine *e, const RunCtx &r) {
+  if (e->trkOps.empty()) return;
+  auto trk_key = [](const lkf_engine::TrackOp &o) {
+    lkf_engine::Pend q;
+    q.ev.at = o.at;
+    q.key = o.key;
+    q.kind = o.kind;
+    return ctl_sort_key(q);
+  };
+  std::stable_sort(e->trkOps.begin(), e->trkOps.end(),
+                   [&](const lkf_engine::TrackOp &a, const lkf_engine::TrackOp &b) {
+                     return a.track != b.track ? a.track < b.track : trk_key(a) < trk_key(b);
+                   });
+  std::vector<std::vector<uint32_t>> byT(r.nt);
+  for (uint32_t d = 0; d < r.nd; d++)
+    if (e->active[d]) byT[e->dtp[d].track].push_back(d);
+  for (const auto &op : e->trkOps) {
+    lkf_engine::Pend q;
+    std::memset(&q.ev, 0, sizeof(q.ev));
+    q.ev.at = op.at;
+    q.key = op.key;
+    q.kind = op.kind;
+    q.ev.op = kOpLayerOffsets;
+    for (int k = 0; k < 4; k++) q.ev.a[k] = int64_t(uint64_t(op.offs[2 * k]) | (uint64_t(op.offs[2 * k + 1]) << 32));
+    q.ev.pad = int64_t(op.offs[8]);
+    for (uint32_t d : byT[op.track]) {
+      q.dt = d;
+      e->pending.push_back(q);
     }
   }
-  // Keyed ops: a DownTrack's in-batch ops must all be of one kind (its
-  // positions resolve in one space, and its lane stays sorted by at_pkt).
-  // Nothing of this run is enqueued yet: the ops are dropped, the batch stays.
-  const bool keyed = e->keyedPending;
-  e->keyedPending = false;
-  if (keyed) {
-    const int64_t bad = e->csr.mixed(e->pending.data(), e->pending.size(), e->dtLane.data(), nd);
-    if (bad >= 0) {
-      char buf[160];
-      snprintf(buf, sizeof(buf), "DownTrack %lld: control ops of two position kinds (lkf_at_kind) in one run",
-               (long long)bad);
-      e->err = buf;
-      e->pending.clear();
-      e->trkOps.clear();
-      return LKF_EINVAL;
-    }
-  }
-  for (const auto &op : e->trkOps)
-    std::memcpy(e->tracks[op.track].layer_offsets, op.offs, sizeof(op.offs));  // as of the end of this run
+}
+
+// Keyed ops: a DownTrack's in-batch ops must all be of one kind (its
+// positions resolve in one space, and its lane stays sorted by at_pkt).
+// Nothing of this run is enqueued yet: the ops are dropped, the batch stays.
+static int refuse_mixed_kinds(lkf_engine *e, const RunCtx &r) {
+  const int64_t bad = e->csr.mixed(e->pending.data(), e->pending.size(), e->dtLane.data(), r.nd);
+  if (bad < 0) return LKF_OK;
+  char buf[160];
+  snprintf(buf, sizeof(buf), "DownTrack %lld: control ops of two position kinds (lkf_at_kind) in one run",
+           (long long)bad);
+  e->err = buf;
+  e->pending.clear();
   e->trkOps.clear();
+  return LKF_EINVAL;
+}
+
+// The prep stream waits for the batch's inputs (the caller's stream, an
+// ingest) and for this context's previous batch; what kind of batch this is.
+static int wait_inputs(lkf_engine *e, BatchCtx &x, RunCtx &r, hipStream_t us) {
+  hipStream_t ps = e->prepS;
   HIPCHK(hipEventRecord(e->inEv, us), "event");
   HIPCHK(hipStreamWaitEvent(ps, e->inEv, 0), "wait caller stream");
   // this context's previous batch (run n-2) must have finished its emit stage
   if (x.used) HIPCHK(hipStreamWaitEvent(ps, x.emitted, 0), "wait emit");
   if (x.fromIngest && e->haveBatch) HIPCHK(hipStreamWaitEvent(ps, x.ingested, 0), "wait ingest");
-  const bool prepDone = x.fromIngest && e->haveBatch && x.prepByIngest && x.prepNT == nt && x.prepND == nd &&
-                        e->curPkts == x.dPktsOwn;
-  const bool ingestFed = x.fromIngest && e->haveBatch;  // (emit's residency, below)
+  r.prepDone = x.fromIngest && e->haveBatch && x.prepByIngest && x.prepNT == r.nt && x.prepND == r.nd &&
+               e->curPkts == x.dPktsOwn;
+  r.ingestFed = x.fromIngest && e->haveBatch;
   x.fromIngest = false;
   x.prepByIngest = false;
+  return LKF_OK;
+}
 
-  // Per-lane control-op CSR (stable: queue order within a lane, then by
-  // key: at_pkt, or a keyed op's datagram index / arrival time).  The host
-  // sorts only the ops: an LSD radix sort on the lane (8-bit digits, stable),
-  // then a stable insertion by key inside a lane with several ops; it stages
-  // the run's RunDesc, the sorted ops, their lanes and — in a run with keyed
-  // ops — their keys in this context's page-locked cached buffer.  The prep stage's
-  // first kernel pulls them and k_ev_offsets derives the dense per-lane
-  // offsets on the GPU (no host pass over all lanes).
-  const auto tp1 = clk::now();
+// Per-lane control-op CSR (stable: queue order within a lane, then by
+// key: at_pkt, or a keyed op's datagram index / arrival time).  The host
+// sorts only the ops: an LSD radix sort on the lane (8-bit digits, stable),
+// then a stable insertion by key inside a lane with several ops; it stages
+// the run's RunDesc, the sorted ops, their lanes and — in a run with keyed
+// ops — their keys in this context's page-locked cached buffer.  The prep stage's
+// first kernel pulls them and k_ev_offsets derives the dense per-lane
+// offsets on the GPU (no host pass over all lanes).
+static int stage_ctl(lkf_engine *e, BatchCtx &x, RunCtx &r) {
+  r.tp1 = clk::now();
   if (x.used) HIPCHK(hipEventSynchronize(x.pulled), "stage wait");  // run n-3's pull of this staging is done
   if (x.used && x.keyed) HIPCHK(hipEventSynchronize(x.prepped), "stage wait (keys)");  // ... and its resolver
-  x.keyed = keyed;
-  const auto tp2 = clk::now();
-  const size_t nev = e->csr.sort(e->pending.data(), e->pending.size(), e->dtLane.data(), nl);  // (ctl_csr.h)
+  x.keyed = r.keyed;
+  r.tp2 = clk::now();
+  const size_t nev = r.nev = e->csr.sort(e->pending.data(), e->pending.size(), e->dtLane.data(), r.nl);  // (ctl_csr.h)
   if (nev > x.stageCap || !x.stage.host) {  // (graphs captured with the old staging are re-captured)
     // the queued pull of this context's previous run may still read the old
     // staging, and its graphs are destroyed when re-captured: drain first
@@ -1714,32 +1698,29 @@ int lkf_run(lkf_engine *e, void *stream) {
     x.stageCap = 0;  // (set once the allocation has succeeded: a failed one is retried by the next run)
     // (a multiple of 4 ops: the keys behind the lane list stay 16-B aligned)
     const uint32_t cap = uint32_t(std::max<size_t>(2 * nev, 4096) + 3) & ~3u;
-    HIPCHK(x.stage.alloc(sizeof(RunDesc) + size_t(cap) * (sizeof(DevEvent) + 4 + sizeof(DevKey))), "alloc stage");
+    HIPCHK(x.stage.alloc(stage_bytes(cap)), "alloc stage");
     x.stageCap = cap;
-    x.gPrepEpoch[0] = x.gPrepEpoch[1] = 0;
-    x.gCtlEpoch = 0;
+    x.forget_pull_graphs();
   }
-  DevEvent *evs = reinterpret_cast<DevEvent *>(x.stage.host + sizeof(RunDesc));
-  uint32_t *lanes =
-      reinterpret_cast<uint32_t *>(x.stage.host + sizeof(RunDesc) + size_t(x.stageCap) * sizeof(DevEvent));
   // (the keys of a run with keyed ops: behind the lane list, read in place by k_ev_resolve)
-  const size_t keyOff = sizeof(RunDesc) + size_t(x.stageCap) * (sizeof(DevEvent) + 4);
-  e->csr.emit(e->pending.data(), evs, lanes, keyed ? reinterpret_cast<DevKey *>(x.stage.host + keyOff) : nullptr,
-              e->dtp.data());
+  uint8_t *h = x.stage.host;
+  e->csr.emit(e->pending.data(), reinterpret_cast<DevEvent *>(h + stage_ev_off(x.stageCap)),
+              reinterpret_cast<uint32_t *>(h + stage_lane_off(x.stageCap)),
+              r.keyed ? reinterpret_cast<DevKey *>(h + stage_key_off(x.stageCap)) : nullptr, e->dtp.data());
   e->pending.clear();
   {
-    RunDesc &h = *reinterpret_cast<RunDesc *>(x.stage.host);
-    std::memset(&h, 0, sizeof(h));
-    h.pkts = reinterpret_cast<uint64_t>(e->curPkts);
-    h.arena = reinterpret_cast<uint64_t>(e->curArena);
-    h.dd = reinterpret_cast<uint64_t>(e->curDD);
-    h.nDev = reinterpret_cast<uint64_t>(e->curNDev);
-    h.n = e->curN;
-    h.nev = uint32_t(nev);
-    h.evCap = x.stageCap;
+    RunDesc &d = *reinterpret_cast<RunDesc *>(h);
+    std::memset(&d, 0, sizeof(d));
+    d.pkts = reinterpret_cast<uint64_t>(e->curPkts);
+    d.arena = reinterpret_cast<uint64_t>(e->curArena);
+    d.dd = reinterpret_cast<uint64_t>(e->curDD);
+    d.nDev = reinterpret_cast<uint64_t>(e->curNDev);
+    d.n = e->curN;
+    d.nev = uint32_t(nev);
+    d.evCap = x.stageCap;
   }
-  const auto tp25 = clk::now();
-  if (nev > x.dEvents.cap() || size_t(nl) + 1 > x.dEvOff.cap() || nev > x.dEvLane.cap()) {
+  r.tp25 = clk::now();
+  if (nev > x.dEvents.cap() || size_t(r.nl) + 1 > x.dEvOff.cap() || nev > x.dEvLane.cap()) {
     // this context's op buffers: its previous run (n-3) must be done with them.
     // ps waits on that run's "emitted" event above, so draining ps covers its
     // prep, decide and emit stages (the lane list is read by k_ev_offsets on ps,
@@ -1748,117 +1729,110 @@ int lkf_run(lkf_engine *e, void *stream) {
     // and the graphs captured with them are destroyed below)
     if (int rc = drain_streams(e)) return rc;
     if (nev > x.dEvents.cap()) HIPCHK(x.dEvents.reserve(2 * nev, 4096), "alloc events");
-    if (size_t(nl) + 1 > x.dEvOff.cap()) HIPCHK(x.dEvOff.alloc(size_t(nl) + 1 + 4096), "alloc evoff");
+    if (size_t(r.nl) + 1 > x.dEvOff.cap()) HIPCHK(x.dEvOff.alloc(size_t(r.nl) + 1 + 4096), "alloc evoff");
     if (nev > x.dEvLane.cap()) HIPCHK(x.dEvLane.reserve(2 * nev, 4096), "alloc evlane");
-    x.gPrepEpoch[0] = x.gPrepEpoch[1] = 0;
-    x.gCtlEpoch = 0;
+    x.forget_pull_graphs();
   }
-  const auto tp3 = clk::now();
+  r.tp3 = clk::now();
+  return LKF_OK;
+}
 
-  // ---- prep stage (prep stream): the pull, per-batch init, track ranges,
-  // slot scan, layer index, tracker observe, DD decode
-  Event *rg = e->ring[e->nRuns % lkf_engine::kRing];
-  if (!e->ingestStarted) HIPCHK(hipEventRecord(rg[0], ps), "event");  // else: recorded ahead of the ingest
+// A stage's launches on stream st (pull_body, prep_body, scan_tail).
+using StageBody = int (*)(lkf_engine *e, BatchCtx &x, const RunCtx &r, hipStream_t st);
+
+// (Re)captures a stage as a graph on stream st: the captured launches are the
+// same as the direct ones.
+static int capture_stage(lkf_engine *e, BatchCtx &x, const RunCtx &r, hipStream_t st, GraphExec &g, StageBody body) {
+  // an exec is destroyed only once its last launch (on st, this context's
+  // previous run) has finished: HIP may release its kernel arguments at once
+  if (g) {
+    HIPCHK(hipStreamSynchronize(st), "graph idle");
+    HIPCHK(g.destroy(), "graph destroy");
+  }
+  HIPCHK(hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed), "begin capture");
+  const int rc = body(e, x, r, st);
+  hipGraph_t graph = nullptr;
+  const hipError_t re = hipStreamEndCapture(st, &graph);
+  if (rc) return rc;
+  HIPCHK(re, "end capture");
+  const hipError_t ri = hipGraphInstantiate(&g.h, graph, nullptr, nullptr, 0);
+  (void)hipGraphDestroy(graph);
+  HIPCHK(ri, "graph instantiate");
+  return LKF_OK;
+}
+
+// One stage on stream st: its graph, re-captured when the topology epoch moved
+// (or nothing is captured yet), or — LKF_GRAPH=0 — body's launches directly.
+static int run_stage(lkf_engine *e, BatchCtx &x, const RunCtx &r, hipStream_t st, StageGraph &g, StageBody body,
+                     const char *what) {
+  if (!e->knobs.useGraph) return body(e, x, r, st);
+  if (g.epoch != e->epoch || !g.exec) {
+    if (int rc = capture_stage(e, x, r, st, g.exec, body)) return rc;
+    g.epoch = e->epoch;
+  }
+  HIPCHK(hipGraphLaunch(g.exec, st), what);
+  return LKF_OK;
+}
+
+// the control-op pull (k_h2d: the run descriptor and the ops from the
+// pinned staging; k_ev_offsets)
+static int pull_body(lkf_engine *e, BatchCtx &x, const RunCtx &r, hipStream_t cs) {
+  HIPCHK(launch_h2d(cs, x.stage.dev, x.dDesc, x.dEvents, x.dEvLane), "event pull");
+  HIPCHK(launch_ev_offsets(cs, x.dEvLane, x.dDesc, r.nl, x.dEvOff), "event offsets");
+  return LKF_OK;
+}
+
+static int prep_body(lkf_engine *e, BatchCtx &x, const RunCtx &r, hipStream_t ps) {
+  const uint32_t nt = r.nt, nd = r.nd;
+  if (!r.prepDone) {  // (an ingest's k_ing_out did both)
+    HIPCHK(launch_batch_init(ps, nt, nd, kStatsWords * (1 + kStatCopies), x.dTBegin, x.dTEnd, x.dTRuns, x.dErr,
+                             x.dStats, x.dFwdCnt, x.dFwdBytes),
+           "batch init");
+    HIPCHK(launch_track_ranges(ps, x.dDesc, e->cfg.max_batch_pkts, nt, x.dTBegin, x.dTEnd, x.dTRuns, x.dErr),
+           "track_ranges");
+  }
+  HIPCHK(launch_scan(ps, 0, e->dDTs, x.dTBegin, x.dTEnd, nullptr, nullptr, nd, x.dPartA, nullptr, x.dSlotBase,
+                     nullptr, x.dTot + 0, nullptr, nullptr),
+         "slot scan");
+  HIPCHK(launch_layer_index(ps, x.dDesc, x.dTBegin, x.dTEnd, nt, e->cfg.max_batch_pkts, x.dLayerList,
+                            x.dLayerBefore, x.dLayerCnt, e->ddAlloc ? x.dDDUsed : nullptr),
+         "layer index");
+  if (e->nTrk)  // StreamTracker.Observe of every (track, spatial layer) tracker (receiver.go:686-695)
+    HIPCHK(launch_tracker_observe(ps, e->dTrk, e->nTrk, x.dDesc, x.dTBegin, x.dTEnd), "tracker observe");
+  if (e->ddAlloc) {  // dependency descriptors of this batch (track structure rings advance in order)
+    HIPCHK(launch_dd_decode(ps, x.dDesc, x.dTBegin, x.dTEnd, e->dTracks, nt, e->dDDStruct, e->dDDTrack, x.dDDPkt,
+                            x.dErr, e->nDDTrk ? e->dTrackDDTrk : nullptr, e->dDDTrk, x.dDDSpill,
+                            reinterpret_cast<uint32_t *>(x.dDDUsed + 1), uint32_t(x.dDDSpill.cap())),
+           "dd decode");
+  }
+  return LKF_OK;
+}
+
+// ---- prep stage (prep stream): the pull, per-batch init, track ranges,
+// slot scan, layer index, tracker observe, DD decode, key resolve
+static int enqueue_prep(lkf_engine *e, BatchCtx &x, const RunCtx &r) {
+  hipStream_t ps = e->prepS;
+  if (!e->ingestStarted) HIPCHK(hipEventRecord(r.rg[0], ps), "event");  // else: recorded ahead of the ingest
   e->ingestStarted = false;
-  // the control-op pull (k_h2d: the run descriptor and the ops from the
-  // pinned staging; k_ev_offsets) on the engine's own stream: it does not
-  // depend on the batch, so it runs beside a preceding ingest instead of after
-  // it on the prep stream
+  // the control-op pull on the engine's own stream: it does not depend on the
+  // batch, so it runs beside a preceding ingest instead of after it on the
+  // prep stream
   hipStream_t cs = e->own;
   if (x.used) HIPCHK(hipStreamWaitEvent(cs, x.emitted, 0), "wait emit (pull)");
-  auto ctl = [&]() -> int {
-    HIPCHK(launch_h2d(cs, x.stage.dev, x.dDesc, x.dEvents, x.dEvLane), "event pull");
-    HIPCHK(launch_ev_offsets(cs, x.dEvLane, x.dDesc, nl, x.dEvOff), "event offsets");
-    return LKF_OK;
-  };
-  auto prep = [&]() -> int {
-    if (!prepDone) {  // (an ingest's k_ing_out did both)
-      HIPCHK(launch_batch_init(ps, nt, nd, kStatsWords * (1 + kStatCopies), x.dTBegin, x.dTEnd, x.dTRuns, x.dErr,
-                               x.dStats, x.dFwdCnt, x.dFwdBytes),
-             "batch init");
-      HIPCHK(launch_track_ranges(ps, x.dDesc, e->cfg.max_batch_pkts, nt, x.dTBegin, x.dTEnd, x.dTRuns, x.dErr),
-             "track_ranges");
-    }
-    HIPCHK(launch_scan(ps, 0, e->dDTs, x.dTBegin, x.dTEnd, nullptr, nullptr, nd, x.dPartA, nullptr, x.dSlotBase,
-                       nullptr, x.dTot + 0, nullptr, nullptr),
-           "slot scan");
-    HIPCHK(launch_layer_index(ps, x.dDesc, x.dTBegin, x.dTEnd, nt, e->cfg.max_batch_pkts, x.dLayerList,
-                              x.dLayerBefore, x.dLayerCnt, e->ddAlloc ? x.dDDUsed : nullptr),
-           "layer index");
-    if (e->nTrk)  // StreamTracker.Observe of every (track, spatial layer) tracker (receiver.go:686-695)
-      HIPCHK(launch_tracker_observe(ps, e->dTrk, e->nTrk, x.dDesc, x.dTBegin, x.dTEnd), "tracker observe");
-    if (e->ddAlloc) {  // dependency descriptors of this batch (track structure rings advance in order)
-      HIPCHK(launch_dd_decode(ps, x.dDesc, x.dTBegin, x.dTEnd, e->dTracks, nt, e->dDDStruct, e->dDDTrack, x.dDDPkt,
-                              x.dErr, e->nDDTrk ? e->dTrackDDTrk : nullptr, e->dDDTrk, x.dDDSpill,
-                              reinterpret_cast<uint32_t *>(x.dDDUsed + 1), uint32_t(x.dDDSpill.cap())),
-             "dd decode");
-    }
-    return LKF_OK;
-  };
-  auto scanTail = [&](hipStream_t st) -> int {
-    // counters and the output scan stay on the (high-priority) decide stream:
-    // on the low-priority emit stream these small kernels queued behind the
-    // next batch's decide waves and were on the emit chain's critical path
-    HIPCHK(launch_stats_reduce(st, x.dStats), "stats reduce");
-    HIPCHK(launch_scan(st, 1, e->dDTs, nullptr, nullptr, x.dFwdCnt, x.dFwdBytes, nd, x.dPartA, nullptr, x.dRecBase,
-                       x.dByteBase, x.dTot + 2, x.dTot + 3, e->dPerm, x.dGFirst, e->cfg.max_out_pkts),
-           "out scan");
-    return LKF_OK;
-  };
-  // (re)captures a stage as a graph on stream st: the captured launches are the
-  // same as the direct ones
-  auto capture = [&](hipStream_t st, GraphExec &g, auto body) -> int {
-    // an exec is destroyed only once its last launch (on st, this context's
-    // previous run) has finished: HIP may release its kernel arguments at once
-    if (g) {
-      HIPCHK(hipStreamSynchronize(st), "graph idle");
-      HIPCHK(g.destroy(), "graph destroy");
-    }
-    HIPCHK(hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed), "begin capture");
-    const int rc = body();
-    hipGraph_t graph = nullptr;
-    const hipError_t r = hipStreamEndCapture(st, &graph);
-    if (rc) return rc;
-    HIPCHK(r, "end capture");
-    const hipError_t ri = hipGraphInstantiate(&g.h, graph, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(graph);
-    HIPCHK(ri, "graph instantiate");
-    return LKF_OK;
-  };
-  if (e->knobs.useGraph) {
-    if (x.gCtlEpoch != e->epoch || !x.gCtl) {
-      const int rc = capture(cs, x.gCtl, ctl);
-      if (rc) return rc;
-      x.gCtlEpoch = e->epoch;
-    }
-    HIPCHK(hipGraphLaunch(x.gCtl, cs), "pull graph");
-  } else {
-    const int rc = ctl();
-    if (rc) return rc;
-  }
+  if (int rc = run_stage(e, x, r, cs, x.gCtl, pull_body, "pull graph")) return rc;
   HIPCHK(hipEventRecord(x.pulled, cs), "event");
   HIPCHK(hipStreamWaitEvent(ps, x.pulled, 0), "wait pull");
-  if (e->knobs.useGraph) {
-    const int fi = prepDone ? 1 : 0;
-    if (x.gPrepEpoch[fi] != e->epoch || !x.gPrep[fi]) {
-      const int rc = capture(ps, x.gPrep[fi], prep);
-      if (rc) return rc;
-      x.gPrepEpoch[fi] = e->epoch;
-    }
-    HIPCHK(hipGraphLaunch(x.gPrep[fi], ps), "prep graph");
-  } else {
-    const int rc = prep();
-    if (rc) return rc;
-  }
-  if (keyed && nev) {
+  StageGraph &gPrep = x.gPrep[r.prepDone ? 1 : 0];
+  if (int rc = run_stage(e, x, r, ps, gPrep, prep_body, "prep graph")) return rc;
+  if (r.keyed && r.nev) {
     // Keyed ops -> ExtPacket indices (DevEvent.at), after the pull and the
     // track ranges, before the decide stage reads the ops.  Launched directly
     // and only for a run with keyed ops: a run without them enqueues what it
     // always did.
     const bool scan = e->curFromIngest && e->curNDev;  // (an empty ingest: every datagram key is past it)
-    HIPCHK(launch_ev_resolve(ps, reinterpret_cast<const DevKey *>(x.stage.dev + keyOff), x.dEvents, x.dEvLane,
-                             uint32_t(nev), e->curPkts, x.dTBegin, x.dTEnd, nt, scan ? e->dPos.get() : nullptr,
-                             e->curFromIngest ? e->lastIngestN : 0xffffffffu),
+    HIPCHK(launch_ev_resolve(ps, reinterpret_cast<const DevKey *>(x.stage.dev + stage_key_off(x.stageCap)), x.dEvents,
+                             x.dEvLane, uint32_t(r.nev), e->curPkts, x.dTBegin, x.dTEnd, r.nt,
+                             scan ? e->dPos.get() : nullptr, e->curFromIngest ? e->lastIngestN : 0xffffffffu),
            "key resolve");
     if (scan) {
       HIPCHK(hipEventRecord(e->scanRead, ps), "event");
@@ -1871,18 +1845,40 @@ int lkf_run(lkf_engine *e, void *stream) {
     uint64_t u[2] = {0, 0};
     HIPCHK(hipMemcpy(u, x.dDDUsed, sizeof(u), hipMemcpyDeviceToHost), "debug copy");
     fprintf(stderr, "[lkf dd] run %llu ctx %d after prep: cursor %llu spill %llu graph %d epoch %llu/%llu\n",
-            (unsigned long long)e->nRuns, ci, (unsigned long long)u[0], (unsigned long long)u[1], int(e->knobs.useGraph),
-            (unsigned long long)x.gPrepEpoch[prepDone ? 1 : 0], (unsigned long long)e->epoch);
+            (unsigned long long)e->nRuns, r.ci, (unsigned long long)u[0], (unsigned long long)u[1],
+            int(e->knobs.useGraph), (unsigned long long)gPrep.epoch, (unsigned long long)e->epoch);
   }
-  HIPCHK(hipStreamWaitEvent(s, x.prepped, 0), "wait prep");
-  DecideLaunch d;
+  return LKF_OK;
+}
+
+// Several DownTracks per decide wave when the batch is short (a 10-20 ms
+// tick has a few packets per track): the per-DownTrack prologue then
+// dominates and one workgroup per DownTrack is dispatch-rate bound.
+static uint32_t decide_per_wave(const lkf_engine *e, const RunCtx &r) {
+  if (e->knobs.decideK) return e->knobs.decideK;
+  // (round 6: 2 below 48 packets per track — 4 at the shortest ticks measured
+  // slower since the stream wave and the NACK queues changed: 10-ms ticks at
+  // 1,000 rooms 0.555 -> 0.533 ms ingress, 0.338 -> 0.331 ms ExtPacket, at 100
+  // rooms 0.130 -> 0.106 ms; 1: 0.557 / 0.346 ms; profiles/r6_ab_runs.txt)
+  // Many DownTracks: one wave each is bound by the dispatch rate (≈240 waves
+  // per µs over the 8 XCDs: configs[2]'s 337 k DownTracks ≈ 1.4 ms), so a
+  // wave serves one more DownTrack per 100 k (configs[2] 2.74 -> 2.54 ms at
+  // 4; configs[1]'s 18 k stay at one: 2 costs 0.74 -> 0.87 ms there;
+  // configs[3]'s 100 k measured alike at 1 and 2)
+  const uint64_t per = uint64_t(e->curN) / std::max<uint32_t>(1, r.nt);  // (ingest: the datagram count bound)
+  const uint32_t byCount = uint32_t(std::min<uint64_t>(8, (uint64_t(r.nd) + 99999) / 100000));
+  return std::max<uint32_t>(per >= 48 ? 1 : 2, byCount);
+}
+
+static DecideArgs decide_args(const lkf_engine *e, const BatchCtx &x, const RunCtx &r) {
+  DecideArgs d{};
   d.layerList = x.dLayerList;
   d.layerBefore = x.dLayerBefore;
   d.layerCnt = x.dLayerCnt;
   d.pktStride = e->cfg.max_batch_pkts;
   d.sched = e->dSched;
   d.waveTrack = e->dWaveTrack;
-  d.nlanes = nl;
+  d.nlanes = r.nl;
   d.hot = e->dHot;
   d.dts = e->dDTs;
   d.tracks = e->dTracks;
@@ -1912,53 +1908,44 @@ int lkf_run(lkf_engine *e, void *stream) {
   d.fwdBytes = x.dFwdBytes;
   d.dtCum = e->dDTCum;
   d.stats = x.dStats;
-  d.ddLanes = e->ddLanes;
-  // Several DownTracks per decide wave when the batch is short (a 10-20 ms
-  // tick has a few packets per track): the per-DownTrack prologue then
-  // dominates and one workgroup per DownTrack is dispatch-rate bound.
-  if (e->knobs.decideK) {
-    d.perWave = e->knobs.decideK;
-  } else {
-    // (round 6: 2 below 48 packets per track — 4 at the shortest ticks measured
-    // slower since the stream wave and the NACK queues changed: 10-ms ticks at
-    // 1,000 rooms 0.555 -> 0.533 ms ingress, 0.338 -> 0.331 ms ExtPacket, at 100
-    // rooms 0.130 -> 0.106 ms; 1: 0.557 / 0.346 ms; profiles/r6_ab_runs.txt)
-    // Many DownTracks: one wave each is bound by the dispatch rate (≈240 waves
-    // per µs over the 8 XCDs: configs[2]'s 337 k DownTracks ≈ 1.4 ms), so a
-    // wave serves one more DownTrack per 100 k (configs[2] 2.74 -> 2.54 ms at
-    // 4; configs[1]'s 18 k stay at one: 2 costs 0.74 -> 0.87 ms there;
-    // configs[3]'s 100 k measured alike at 1 and 2)
-    const uint64_t per = uint64_t(e->curN) / std::max<uint32_t>(1, nt);  // (ingest: the datagram count bound)
-    const uint32_t byCount = uint32_t(std::min<uint64_t>(8, (uint64_t(nd) + 99999) / 100000));
-    d.perWave = std::max<uint32_t>(per >= 48 ? 1 : 2, byCount);
-  }
-  d.ddPkts = e->ddAlloc ? x.dDDPkt : nullptr;
+  d.perWave = decide_per_wave(e, r);
+  d.ddPkts = e->ddAlloc ? x.dDDPkt.get() : nullptr;
   d.ddStructs = e->dDDStruct;
-  d.ddState = e->ddAlloc ? e->dDDState : nullptr;
+  d.ddState = e->ddAlloc ? e->dDDState.get() : nullptr;
   d.ddArena = x.dDDArena;
   d.ddUsed = x.dDDUsed;
-  d.ddSpill = e->ddAlloc ? x.dDDSpill : nullptr;
+  d.ddSpill = e->ddAlloc ? x.dDDSpill.get() : nullptr;
   d.ddCap = x.dDDArena.cap();
   d.maxDts = e->cfg.max_downtracks;
   d.maxTracks = e->cfg.max_tracks;
   d.npkts = e->curN;  // (an ingest-produced batch: the launch bound)
-  d.nev = uint32_t(nev);
-  HIPCHK(hipEventRecord(rg[1], s), "event");
-  HIPCHK(launch_decide(s, d), "decide");
-  HIPCHK(hipEventRecord(rg[2], s), "event");
-  if (e->knobs.useGraph) {
-    if (x.gScanEpoch != e->epoch || !x.gScan) {
-      const int rc = capture(s, x.gScan, [&]() { return scanTail(s); });
-      if (rc) return rc;
-      x.gScanEpoch = e->epoch;
-    }
-    HIPCHK(hipGraphLaunch(x.gScan, s), "scan graph");
-  } else {
-    const int rc = scanTail(s);
-    if (rc) return rc;
-  }
+  d.nev = uint32_t(r.nev);
+  return d;
+}
+
+static int scan_tail(lkf_engine *e, BatchCtx &x, const RunCtx &r, hipStream_t st) {
+  // counters and the output scan stay on the (high-priority) decide stream:
+  // on the low-priority emit stream these small kernels queued behind the
+  // next batch's decide waves and were on the emit chain's critical path
+  HIPCHK(launch_stats_reduce(st, x.dStats), "stats reduce");
+  HIPCHK(launch_scan(st, 1, e->dDTs, nullptr, nullptr, x.dFwdCnt, x.dFwdBytes, r.nd, x.dPartA, nullptr, x.dRecBase,
+                     x.dByteBase, x.dTot + 2, x.dTot + 3, e->dPerm, x.dGFirst, e->cfg.max_out_pkts),
+         "out scan");
+  return LKF_OK;
+}
+
+// ---- decide stage (decide stream): decide, its counters and output scan,
+// the transport-cc bases, the sequencer's DD bytes
+static int enqueue_decide(lkf_engine *e, BatchCtx &x, const RunCtx &r) {
+  hipStream_t s = e->decS;
+  HIPCHK(hipStreamWaitEvent(s, x.prepped, 0), "wait prep");
+  const DecideArgs d = decide_args(e, x, r);
+  HIPCHK(hipEventRecord(r.rg[1], s), "event");
+  HIPCHK(launch_decide(s, d, e->ddLanes), "decide");
+  HIPCHK(hipEventRecord(r.rg[2], s), "event");
+  if (int rc = run_stage(e, x, r, s, x.gScan, scan_tail, "scan graph")) return rc;
   if (e->anyTwcc)  // the transports' sequence ranges of this batch (after the forwarded counts)
-    HIPCHK(launch_twcc_base(s, e->dDTs, nd, x.dFwdCnt, e->dTwccCtrD, e->dTwccCtrT, e->dTwccTOff, e->dTwccTList,
+    HIPCHK(launch_twcc_base(s, e->dDTs, r.nd, x.dFwdCnt, e->dTwccCtrD, e->dTwccCtrT, e->dTwccTOff, e->dTwccTList,
                             e->nTwccT, x.dTwccBase),
            "twcc base");
   HIPCHK(hipEventRecord(x.decided, s), "event");
@@ -1983,13 +1970,11 @@ int lkf_run(lkf_engine *e, void *stream) {
     q.ddArena = x.dDDArena;
     HIPCHK(launch_seq_dd(s, q), "sequencer dd");
   }
+  return LKF_OK;
+}
 
-  // ---- emit stage (emit stream): wire bytes.  The decide stream goes
-  // straight on to the next batch's decide.
-  hipStream_t es = e->emitS;
-  HIPCHK(hipStreamWaitEvent(es, x.decided, 0), "wait decided");
-  HIPCHK(hipEventRecord(rg[3], es), "event");
-  EmitLaunch m;
+static EmitArgs emit_args(const lkf_engine *e, const BatchCtx &x, const RunCtx &r) {
+  EmitArgs m{};
   m.perm = e->dPerm;
   m.recBase = x.dRecBase;
   m.byteBase = x.dByteBase;
@@ -2002,35 +1987,52 @@ int lkf_run(lkf_engine *e, void *stream) {
   m.pkts = e->curPkts;
   m.arena = e->curArena;
   m.dts = e->dDTs;
-  m.ndts = nd;
+  m.ndts = r.nd;
   m.out = x.dOut;
   m.outArena = x.dOutArena;
   m.outCap = e->cfg.max_out_pkts;
   m.outByteCap = e->cfg.max_out_bytes;
   m.err = x.dErr;
-  m.ddArena = e->ddAlloc ? x.dDDArena : nullptr;
+  m.ddArena = e->ddAlloc ? x.dDDArena.get() : nullptr;
   m.maxDts = e->cfg.max_downtracks;
   m.npkts = e->curN;
   m.tupleCap = e->cfg.max_batch_tuples;
   m.arenaLen = e->curArenaLen;
   m.ddCap = x.dDDArena.cap();
-  m.twccBase = e->anyTwcc ? x.dTwccBase : nullptr;
+  m.twccBase = e->anyTwcc ? x.dTwccBase.get() : nullptr;
   m.gCap = e->cfg.max_out_pkts / 64 + 2;
-  // One workgroup per 64-record group (grid = the capacity bound; workgroups
-  // past the batch's records exit at once).  Short-lived workgroups free their
-  // slots as they finish, so the next batch's decide stage (higher-priority
-  // stream) interleaves with this emit instead of waiting for a persistent grid.
-  m.grid = e->knobs.emitPersistent ? e->emitGrid
-                             : uint32_t(((e->cfg.max_out_pkts + 63) / 64 + 7) / 8 * 8);
-  // An ingest-fed batch's emit runs beside the next ingest chain: at a low
-  // fan-out (fewer than emitCapFanout DownTracks per track) its workgroups are
-  // capped at 12 per CU (LDS reserved at launch), which keeps the payload lines
-  // its DownTracks re-read in L2 and leaves CUs to the ingest (configs[1], 9 per
-  // track: 0.78 -> 0.74 ms per step).  A submitted batch's emit, or one with a
-  // high fan-out, is most of the step and runs uncapped (the cap: ExtPacket
-  // configs[1] 0.455 -> 0.54 ms, configs[2] 2.51 -> 2.83 ms, configs[3] 3.35 ->
-  // 3.47 ms; profiles/r6_ab_runs.txt).
-  m.ldsPad = (ingestFed && uint64_t(nd) < uint64_t(e->knobs.emitCapFanout) * std::max<uint32_t>(1, nt)) ? e->knobs.emitLdsPad : 0;
+  return m;
+}
+
+// One workgroup per 64-record group (grid = the capacity bound; workgroups
+// past the batch's records exit at once).  Short-lived workgroups free their
+// slots as they finish, so the next batch's decide stage (higher-priority
+// stream) interleaves with this emit instead of waiting for a persistent grid.
+static uint32_t emit_grid(const lkf_engine *e) {
+  return e->knobs.emitPersistent ? e->emitGrid : uint32_t(((e->cfg.max_out_pkts + 63) / 64 + 7) / 8 * 8);
+}
+
+// An ingest-fed batch's emit runs beside the next ingest chain: at a low
+// fan-out (fewer than emitCapFanout DownTracks per track) its workgroups are
+// capped at 12 per CU (LDS reserved at launch), which keeps the payload lines
+// its DownTracks re-read in L2 and leaves CUs to the ingest (configs[1], 9 per
+// track: 0.78 -> 0.74 ms per step).  A submitted batch's emit, or one with a
+// high fan-out, is most of the step and runs uncapped (the cap: ExtPacket
+// configs[1] 0.455 -> 0.54 ms, configs[2] 2.51 -> 2.83 ms, configs[3] 3.35 ->
+// 3.47 ms; profiles/r6_ab_runs.txt).
+static uint32_t emit_lds_pad(const lkf_engine *e, const RunCtx &r) {
+  const bool lowFanout = uint64_t(r.nd) < uint64_t(e->knobs.emitCapFanout) * std::max<uint32_t>(1, r.nt);
+  return r.ingestFed && lowFanout ? e->knobs.emitLdsPad : 0;
+}
+
+// ---- emit stage (emit stream): wire bytes.  The decide stream goes
+// straight on to the next batch's decide.
+static int enqueue_emit(lkf_engine *e, BatchCtx &x, const RunCtx &r) {
+  hipStream_t es = e->emitS;
+  HIPCHK(hipStreamWaitEvent(es, x.decided, 0), "wait decided");
+  HIPCHK(hipEventRecord(r.rg[3], es), "event");
+  const EmitArgs m = emit_args(e, x, r);
+  const uint32_t grid = emit_grid(e);
   x.egress = e->egress;
   if (x.egress == LKF_EGRESS_PREFIX) {  // records + prefixes only (three launches, no payload traffic)
     EmitPrefixLaunch q;
@@ -2038,41 +2040,98 @@ int lkf_run(lkf_engine *e, void *stream) {
     q.gSum = x.dPreGSum;
     q.gBase = x.dPreGBase;
     q.total = x.dPreTot;
-    if (nd)
-      HIPCHK(launch_emit_prefix(e->emitS, m, q), "emit prefix");
+    if (r.nd)
+      HIPCHK(launch_emit_prefix(es, m, grid, q), "emit prefix");
     else
-      HIPCHK(hipMemsetAsync(x.dPreTot, 0, sizeof(uint64_t), e->emitS), "emit prefix");
-  } else if (nd) {
-    HIPCHK(launch_emit(e->emitS, m), "emit");
+      HIPCHK(hipMemsetAsync(x.dPreTot, 0, sizeof(uint64_t), es), "emit prefix");
+  } else if (r.nd) {
+    HIPCHK(launch_emit(es, m, grid, emit_lds_pad(e, r)), "emit");
   }
-  HIPCHK(hipEventRecord(rg[4], e->emitS), "event");
-  HIPCHK(launch_accumulate(e->emitS, x.dStats, x.dTot, e->dCum, x.dErr, e->dSticky), "accumulate");
+  HIPCHK(hipEventRecord(r.rg[4], es), "event");
+  HIPCHK(launch_accumulate(es, x.dStats, x.dTot, e->dCum, x.dErr, e->dSticky), "accumulate");
   // (sendingPacket -> RTPStatsSender.Update of every forwarded tuple runs inside
   // decide, ss_fold.)  This batch's bucket copies (sender stream) finish before
   // its context counts as done.
   if (e->bktStorePending) {
     HIPCHK(hipEventRecord(x.sent, e->sendS), "event");
-    HIPCHK(hipStreamWaitEvent(e->emitS, x.sent, 0), "wait bucket store");
+    HIPCHK(hipStreamWaitEvent(es, x.sent, 0), "wait bucket store");
   }
   e->bktStorePending = false;
-  HIPCHK(hipEventRecord(x.emitted, e->emitS), "event");
+  HIPCHK(hipEventRecord(x.emitted, es), "event");
+  return LKF_OK;
+}
+
+// End-of-run bookkeeping: the host profile, then the engine moves on to the
+// next context.
+static void finish_run(lkf_engine *e, BatchCtx &x, const RunCtx &r) {
   if (e->knobs.hostProf && e->nRuns >= 3) {  // steady state: skip the first runs (initial control ops, first touch)
-    e->hp[0] += std::chrono::duration<double, std::milli>(tp1 - tp0).count();
-    e->hp[1] += std::chrono::duration<double, std::milli>(tp2 - tp1).count();
-    e->hp[2] += std::chrono::duration<double, std::milli>(tp25 - tp2).count();
-    e->hp[6] += std::chrono::duration<double, std::milli>(tp3 - tp25).count();
-    e->hp[3] += ms_since(tp3);
-    e->hp[4] += ms_since(tp0);
+    e->hp[0] += ms_between(r.tp0, r.tp1);
+    e->hp[1] += ms_between(r.tp1, r.tp2);
+    e->hp[2] += ms_between(r.tp2, r.tp25);
+    e->hp[6] += ms_between(r.tp25, r.tp3);
+    e->hp[3] += ms_since(r.tp3);
+    e->hp[4] += ms_since(r.tp0);
     e->hp[5] += 1;
   }
   x.used = true;
   x.protectedRun = false;
   if (!e->protRun.empty()) e->protRun[e->nRuns % 256] = 0;
-  e->lastCtx = ci;
+  e->lastCtx = r.ci;
   e->nRuns++;
   e->haveBatch = false;
   e->curNDev = nullptr;
   e->curDD = nullptr;
+}
+
+int lkf_run(lkf_engine *e, void *stream) {
+  if (!e) return LKF_EINVAL;
+  HIPCHK(hipSetDevice(e->dev), "hipSetDevice");
+  if (int rc = flush_topology(e)) return rc;
+  if (e->schedDirty) {
+    if (int rc = rebuild_sched(e)) return rc;
+  }
+  if (e->twccDirty) {
+    if (int rc = rebuild_twcc(e)) return rc;
+  }
+  RunCtx r{};
+  r.ci = int(e->nRuns % lkf_engine::kCtx);
+  BatchCtx &x = e->ctx[r.ci];
+  if (!e->haveBatch) {  // control-only run: an empty batch applies queued ops
+    e->curPkts = x.dPktsOwn;
+    e->curArena = x.dArenaOwn;
+    e->curOwned = e->curDDOwned = true;
+    e->curN = 0;
+    e->curNDev = nullptr;
+    e->curArenaLen = 0;
+    e->curFromIngest = false;
+  }
+  // The caller's stream orders the batch's inputs; the stages themselves run
+  // on the engine's streams (completion: lkf_sync).  The prep stream (the
+  // control-op CSR's offsets, per-batch init, track ranges, slot scan, layer
+  // index and, before lkf_run, the ingest) runs ahead: batch n+1 is prepared
+  // while batch n decides, so decide(n+1) starts as soon as decide(n) ends.
+  r.tp0 = clk::now();
+  hipStream_t us = stream ? reinterpret_cast<hipStream_t>(stream) : e->own;
+  e->cur = us;
+  r.nt = uint32_t(e->tracks.size());
+  r.nd = uint32_t(e->dtp.size());
+  r.nl = uint32_t(e->sched.size());
+  r.rg = e->ring[e->nRuns % lkf_engine::kRing];
+  expand_track_ops(e, r);
+  r.keyed = e->keyedPending;
+  e->keyedPending = false;
+  if (r.keyed) {
+    if (int rc = refuse_mixed_kinds(e, r)) return rc;
+  }
+  for (const auto &op : e->trkOps)
+    std::memcpy(e->tracks[op.track].layer_offsets, op.offs, sizeof(op.offs));  // as of the end of this run
+  e->trkOps.clear();
+  if (int rc = wait_inputs(e, x, r, us)) return rc;
+  if (int rc = stage_ctl(e, x, r)) return rc;
+  if (int rc = enqueue_prep(e, x, r)) return rc;
+  if (int rc = enqueue_decide(e, x, r)) return rc;
+  if (int rc = enqueue_emit(e, x, r)) return rc;
+  finish_run(e, x, r);
   return LKF_OK;
 }
 
@@ -3117,7 +3176,7 @@ static int pad_common(lkf_engine *e, int blank, const lkf_pad_req *reqs, uint32_
     HIPCHK(hipMemcpyAsync(e->dPadReq, lq.data(), m * sizeof(lkf_pad_req), hipMemcpyHostToDevice, ds), "pad req copy");
     HIPCHK(hipMemcpyAsync(e->dPadOff, loff.data(), 2 * size_t(m) * sizeof(uint64_t), hipMemcpyHostToDevice, ds),
            "pad off copy");
-    PadLaunch a;
+    PadArgs a{};
     a.blank = blank;
     a.n = m;
     a.reqs = e->dPadReq;

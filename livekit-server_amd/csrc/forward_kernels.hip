@@ -1668,57 +1668,6 @@ __global__ void __launch_bounds__(SCAN_T) k_scan_1p(ScanIn in, u32 n, u32 nb, u6
   }
 }
 
-// ---------------------------------------------------------------------------
-// k_decide_dt arguments.
-// ---------------------------------------------------------------------------
-struct DecideArgs {
-  const u32 *sched;      // lane -> DownTrack (0xffffffff = idle lane)
-  const u32 *waveTrack;  // wave -> track (every lane of a wave serves one track)
-  u32 nlanes;
-  DTHot *hot;
-  const DevDT *dts;
-  const DevTrack *tracks;
-  RangeEntry *rm;
-  VP8Cold *vc;
-  SeqMeta *seq;
-  u32 seqSize;
-  u8 *srm;  // SeqRM regions (stride srmStride), read with F_SEQ_RM
-  u64 srmStride;
-  u32 srmCap;
-  const lkf_pkt *pkts;
-  const u32 *tBegin, *tEnd;
-  const u64 *slotBase;
-  FwdRec *recs;
-  FwdBase *fbase;  // per DownTrack: its first forwarded record's munged SN / TS (FwdRec widening)
-  FwdBase *wide;   // per tuple slot: the full SN / TS of a T_WIDE record
-  u64 tupleCap;
-  u32 *err;
-  SenderStats *ss;  // RTPStatsSender per DownTrack (+ snInfo ring, gap histogram)
-  u32 *ssRing, *ssGap;
-  u32 *dtOffs;      // per DownTrack reference-layer offsets (kDTOffsWords)
-  const DevEvent *events;
-  const u32 *evOff;  // per lane [evOff[l], evOff[l+1])
-  u32 *fwdCnt;
-  u64 *fwdBytes;
-  DTCum *dtCum;  // per DownTrack totals (sendingPacket counters)
-  u64 *stats;  // lkf_stats as u64[15]
-  const u32 *layerList, *layerBefore, *layerCnt;  // k_layer_index
-  u32 pktStride;
-  u32 waveBase;  // schedule index of this launch's first wave
-  u32 waveEnd;   // schedule index after this launch's last wave
-  u32 perWave;   // DownTracks (schedule slots) per wave: 1 for long batches, more for short ticks
-  // dependency descriptor (F_DD DownTracks)
-  const DDPkt *ddPkts;
-  const DDStruct *ddStructs;
-  DDState *ddState;
-  u8 *ddArena;
-  u64 *ddUsed;
-  u64 ddCap;
-  const u16 *ddSpill;
-  // capacities (checked builds test device-computed indices against them)
-  u32 maxDts, maxTracks, npkts, nev;
-};
-
 struct SsEnt;
 // One wave per (track, <=64 DownTracks): the packet loop is wave-uniform, so
 // packet descriptors come through the scalar cache and every branch on packet
@@ -3603,32 +3552,6 @@ constexpr int PRE_MAX_DD = 352;
 #endif
 constexpr int EMIT_U = LKF_EMIT_U;
 
-
-struct EmitArgs {
-  const u32 *perm;      // output position -> DownTrack (track-major order)
-  const u64 *recBase;   // [position] exclusive scan of forwarded counts
-  const u64 *byteBase;  // [position] exclusive scan of output bytes
-  const u32 *gFirst;    // [group] position owning record group*EMIT_G
-  const u64 *slotBase;
-  const u64 *totals;    // [0] records, [1] bytes
-  const FwdRec *recs;
-  const FwdBase *fbase;  // per DownTrack: the base its records' 32-bit SN / TS widen against
-  const FwdBase *wide;   // per tuple slot: a T_WIDE record's full SN / TS
-  const lkf_pkt *pkts;
-  const u8 *arena;
-  const DevDT *dts;
-  u32 ndts;
-  lkf_out *out;
-  u8 *outArena;
-  u64 outCap, outByteCap;
-  u32 *err;
-  const u8 *ddArena;  // marshalled DD bytes of T_DD tuples
-  const u32 *twccBase;  // per DownTrack: the batch's first transport-wide sequence number (k_twcc_base)
-  // capacities (checked builds test device-computed indices against them)
-  u32 maxDts, npkts;
-  u64 tupleCap, arenaLen, ddCap, gCap;
-};
-
 __device__ __forceinline__ u32 align_byte(u32 hi, u32 lo, u32 sh) {
   return __builtin_amdgcn_alignbyte(hi, lo, sh);
 }
@@ -3865,7 +3788,7 @@ __device__ __forceinline__ int emit_marshal(const EmitArgs &A, const EmitRec &q,
 // size) 651 MB per configs[1] batch for 319 MB of payload.  Extra LDS per
 // workgroup bounds residency (A/B in one GPU call, profiles/r6_ab_runs.txt):
 // 12 per CU -> 524 MB, 8 -> 449 MB, 4 -> 339 MB.  The cap is reserved at
-// launch as dynamic LDS (EmitLaunch.ldsPad): it pays where emit shares the GPU
+// launch as dynamic LDS (launch_emit's ldsPad): it pays where emit shares the GPU
 // with an ingest chain, and costs where emit has it to itself (§4 DESIGN.md).
 template <int PRE>
 __global__ void __launch_bounds__(EMIT_T) k_emit(EmitArgs A) {
@@ -4497,27 +4420,6 @@ __device__ int vp8_padding(Lane &L, bool newPicture, u64 &out) {
   return vp8_marshal(0x10, picUsed, pid > 127, pid, tl0Used, tl0, tidUsed, 0, true, keyUsed, key, hs, out);
 }
 
-struct PadArgs {
-  int blank;
-  u32 n;
-  const lkf_pad_req *reqs;
-  i64 nowNs;
-  DTHot *hot;
-  const DevDT *dts;
-  const DevTrack *tracks;
-  RangeEntry *rm;
-  SeqMeta *seq;
-  u32 seqSize;
-  u8 *srm;
-  u64 srmStride;
-  u32 srmCap;
-  DTCum *dtCum;
-  const u64 *recOff, *byteOff;
-  lkf_out *out;
-  u8 *arena;
-  u32 *cnt, *bytes;
-};
-
 // RTP header of a padding / blank packet (pion Header.MarshalTo; pacer
 // writeRTPHeaderExtensions pacer/base.go:71-100: abs-send-time placeholder)
 __device__ __forceinline__ u32 pad_hdr_len(const DevDT &dt) {
@@ -4692,30 +4594,9 @@ __global__ void __launch_bounds__(64) k_pad(PadArgs A) {
   }
 }
 
-hipError_t launch_pad(hipStream_t s, const PadLaunch &a) {
+hipError_t launch_pad(hipStream_t s, const PadArgs &a) {
   if (!a.n) return hipSuccess;
-  PadArgs A;
-  A.blank = a.blank;
-  A.n = a.n;
-  A.reqs = a.reqs;
-  A.nowNs = a.nowNs;
-  A.hot = a.hot;
-  A.dts = a.dts;
-  A.tracks = a.tracks;
-  A.rm = a.rm;
-  A.seq = a.seq;
-  A.seqSize = a.seqSize;
-  A.srm = a.srm;
-  A.srmStride = a.srmStride;
-  A.srmCap = a.srmCap;
-  A.dtCum = a.dtCum;
-  A.recOff = a.recOff;
-  A.byteOff = a.byteOff;
-  A.out = a.out;
-  A.arena = a.arena;
-  A.cnt = a.cnt;
-  A.bytes = a.bytes;
-  hipLaunchKernelGGL(k_pad, dim3(a.n), dim3(64), 0, s, A);
+  hipLaunchKernelGGL(k_pad, dim3(a.n), dim3(64), 0, s, a);
   return hipGetLastError();
 }
 
@@ -5092,70 +4973,22 @@ hipError_t launch_scan(hipStream_t s, int mode, const DevDT *dts, const u32 *tBe
 
 size_t scan_state_words(uint32_t maxN) { return kScanStHead + 8 * size_t(nblk(maxN ? maxN : 1, SCAN_TILE)); }
 
-hipError_t launch_decide(hipStream_t s, const DecideLaunch &a) {
-  if (a.nlanes == 0) return hipSuccess;
-  DecideArgs A;
-  A.sched = a.sched;
-  A.waveTrack = a.waveTrack;
-  A.nlanes = a.nlanes;
-  A.hot = a.hot;
-  A.dts = a.dts;
-  A.tracks = a.tracks;
-  A.rm = a.rm;
-  A.vc = a.vc;
-  A.seq = a.seq;
-  A.seqSize = a.seqSize;
-  A.srm = a.srm;
-  A.srmStride = a.srmStride;
-  A.srmCap = a.srmCap;
-  A.pkts = a.pkts;
-  A.tBegin = a.tBegin;
-  A.tEnd = a.tEnd;
-  A.slotBase = a.slotBase;
-  A.recs = a.recs;
-  A.fbase = a.fbase;
-  A.wide = a.wide;
-  A.tupleCap = a.tupleCap;
-  A.err = a.err;
-  A.ss = a.ss;
-  A.ssRing = a.ssRing;
-  A.ssGap = a.ssGap;
-  A.dtOffs = a.dtOffs;
-  A.events = a.events;
-  A.evOff = a.evOff;
-  A.fwdCnt = a.fwdCnt;
-  A.layerList = a.layerList;
-  A.layerBefore = a.layerBefore;
-  A.layerCnt = a.layerCnt;
-  A.pktStride = a.pktStride;
-  A.fwdBytes = a.fwdBytes;
-  A.dtCum = a.dtCum;
-  A.stats = a.stats;
-  A.ddPkts = a.ddPkts;
-  A.ddStructs = a.ddStructs;
-  A.ddState = a.ddState;
-  A.ddArena = a.ddArena;
-  A.ddUsed = a.ddUsed;
-  A.ddSpill = a.ddSpill;
-  A.ddCap = a.ddCap;
-  A.maxDts = a.maxDts;
-  A.maxTracks = a.maxTracks;
-  A.npkts = a.npkts;
-  A.nev = a.nev;
+hipError_t launch_decide(hipStream_t s, DecideArgs A, u32 ddLanes) {
+  if (A.nlanes == 0) return hipSuccess;
   // DownTracks of the dependency-descriptor selector run in their own
   // instantiation (the last ddLanes waves of the schedule)
   // Each part is a multiple of 8 slots (per-XCD lists of equal length);
   // a workgroup takes perWave consecutive slots of one XCD's list.
-  const u32 nPlain = a.nlanes - a.ddLanes;
-  const u32 K = a.perWave ? (a.perWave < kDecideMaxK ? a.perWave : kDecideMaxK) : 1;
+  const u32 nPlain = A.nlanes - ddLanes;
+  const u32 K = A.perWave ? (A.perWave < kDecideMaxK ? A.perWave : kDecideMaxK) : 1;
   A.perWave = K;
   auto blocks = [K](u32 lanes) { return (lanes / 8 + K - 1) / K * 8; };
   A.waveBase = 0;
   A.waveEnd = nPlain;
-  if (nPlain) hipLaunchKernelGGL(k_decide_dt<false>, dim3(blocks(nPlain)), dim3(64), 0, s, A, a.pkts);
+  if (nPlain) hipLaunchKernelGGL(k_decide_dt<false>, dim3(blocks(nPlain)), dim3(64), 0, s, A, A.pkts);
   A.waveBase = nPlain;
-  A.waveEnd = a.nlanes;
-  if (a.ddLanes) hipLaunchKernelGGL(k_decide_dt<true>, dim3(blocks(a.ddLanes)), dim3(64), 0, s, A, a.pkts);
+  A.waveEnd = A.nlanes;
+  if (ddLanes) hipLaunchKernelGGL(k_decide_dt<true>, dim3(blocks(ddLanes)), dim3(64), 0, s, A, A.pkts);
   return hipGetLastError();
 }
 
@@ -5279,68 +5112,34 @@ hipError_t launch_twcc_stamp(hipStream_t s, const DevDT *dts, uint32_t *ctrD, ui
   return hipGetLastError();
 }
 
-static EmitArgs emit_args(const EmitLaunch &a);
-
-hipError_t launch_emit(hipStream_t s, const EmitLaunch &a) {
-  const EmitArgs A = emit_args(a);
+hipError_t launch_emit(hipStream_t s, const EmitArgs &a, u32 grid, u32 ldsPad) {
   if (a.ddArena)
-    hipLaunchKernelGGL(k_emit<PRE_MAX_DD>, dim3(a.grid), dim3(EMIT_T), 0, s, A);
+    hipLaunchKernelGGL(k_emit<PRE_MAX_DD>, dim3(grid), dim3(EMIT_T), 0, s, a);
   else
-    hipLaunchKernelGGL(k_emit<PRE_MAX>, dim3(a.grid), dim3(EMIT_T), a.ldsPad, s, A);
+    hipLaunchKernelGGL(k_emit<PRE_MAX>, dim3(grid), dim3(EMIT_T), ldsPad, s, a);
   return hipGetLastError();
 }
 
 // The prefix egress's three launches (length pass, group-base scan, write
 // pass), in stream order.
-hipError_t launch_emit_prefix(hipStream_t s, const EmitLaunch &a, const EmitPrefixLaunch &x) {
+hipError_t launch_emit_prefix(hipStream_t s, const EmitArgs &a, u32 grid, const EmitPrefixLaunch &x) {
   EmitPreArgs P;
-  P.e = emit_args(a);
+  P.e = a;
   P.e.out = nullptr;
   P.pre = x.pre;
   P.gSum = x.gSum;
   P.gBase = x.gBase;
   P.preTotal = x.total;
   if (a.ddArena)
-    hipLaunchKernelGGL(k_emit_prelen<PRE_MAX_DD>, dim3(a.grid), dim3(EMIT_T), 0, s, P);
+    hipLaunchKernelGGL(k_emit_prelen<PRE_MAX_DD>, dim3(grid), dim3(EMIT_T), 0, s, P);
   else
-    hipLaunchKernelGGL(k_emit_prelen<PRE_MAX>, dim3(a.grid), dim3(EMIT_T), 0, s, P);
+    hipLaunchKernelGGL(k_emit_prelen<PRE_MAX>, dim3(grid), dim3(EMIT_T), 0, s, P);
   hipLaunchKernelGGL(k_emit_prescan, dim3(1), dim3(PRESCAN_T), 0, s, P);
   if (a.ddArena)
-    hipLaunchKernelGGL(k_emit_prefix<PRE_MAX_DD>, dim3(a.grid), dim3(EMIT_T), 0, s, P);
+    hipLaunchKernelGGL(k_emit_prefix<PRE_MAX_DD>, dim3(grid), dim3(EMIT_T), 0, s, P);
   else
-    hipLaunchKernelGGL(k_emit_prefix<PRE_MAX>, dim3(a.grid), dim3(EMIT_T), 0, s, P);
+    hipLaunchKernelGGL(k_emit_prefix<PRE_MAX>, dim3(grid), dim3(EMIT_T), 0, s, P);
   return hipGetLastError();
-}
-
-static EmitArgs emit_args(const EmitLaunch &a) {
-  EmitArgs A;
-  A.perm = a.perm;
-  A.recBase = a.recBase;
-  A.byteBase = a.byteBase;
-  A.gFirst = a.gFirst;
-  A.slotBase = a.slotBase;
-  A.totals = a.totals;
-  A.recs = a.recs;
-  A.fbase = a.fbase;
-  A.wide = a.wide;
-  A.pkts = a.pkts;
-  A.arena = a.arena;
-  A.dts = a.dts;
-  A.ndts = a.ndts;
-  A.out = a.out;
-  A.outArena = a.outArena;
-  A.outCap = a.outCap;
-  A.outByteCap = a.outByteCap;
-  A.err = a.err;
-  A.ddArena = a.ddArena;
-  A.twccBase = a.twccBase;
-  A.maxDts = a.maxDts;
-  A.npkts = a.npkts;
-  A.tupleCap = a.tupleCap;
-  A.arenaLen = a.arenaLen;
-  A.ddCap = a.ddCap;
-  A.gCap = a.gCap;
-  return A;
 }
 
 // The run's first kernel: pulls the page-locked staging buffer (the host's
@@ -5352,8 +5151,8 @@ __global__ void k_h2d(const u8 *__restrict__ stage, RunDesc *__restrict__ dDesc,
   const RunDesc *h = reinterpret_cast<const RunDesc *>(stage);
   const u32 nev = h->nev, cap = h->evCap;
   const u64 nA = u64(nev) * (sizeof(DevEvent) / 4), nB = nev;
-  const u32 *sA = reinterpret_cast<const u32 *>(stage + sizeof(RunDesc));
-  const u32 *sB = reinterpret_cast<const u32 *>(stage + sizeof(RunDesc) + u64(cap) * sizeof(DevEvent));
+  const u32 *sA = reinterpret_cast<const u32 *>(stage + stage_ev_off(cap));
+  const u32 *sB = reinterpret_cast<const u32 *>(stage + stage_lane_off(cap));
   u32 *dA = reinterpret_cast<u32 *>(dEv);
   const u64 stride = u64(gridDim.x) * blockDim.x;
   const u64 t = u64(blockIdx.x) * blockDim.x + threadIdx.x;

@@ -525,4 +525,17 @@ struct DevKey {  // 16 B
 };
 static_assert(sizeof(DevKey) == 16, "DevKey is 16 B");
 
+// A run's staging buffer: [RunDesc][cap x DevEvent][cap x u32 lane][cap x DevKey],
+// cap = RunDesc.evCap (a multiple of 4 ops: the keys stay 16-B aligned).
+__host__ __device__ constexpr uint64_t stage_ev_off(uint32_t) { return sizeof(RunDesc); }
+__host__ __device__ constexpr uint64_t stage_lane_off(uint32_t cap) {
+  return sizeof(RunDesc) + uint64_t(cap) * sizeof(DevEvent);
+}
+__host__ __device__ constexpr uint64_t stage_key_off(uint32_t cap) {
+  return sizeof(RunDesc) + uint64_t(cap) * (sizeof(DevEvent) + 4);
+}
+__host__ __device__ constexpr uint64_t stage_bytes(uint32_t cap) {
+  return sizeof(RunDesc) + uint64_t(cap) * (sizeof(DevEvent) + 4 + sizeof(DevKey));
+}
+
 }  // namespace lkf

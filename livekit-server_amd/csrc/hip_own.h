@@ -64,6 +64,13 @@ struct GraphExec : Owned<hipGraphExec_t> {
   void reset() { (void)destroy(); }
 };
 
+// A stage of lkf_run captured as a graph, with the topology epoch it was
+// captured for (epoch 0: none, re-captured by its next use).
+struct StageGraph {
+  GraphExec exec;
+  uint64_t epoch = 0;
+};
+
 // Page-locked, CPU-cached host staging (aligned_alloc + hipHostRegister) with
 // its device mapping.
 struct StagePair {

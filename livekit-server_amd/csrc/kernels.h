@@ -8,12 +8,12 @@
 
 namespace lkf {
 
-struct DecideLaunch {
-  const uint32_t *sched;    // wave -> DownTrack (per-XCD interleaved schedule)
-  const uint32_t *waveTrack;
-  uint32_t nlanes;          // waves
-  uint32_t ddLanes;         // the last ddLanes waves: DownTracks of the DD selector (k_decide_dt<true>)
-  uint32_t perWave;         // DownTracks per wave (1..64; 0 = 1)
+// k_decide_dt<*> arguments: the kernarg struct itself.  perWave, waveBase and
+// waveEnd are written by launch_decide (the engine sets perWave as its request).
+struct DecideArgs {
+  const uint32_t *sched;      // lane -> DownTrack (0xffffffff = idle lane; per-XCD interleaved schedule)
+  const uint32_t *waveTrack;  // wave -> track (every lane of a wave serves one track)
+  uint32_t nlanes;            // waves
   DTHot *hot;
   const DevDT *dts;
   const DevTrack *tracks;
@@ -21,29 +21,32 @@ struct DecideLaunch {
   VP8Cold *vc;
   SeqMeta *seq;
   uint32_t seqSize;
-  uint8_t *srm;  // SeqRM regions (the sequencer RangeMaps of padding exclusions)
+  uint8_t *srm;  // SeqRM regions (the sequencer RangeMaps of padding exclusions; stride srmStride), read with F_SEQ_RM
   uint64_t srmStride;
   uint32_t srmCap;
   const lkf_pkt *pkts;
   const uint32_t *tBegin, *tEnd;
   const uint64_t *slotBase;
-  FwdRec *recs;     // forwarded records at slotBase[dt] + j
-  FwdBase *fbase;   // per DownTrack: the base of its records' 32-bit SN / TS
-  FwdBase *wide;    // per tuple slot: the full SN / TS of a T_WIDE record
+  FwdRec *recs;    // forwarded records at slotBase[dt] + j
+  FwdBase *fbase;  // per DownTrack: its first forwarded record's munged SN / TS (FwdRec widening)
+  FwdBase *wide;   // per tuple slot: the full SN / TS of a T_WIDE record
   uint64_t tupleCap;
   uint32_t *err;
-  SenderStats *ss;  // RTPStatsSender per DownTrack, updated by decide (snInfo ring, gap histogram)
+  SenderStats *ss;  // RTPStatsSender per DownTrack, updated by decide (+ snInfo ring, gap histogram)
   uint32_t *ssRing, *ssGap;
   uint32_t *dtOffs;  // per DownTrack kDTOffsWords: the reference-layer offsets its Forwarder reads
   const DevEvent *events;
-  const uint32_t *evOff;
+  const uint32_t *evOff;  // per lane [evOff[l], evOff[l+1])
   uint32_t *fwdCnt;
   uint64_t *fwdBytes;
-  DTCum *dtCum;
-  uint64_t *stats;
-  const uint32_t *layerList, *layerBefore, *layerCnt;  // launch_layer_index outputs
+  DTCum *dtCum;     // per DownTrack totals (sendingPacket counters)
+  uint64_t *stats;  // lkf_stats as u64[15]
+  const uint32_t *layerList, *layerBefore, *layerCnt;  // launch_layer_index (k_layer_index) outputs
   uint32_t pktStride;                                  // max_batch_pkts
-  // dependency descriptor (nullptr when no track uses the DD selector)
+  uint32_t waveBase;  // schedule index of this launch's first wave
+  uint32_t waveEnd;   // schedule index after this launch's last wave
+  uint32_t perWave;   // DownTracks (schedule slots) per wave: 1 for long batches, more for short ticks (0 = 1)
+  // dependency descriptor (F_DD DownTracks; nullptr when no track uses the DD selector)
   const DDPkt *ddPkts;
   const DDStruct *ddStructs;
   DDState *ddState;
@@ -51,17 +54,21 @@ struct DecideLaunch {
   uint64_t *ddUsed;
   uint64_t ddCap;
   const uint16_t *ddSpill;  // k_dd_decode's spilled frame-diff lists
-  // capacities (tested in -DLKF_CHECKED=1 builds)
+  // capacities (-DLKF_CHECKED=1 builds test device-computed indices against them)
   uint32_t maxDts, maxTracks, npkts, nev;
 };
 
-struct EmitLaunch {
-  const uint32_t *perm;  // output position -> DownTrack
-  const uint64_t *recBase, *byteBase, *slotBase, *totals;  // recBase/byteBase by position
-  const uint32_t *gFirst;  // [group] position owning record 64*group (k_scan_down mode 1)
+// k_emit<*> arguments (and, inside EmitPreArgs, the prefix egress kernels')
+struct EmitArgs {
+  const uint32_t *perm;      // output position -> DownTrack (track-major order)
+  const uint64_t *recBase;   // [position] exclusive scan of forwarded counts
+  const uint64_t *byteBase;  // [position] exclusive scan of output bytes
+  const uint32_t *gFirst;    // [group] position owning record 64*group (k_scan_down mode 1)
+  const uint64_t *slotBase;
+  const uint64_t *totals;    // [0] records, [1] bytes
   const FwdRec *recs;
-  const FwdBase *fbase;
-  const FwdBase *wide;
+  const FwdBase *fbase;  // per DownTrack: the base its records' 32-bit SN / TS widen against
+  const FwdBase *wide;   // per tuple slot: a T_WIDE record's full SN / TS
   const lkf_pkt *pkts;
   const uint8_t *arena;
   const DevDT *dts;
@@ -70,11 +77,9 @@ struct EmitLaunch {
   uint8_t *outArena;
   uint64_t outCap, outByteCap;
   uint32_t *err;
-  uint32_t grid;
-  const uint8_t *ddArena;  // non-null: batches with DD tracks (k_emit<PRE_MAX_DD>)
-  const uint32_t *twccBase = nullptr;  // per DownTrack transport-cc base of the batch (DownTracks with extTcc)
-  uint32_t ldsPad = 0;  // dynamic LDS reserved per workgroup (caps residency; the plain instantiation)
-  // capacities (tested in -DLKF_CHECKED=1 builds)
+  const uint8_t *ddArena;  // marshalled DD bytes of T_DD tuples; non-null: batches with DD tracks (k_emit<PRE_MAX_DD>)
+  const uint32_t *twccBase;  // per DownTrack: the batch's first transport-wide sequence number (k_twcc_base; DownTracks with extTcc)
+  // capacities (-DLKF_CHECKED=1 builds test device-computed indices against them)
   uint32_t maxDts, npkts;
   uint64_t tupleCap, arenaLen, ddCap, gCap;
 };
@@ -255,11 +260,13 @@ struct RoomPackLaunch {
 };
 // (the ranking's pack on spkStream, the totals' pack on bweStream)
 hipError_t launch_room_pack(hipStream_t spkStream, hipStream_t bweStream, const RoomPackLaunch &a);
-hipError_t launch_decide(hipStream_t s, const DecideLaunch &a);
+// ddLanes: the last ddLanes waves of the schedule are DownTracks of the DD selector (k_decide_dt<true>)
+hipError_t launch_decide(hipStream_t s, DecideArgs a, uint32_t ddLanes);
 hipError_t launch_layer_index(hipStream_t s, const RunDesc *desc, const uint32_t *tBegin, const uint32_t *tEnd,
                               uint32_t ntracks, uint32_t stride, uint32_t *list, uint32_t *before, uint32_t *cnt,
                               uint64_t *zero2 = nullptr);
-hipError_t launch_emit(hipStream_t s, const EmitLaunch &a);
+// grid: workgroups; ldsPad: dynamic LDS reserved per workgroup (caps residency; the plain instantiation)
+hipError_t launch_emit(hipStream_t s, const EmitArgs &a, uint32_t grid, uint32_t ldsPad);
 // Prefix egress (LKF_EGRESS_PREFIX) of the same batch: a.out is unused and
 // a.outArena takes the prefixes; ldsPad does not apply (no payload re-read).
 struct EmitPrefixLaunch {
@@ -268,7 +275,7 @@ struct EmitPrefixLaunch {
   uint64_t *gBase;   // a.gCap group bases (their exclusive scan)
   uint64_t *total;   // one word: the batch's prefix arena bytes
 };
-hipError_t launch_emit_prefix(hipStream_t s, const EmitLaunch &a, const EmitPrefixLaunch &x);
+hipError_t launch_emit_prefix(hipStream_t s, const EmitArgs &a, uint32_t grid, const EmitPrefixLaunch &x);
 hipError_t launch_dd_decode(hipStream_t s, const RunDesc *desc, const uint32_t *tBegin, const uint32_t *tEnd,
                             const DevTrack *tracks, uint32_t ntracks, DDStruct *structs, DDTrack *ddTracks, DDPkt *out,
                             uint32_t *err, const uint32_t *trackDDTrk, DDTrkState *ddTrk, uint16_t *spill,
@@ -333,7 +340,7 @@ hipError_t launch_seq_lookup(hipStream_t s, DTHot *hot, SeqMeta *seq, uint32_t s
                              const uint16_t *sns, uint32_t n, int64_t nowMs, lkf_seq_meta *out, uint32_t *nOut);
 
 // ---- padding / blank frames (WritePaddingRTP, writeBlankFrameRTP) ----
-struct PadLaunch {
+struct PadArgs {  // k_pad arguments
   int blank;  // 0: WritePaddingRTP requests, 1: one writeBlankFrameRTP tick per request
   uint32_t n;
   const lkf_pad_req *reqs;
@@ -354,7 +361,7 @@ struct PadLaunch {
   uint32_t *cnt;    // per request: packets written
   uint32_t *bytes;  // per request: WritePaddingRTP's return value (blank: bytes counted by sendingPacket)
 };
-hipError_t launch_pad(hipStream_t s, const PadLaunch &a);
+hipError_t launch_pad(hipStream_t s, const PadArgs &a);
 // allocation control kernels (alloc_kernels.hip); `last` is the stored
 // lastAllocation per DownTrack; `out` is lkf_allocation[n] or, for
 // ALLOC_TRANSITION, lkf_video_transition[n]; `capacity` only for NEXT_HIGHER
