@@ -615,7 +615,8 @@ int lkf_downtrack_summaries(lkf_engine *e, lkf_dt_summary *out, uint32_t cap, ui
  * payload); packet time for the last three = the call's now_ns (lkf_rtx_emit:
  * that of the last lkf_rtx_lookup), the reference's time.Now().  Key frames
  * forwarded: UpdateKeyFrame.  Not kept: startTime / endTime / lastKeyFrame
- * (wall clock) and the RTCP report snapshots.  Waits for queued runs. */
+ * (wall clock); the RTCP half (reports, snapshots) is lkf_sender_rtcp below.
+ * Waits for queued runs. */
 typedef struct lkf_sender_stats {
   uint64_t ext_start_sn, ext_highest_sn, ext_start_ts, ext_highest_ts;
   int64_t first_time_ns, highest_time_ns;
@@ -633,8 +634,150 @@ int lkf_sender_stats_get(lkf_engine *e, int32_t dt, lkf_sender_stats *out);
 int lkf_sender_sninfo(lkf_engine *e, int32_t dt, uint64_t esn, uint32_t *out);
 /* RTPStatsSender.Seed (rtpstats_sender.go:173-201; DownTrack.SeedState
  * downtrack.go:1051-1055 on transceiver reuse): dt takes from_dt's statistics,
- * gap histogram and snInfo ring if from_dt's are initialized (clock rate kept). */
+ * gap histogram and snInfo ring if from_dt's are initialized (clock rate kept),
+ * and the RTCP state below (lkf_sender_rtcp: all of it but end_time_ns and the
+ * three log counters, which Seed does not copy). */
 int lkf_sender_stats_seed(lkf_engine *e, int32_t dt, int32_t from_dt);
+
+/* ---- the DownTrack RTCP loop (the RTCP half of buffer.RTPStatsSender) ---- *
+ * Three batched calls over the per-DownTrack state lkf_sender_rtcp, replacing
+ * three Go call sites:
+ *   DownTrack.handleRTCP -> UpdateFromReceiverReport, UpdateNack / UpdatePli /
+ *     UpdateFir (downtrack.go:1516-1567)            lkf_rtcp_feedback
+ *   DownTrack.CreateSenderReport -> GetRtcpSenderReport
+ *     (downtrack.go:1295-1305)                      lkf_rtcp_sender_reports
+ *   DownTrack.DeltaInfoSender (downtrack.go:1794)   lkf_sender_delta_info
+ * Each call waits for queued runs, runs on the stream that owns the sender
+ * statistics and copies its results back before it returns.  Times are the
+ * engine's virtual clock: now_ns (read as Unix ns) is the reference's
+ * time.Now(), time.Since(x) is now_ns - x; 0 is the zero time.
+ *
+ * startTime, which the engine does not keep, is lkf_sender_stats.first_time_ns
+ * (the reference sets both at the first packet).  end_time_ns != 0: the handle
+ * was removed (lkf_remove_downtrack / lkf_remove_track); it is a mark, not a
+ * time.  One senderSnapshot per DownTrack (DownTrack takes one
+ * NewSenderSnapshotId, downtrack.go:319); it starts as the zero value with
+ * is_valid 0 and is first initialized by lkf_sender_delta_info
+ * (getAndResetSenderSnapshot).  NOTE: the reference also initializes the
+ * snapshots taken before the first packet when that packet arrives
+ * (rtpstats_sender.go:268-270); the engine's per-packet Update does not, so
+ * the reports before the first lkf_sender_delta_info aggregate from sequence
+ * number 1 into a snapshot that call then replaces.
+ * Out of scope: the base-class snapshots / DeltaInfo(snapshotID) and the
+ * wall-clock UpdatePliTime / lastPli.
+ *
+ * mediatransportutil (v0.0.0-20231213075826-cccbf2b93d3f) is not part of the
+ * reference tree; these three definitions are what the engine computes
+ * (parity unpinned):
+ *   ToNtpTime(unix_ns): n = unix_ns + 2208988800e9 (u64); sec = n / 1e9;
+ *     f = (n - sec * 1e9) << 32; frac = f / 1e9, + 1 if f % 1e9 >= 5e8;
+ *     sec << 32 | frac.
+ *   NtpTime.Time(): Duration() from the same epoch: (t >> 32) * 1e9 +
+ *     (((t & 0xffffffff) * 1e9) >> 32), + 1 if the low 32 bits of that product
+ *     are >= 0x80000000.
+ *   GetRttMs(rr, lastSRNTP, lastSentAt): no RTT if rr.LastSenderReport == 0,
+ *     or lastSRNTP != 0 and uint32(lastSRNTP >> 16) != rr.LastSenderReport;
+ *     else nowNTP = ToNtpTime(lastSRNTP.Time() + (now_ns - lastSentAt)),
+ *     now32 = uint32(nowNTP >> 16); no RTT if now32 < LSR + DLSR (u32); else
+ *     uint32(ceil(double(now32 - LSR - DLSR) * 1000.0 / 65536.0)).
+ * One divergence: getIntervalStats loops esn != extEndExclusive; with
+ * extEndExclusive < extStartInclusive the Go loop runs about 2^64 times, the
+ * engine treats that interval as empty. */
+typedef struct lkf_rtcp_sr_data { /* RTCPSenderReportData; RTPTimestamp = (uint32_t)rtp_ext */
+  uint64_t ntp, rtp_ext;
+  int64_t at_ns;
+  uint32_t valid, reserved; /* valid 0: nil */
+} lkf_rtcp_sr_data;
+typedef struct lkf_interval_stats { /* intervalStats rtpstats_sender.go:50-61 */
+  uint64_t packets, bytes, header_bytes, packets_padding, bytes_padding, header_bytes_padding;
+  uint64_t packets_lost, packets_out_of_order, packets_not_found;
+  uint32_t frames, reserved;
+} lkf_interval_stats;
+typedef struct lkf_sender_snapshot { /* senderSnapshot rtpstats_sender.go:101-135 */
+  uint32_t is_valid, frames;
+  int64_t start_time_ns;
+  uint64_t ext_start_sn, bytes, header_bytes, packets_padding, bytes_padding, header_bytes_padding;
+  uint64_t packets_duplicate, bytes_duplicate, header_bytes_duplicate, packets_out_of_order, packets_lost_feed,
+      packets_lost;
+  uint32_t nacks, plis, firs, max_rtt;
+  double max_jitter_feed, max_jitter;
+  uint64_t ext_last_rr_sn;
+  lkf_interval_stats interval_stats;
+} lkf_sender_snapshot;
+typedef struct lkf_sender_rtcp { /* 384 B */
+  uint64_t ext_highest_sn_from_rr;
+  int64_t last_rr_time_ns;
+  uint64_t packets_lost_from_rr;
+  double jitter_from_rr, max_jitter_from_rr;
+  int64_t end_time_ns;
+  uint32_t last_rr_last_sequence_number, last_rr_total_lost; /* lastRR */
+  uint32_t rtt, max_rtt, nacks, plis, firs;
+  uint32_t clock_skew_count, out_of_order_sender_report_count, metadata_cache_overflow_count;
+  lkf_rtcp_sr_data sr_first, sr_newest;
+  lkf_sender_snapshot snapshot;
+} lkf_sender_rtcp;
+/* The whole RTCP state of one DownTrack (tests; what lkf_sender_stats_seed
+ * copies besides the per-packet statistics: everything RTPStatsSender.Seed
+ * copies, i.e. all of it but end_time_ns and the three log counters). */
+int lkf_sender_rtcp_get(lkf_engine *e, int32_t dt, lkf_sender_rtcp *out);
+
+/* One DownTrack's share of one compound RTCP packet: its reception report
+ * (LKF_FB_HAS_RR; the rtcp.ReceptionReport fields) and the NACKed sequence
+ * numbers, PLIs and FIRs counted in that packet (added after the report, as
+ * handleRTCP does; not added once the handle was removed). */
+#define LKF_FB_HAS_RR 0x1
+typedef struct lkf_rtcp_fb { /* 48 B */
+  int32_t dt;
+  uint32_t flags;
+  uint32_t last_sequence_number, total_lost, jitter, last_sender_report, delay;
+  uint32_t nacks, plis, firs;
+  uint8_t fraction_lost;
+  uint8_t reserved[7];
+} lkf_rtcp_fb;
+#define LKF_FB_RTT_CHANGED 0x1    /* isRttChanged: the host forwards rtt_ms to sequencer.setRTT */
+#define LKF_FB_IGNORED 0x2        /* uninitialized, closed, before the start SN, or out of order */
+#define LKF_FB_CACHE_OVERFLOW 0x4 /* packetsNotFound != 0 in this report's interval */
+typedef struct lkf_rtcp_fb_result {
+  uint32_t rtt_ms; /* UpdateFromReceiverReport's rtt (0: none) */
+  uint32_t flags;
+} lkf_rtcp_fb_result;
+/* Entries grouped by DownTrack (a DownTrack's entries contiguous, applied in
+ * list order; LKF_EORDER otherwise).  out[i] answers in[i]. */
+int lkf_rtcp_feedback(lkf_engine *e, const lkf_rtcp_fb *in, uint32_t n, int64_t now_ns, lkf_rtcp_fb_result *out);
+
+/* calculated_clock_rate: StreamTrackerManager.GetCalculatedClockRate of the
+ * DownTrack's clock layer, which the host owns (0: none). */
+typedef struct lkf_rtcp_sr_req {
+  int32_t dt;
+  uint32_t calculated_clock_rate;
+} lkf_rtcp_sr_req;
+#define LKF_SR_VALID 0x1      /* 0: the reference returns nil (no packet sent yet) */
+#define LKF_SR_CLOCK_SKEW 0x2 /* the clock-skew branch counted this report */
+#define LKF_SR_REPAIRED 0x4   /* behind the last report: rebuilt from it and the NTP difference */
+typedef struct lkf_rtcp_sr { /* 40 B */
+  int32_t dt;
+  uint32_t flags;
+  uint64_t ntp, rtp_ext;
+  uint32_t rtp, packet_count, octet_count, reserved;
+} lkf_rtcp_sr;
+/* One sender report per request (each DownTrack at most once; LKF_EORDER
+ * otherwise).  wire28 (may be NULL): 28 bytes per
+ * request, the marshalled rtcp.SenderReport (V=2, P=0, RC=0, PT=200, length 6,
+ * SSRC, NTP, RTP, packet count, octet count; zeros when not VALID). */
+int lkf_rtcp_sender_reports(lkf_engine *e, const lkf_rtcp_sr_req *req, uint32_t n, int64_t now_ns, lkf_rtcp_sr *out,
+                            uint8_t *wire28);
+
+typedef struct lkf_rtp_delta_info { /* RTPDeltaInfo rtpstats_sender.go:786-807; 120 B */
+  int64_t start_time_ns, duration_ns;
+  uint64_t bytes, header_bytes, bytes_duplicate, header_bytes_duplicate, bytes_padding, header_bytes_padding;
+  double jitter_max;
+  uint32_t valid; /* 0: the reference returns nil */
+  uint32_t packets, packets_duplicate, packets_padding, packets_lost, packets_missing, packets_out_of_order, frames;
+  uint32_t rtt_max, nacks, plis, firs;
+} lkf_rtp_delta_info;
+/* DeltaInfoSender for each listed DownTrack (each at most once; LKF_EORDER
+ * otherwise); resets the snapshot as the reference does. */
+int lkf_sender_delta_info(lkf_engine *e, const int32_t *dts, uint32_t n, lkf_rtp_delta_info *out);
 
 /* ---- sequencer (sequencer.getExtPacketMetas sequencer.go:263, for RTX) --- */
 typedef struct lkf_seq_meta {

@@ -307,6 +307,40 @@ class Engine:
     def sync(self):
         self._chk(self.lib.lkf_sync(self.h), "sync")
 
+    def rtcp_feedback(self, entries, now_ns):
+        """lkf_rtcp_feedback: `entries` an abi.RTCP_FB_DTYPE array grouped by
+        DownTrack -> abi.RTCP_FB_RESULT_DTYPE array (one row per entry)."""
+        ent = np.ascontiguousarray(entries, dtype=abi.RTCP_FB_DTYPE)
+        out = np.zeros(len(ent), dtype=abi.RTCP_FB_RESULT_DTYPE)
+        self._chk(self.api["rtcp_feedback"](self.h, ent.ctypes.data, len(ent), now_ns, out.ctypes.data),
+                  "rtcp_feedback")
+        return out
+
+    def rtcp_sender_reports(self, reqs, now_ns, wire=False):
+        """lkf_rtcp_sender_reports: `reqs` an abi.RTCP_SR_REQ_DTYPE array ->
+        abi.RTCP_SR_DTYPE array, and with wire=True also a uint8 [n, 28] array
+        of the marshalled packets."""
+        rq = np.ascontiguousarray(reqs, dtype=abi.RTCP_SR_REQ_DTYPE)
+        out = np.zeros(len(rq), dtype=abi.RTCP_SR_DTYPE)
+        w = np.zeros((len(rq), 28), dtype=np.uint8) if wire else None
+        self._chk(self.api["rtcp_sender_reports"](self.h, rq.ctypes.data, len(rq), now_ns, out.ctypes.data,
+                                                  w.ctypes.data if wire else None), "rtcp_sender_reports")
+        return (out, w) if wire else out
+
+    def sender_delta_info(self, dts):
+        """lkf_sender_delta_info for the DownTrack handles `dts` -> abi.RTP_DELTA_INFO_DTYPE array."""
+        d = np.ascontiguousarray(dts, dtype=np.int32)
+        out = np.zeros(len(d), dtype=abi.RTP_DELTA_INFO_DTYPE)
+        self._chk(self.api["sender_delta_info"](self.h, d.ctypes.data, len(d), out.ctypes.data), "sender_delta_info")
+        return out
+
+    def sender_rtcp(self, dts):
+        """lkf_sender_rtcp_get for each DownTrack handle in `dts` -> abi.SENDER_RTCP_DTYPE array."""
+        out = np.zeros(len(dts), dtype=abi.SENDER_RTCP_DTYPE)
+        for i, d in enumerate(dts):
+            self._chk(self.api["sender_rtcp_get"](self.h, int(d), out[i:i + 1].ctypes.data), "sender_rtcp_get")
+        return out
+
     def stats(self):
         st = abi.lkf_stats()
         self._chk(self.api["get_stats"](self.h, C.byref(st)), "get_stats")

@@ -143,6 +143,103 @@ SENDER_STATS_DTYPE = np.dtype(
     + [(f, "<u4") for f in ("frames", "key_frames", "initialized", "clock_rate")]
     + [("gap_histogram", "<u4", (101,)), ("reserved", "<u4")])
 assert SENDER_STATS_DTYPE.itemsize == 584
+
+
+# ---- the DownTrack RTCP loop (lkf_rtcp_feedback / lkf_rtcp_sender_reports / lkf_sender_delta_info) ----
+class lkf_rtcp_sr_data(C.Structure):
+    _fields_ = [("ntp", C.c_uint64), ("rtp_ext", C.c_uint64), ("at_ns", C.c_int64), ("valid", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+class lkf_interval_stats(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("packets", "bytes", "header_bytes", "packets_padding", "bytes_padding",
+                                          "header_bytes_padding", "packets_lost", "packets_out_of_order",
+                                          "packets_not_found")] + [("frames", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class lkf_sender_snapshot(C.Structure):
+    _fields_ = ([("is_valid", C.c_uint32), ("frames", C.c_uint32), ("start_time_ns", C.c_int64)]
+                + [(f, C.c_uint64) for f in ("ext_start_sn", "bytes", "header_bytes", "packets_padding",
+                                             "bytes_padding", "header_bytes_padding", "packets_duplicate",
+                                             "bytes_duplicate", "header_bytes_duplicate", "packets_out_of_order",
+                                             "packets_lost_feed", "packets_lost")]
+                + [(f, C.c_uint32) for f in ("nacks", "plis", "firs", "max_rtt")]
+                + [("max_jitter_feed", C.c_double), ("max_jitter", C.c_double), ("ext_last_rr_sn", C.c_uint64),
+                   ("interval_stats", lkf_interval_stats)])
+
+
+class lkf_sender_rtcp(C.Structure):
+    _fields_ = ([("ext_highest_sn_from_rr", C.c_uint64), ("last_rr_time_ns", C.c_int64),
+                 ("packets_lost_from_rr", C.c_uint64), ("jitter_from_rr", C.c_double),
+                 ("max_jitter_from_rr", C.c_double), ("end_time_ns", C.c_int64)]
+                + [(f, C.c_uint32) for f in ("last_rr_last_sequence_number", "last_rr_total_lost", "rtt", "max_rtt",
+                                             "nacks", "plis", "firs", "clock_skew_count",
+                                             "out_of_order_sender_report_count", "metadata_cache_overflow_count")]
+                + [("sr_first", lkf_rtcp_sr_data), ("sr_newest", lkf_rtcp_sr_data),
+                   ("snapshot", lkf_sender_snapshot)])
+
+
+class lkf_rtcp_fb(C.Structure):
+    _fields_ = ([("dt", C.c_int32)]
+                + [(f, C.c_uint32) for f in ("flags", "last_sequence_number", "total_lost", "jitter",
+                                             "last_sender_report", "delay", "nacks", "plis", "firs")]
+                + [("fraction_lost", C.c_uint8), ("reserved", C.c_uint8 * 7)])
+
+
+class lkf_rtcp_fb_result(C.Structure):
+    _fields_ = [("rtt_ms", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class lkf_rtcp_sr_req(C.Structure):
+    _fields_ = [("dt", C.c_int32), ("calculated_clock_rate", C.c_uint32)]
+
+
+class lkf_rtcp_sr(C.Structure):
+    _fields_ = [("dt", C.c_int32), ("flags", C.c_uint32), ("ntp", C.c_uint64), ("rtp_ext", C.c_uint64),
+                ("rtp", C.c_uint32), ("packet_count", C.c_uint32), ("octet_count", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+class lkf_rtp_delta_info(C.Structure):
+    _fields_ = ([("start_time_ns", C.c_int64), ("duration_ns", C.c_int64)]
+                + [(f, C.c_uint64) for f in ("bytes", "header_bytes", "bytes_duplicate", "header_bytes_duplicate",
+                                             "bytes_padding", "header_bytes_padding")]
+                + [("jitter_max", C.c_double)]
+                + [(f, C.c_uint32) for f in ("valid", "packets", "packets_duplicate", "packets_padding",
+                                             "packets_lost", "packets_missing", "packets_out_of_order", "frames",
+                                             "rtt_max", "nacks", "plis", "firs")])
+
+
+def _dtype_of(struct):
+    """The numpy dtype of a ctypes structure of integers, doubles, byte arrays and nested structures."""
+    kinds = {C.c_uint64: "<u8", C.c_int64: "<i8", C.c_uint32: "<u4", C.c_int32: "<i4", C.c_double: "<f8",
+             C.c_uint8: "u1"}
+    out = []
+    for name, t in struct._fields_:
+        if t in kinds:
+            out.append((name, kinds[t]))
+        elif issubclass(t, C.Structure):
+            out.append((name, _dtype_of(t)))
+        else:  # a byte array
+            out.append((name, "u1", (C.sizeof(t),)))
+    return np.dtype(out)
+
+
+LKF_FB_HAS_RR = 0x1
+LKF_FB_RTT_CHANGED, LKF_FB_IGNORED, LKF_FB_CACHE_OVERFLOW = 0x1, 0x2, 0x4
+LKF_SR_VALID, LKF_SR_CLOCK_SKEW, LKF_SR_REPAIRED = 0x1, 0x2, 0x4
+SENDER_RTCP_DTYPE = _dtype_of(lkf_sender_rtcp)
+RTCP_FB_DTYPE = _dtype_of(lkf_rtcp_fb)
+RTCP_FB_RESULT_DTYPE = _dtype_of(lkf_rtcp_fb_result)
+RTCP_SR_REQ_DTYPE = _dtype_of(lkf_rtcp_sr_req)
+RTCP_SR_DTYPE = _dtype_of(lkf_rtcp_sr)
+RTP_DELTA_INFO_DTYPE = _dtype_of(lkf_rtp_delta_info)
+assert C.sizeof(lkf_sender_rtcp) == 384 == SENDER_RTCP_DTYPE.itemsize, C.sizeof(lkf_sender_rtcp)
+assert C.sizeof(lkf_rtcp_fb) == 48 == RTCP_FB_DTYPE.itemsize
+assert C.sizeof(lkf_rtcp_fb_result) == 8 == RTCP_FB_RESULT_DTYPE.itemsize
+assert C.sizeof(lkf_rtcp_sr_req) == 8 == RTCP_SR_REQ_DTYPE.itemsize
+assert C.sizeof(lkf_rtcp_sr) == 40 == RTCP_SR_DTYPE.itemsize
+assert C.sizeof(lkf_rtp_delta_info) == 120 == RTP_DELTA_INFO_DTYPE.itemsize
 # NACK -> RTX (lkf_nack / lkf_rtx)
 NACK_DTYPE = np.dtype([("dt", "<i4"), ("sn", "<u2"), ("reserved", "<u2")])
 assert NACK_DTYPE.itemsize == 8
@@ -576,6 +673,14 @@ def bind_engine_api(lib, prefix):
         api["sender_stats_get"] = _bind(lib, prefix + "sender_stats_get", C.c_int, [e, C.c_int32, C.c_void_p])
         api["sender_sninfo"] = _bind(lib, prefix + "sender_sninfo", C.c_int, [e, C.c_int32, C.c_uint64, P(C.c_uint32)])
         api["sender_stats_seed"] = _bind(lib, prefix + "sender_stats_seed", C.c_int, [e, C.c_int32, C.c_int32])
+    if hasattr(lib, prefix + "rtcp_feedback"):  # engine only: the DownTrack RTCP loop
+        api["rtcp_feedback"] = _bind(lib, prefix + "rtcp_feedback", C.c_int,
+                                     [e, C.c_void_p, C.c_uint32, C.c_int64, C.c_void_p])
+        api["rtcp_sender_reports"] = _bind(lib, prefix + "rtcp_sender_reports", C.c_int,
+                                           [e, C.c_void_p, C.c_uint32, C.c_int64, C.c_void_p, C.c_void_p])
+        api["sender_delta_info"] = _bind(lib, prefix + "sender_delta_info", C.c_int,
+                                         [e, C.c_void_p, C.c_uint32, C.c_void_p])
+        api["sender_rtcp_get"] = _bind(lib, prefix + "sender_rtcp_get", C.c_int, [e, C.c_int32, C.c_void_p])
     api["blank_frames"] = _bind(lib, prefix + "blank_frames", C.c_int,
                                 [e, C.c_void_p, C.c_uint32, C.c_int64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64,
                                  P(C.c_uint32), P(C.c_uint64)])

@@ -316,6 +316,12 @@ struct lkf_engine {
   DevBuf<uint32_t> dSSRing;
   DevBuf<SenderUpd> dSSList;
   DevBuf<uint32_t> dSSGroups;  // (one more than dSSList)
+  // the RTCP half of RTPStatsSender (rtcp_kernels.hip): per DownTrack state,
+  // and one call's entries / groups / results (wire bytes behind the records)
+  DevBuf<SenderRtcp> dRtcp;
+  DevBuf<uint8_t> dRtcpIn;
+  DevBuf<uint32_t> dRtcpGroups;
+  DevBuf<uint8_t> dRtcpOut;
   int64_t rtxNow = 0;  // now_ns of the last lkf_rtx_lookup (the RTX packets' sendingPacket time)
   // sequencer ddBytes (sequencer.go:198-199) of the DownTracks that can forward
   // a dependency descriptor: [ring index][slot] kSeqDDBytes, grown on demand
@@ -765,6 +771,7 @@ static int flush_topology(lkf_engine *e) {
              "sender gap reset");
       HIPCHK(hipMemset(e->dSSRing + first * kSnInfoSize, 0, e->pendDTs.size() * kSnInfoSize * sizeof(uint32_t)),
              "sender ring reset");
+      HIPCHK(hipMemset(e->dRtcp + first, 0, e->pendDTs.size() * sizeof(SenderRtcp)), "sender rtcp reset");
     }
     {  // DownTracks that can forward a DD (its selector and a negotiated extension id): a ddBytes ring
       std::vector<uint32_t> idx;
@@ -961,6 +968,7 @@ lkf_engine *lkf_create(int hip_device, const lkf_cfg *cfg) {
   A(e->dTwccCtrD.alloc(c.max_downtracks));
   if (ok) A(hipMemset(e->dTwccCtrD, 0, size_t(c.max_downtracks) * sizeof(uint32_t)));
   A(e->dSS.alloc(c.max_downtracks));
+  A(e->dRtcp.alloc(c.max_downtracks));
   A(e->dSeqDDIdx.alloc(c.max_downtracks));
   A(e->dSSGap.alloc(size_t(c.max_downtracks) * kGapWords));
   A(e->dSSRing.alloc(size_t(c.max_downtracks) * kSnInfoSize));
@@ -1254,6 +1262,15 @@ int32_t lkf_add_downtrack(lkf_engine *e, const lkf_downtrack_params *p) {
   return h;
 }
 
+// rtpStatsBase.Stop (DownTrack.CloseWithFlush): endTime set, a mark (streams drained)
+static int rtcp_stop(lkf_engine *e, size_t dt) {
+  const int64_t mark = 1;
+  HIPCHK(hipMemcpy(reinterpret_cast<uint8_t *>(e->dRtcp + dt) + offsetof(SenderRtcp, endTime), &mark, sizeof(mark),
+                   hipMemcpyHostToDevice),
+         "rtcp stop copy");
+  return LKF_OK;
+}
+
 int lkf_remove_downtrack(lkf_engine *e, int32_t dt) {
   if (!e || dt < 0 || dt >= int32_t(e->dtp.size())) return LKF_EINVAL;
   int rc = flush_topology(e);
@@ -1266,6 +1283,8 @@ int lkf_remove_downtrack(lkf_engine *e, int32_t dt) {
   HIPCHK(hipMemcpy(reinterpret_cast<uint8_t *>(e->dDTs + dt) + offsetof(DevDT, active), &zero, 1,
                    hipMemcpyHostToDevice),
          "remove copy");
+  rc = rtcp_stop(e, size_t(dt));
+  if (rc) return rc;
   e->schedDirty = true;
   return upload_done(e);
 }
@@ -1286,6 +1305,8 @@ int lkf_remove_track(lkf_engine *e, int32_t track) {
       HIPCHK(hipMemcpy(reinterpret_cast<uint8_t *>(e->dDTs + d) + offsetof(DevDT, active), &zero, 1,
                        hipMemcpyHostToDevice),
              "remove copy");
+      rc = rtcp_stop(e, d);
+      if (rc) return rc;
     }
   for (size_t sid = 0; sid < e->streams.size(); sid++)  // Buffer.Close of its streams
     if (e->streams[sid].track == track)
@@ -2681,7 +2702,165 @@ int lkf_sender_stats_seed(lkf_engine *e, int32_t dt, int32_t from_dt) {
   HIPCHK(hipMemcpy(e->dSSRing + size_t(dt) * kSnInfoSize, e->dSSRing + size_t(from_dt) * kSnInfoSize,
                    kSnInfoSize * sizeof(uint32_t), hipMemcpyDeviceToDevice),
          "sender ring seed");
+  {  // the RTCP half: what rtpStatsBase.seed (rtpstats_base.go:206-279) and RTPStatsSender.Seed copy of it;
+     // endTime is not cloned, the three log counters are not part of Seed
+    SenderRtcp rf, rt;
+    D2H(&rf, e->dRtcp + from_dt, sizeof(rf), "sender rtcp copy");
+    D2H(&rt, e->dRtcp + dt, sizeof(rt), "sender rtcp copy");
+    rf.endTime = rt.endTime;
+    rf.clockSkewCount = rt.clockSkewCount;
+    rf.outOfOrderSenderReportCount = rt.outOfOrderSenderReportCount;
+    rf.metadataCacheOverflowCount = rt.metadataCacheOverflowCount;
+    HIPCHK(hipMemcpy(e->dRtcp + dt, &rf, sizeof(rf), hipMemcpyHostToDevice), "sender rtcp seed");
+  }
   return upload_done(e);
+}
+
+// ---- the DownTrack RTCP loop (rtcp_kernels.hip) -------------------------------
+static_assert(sizeof(lkf_sender_rtcp) == sizeof(SenderRtcp), "lkf_sender_rtcp is SenderRtcp's layout");
+static_assert(offsetof(lkf_sender_rtcp, snapshot) == offsetof(SenderRtcp, snap) &&
+                  offsetof(lkf_sender_rtcp, sr_first) == offsetof(SenderRtcp, srFirst) &&
+                  offsetof(lkf_sender_rtcp, end_time_ns) == offsetof(SenderRtcp, endTime) &&
+                  offsetof(lkf_sender_snapshot, interval_stats) == offsetof(RtcpSnapshot, intervalStats),
+              "lkf_sender_rtcp is SenderRtcp's layout");
+static_assert(sizeof(lkf_rtcp_fb) == 48 && sizeof(lkf_rtcp_sr) == 40 && sizeof(lkf_rtp_delta_info) == 120 &&
+                  sizeof(lkf_rtcp_fb_result) == 8 && sizeof(lkf_rtcp_sr_req) == 8,
+              "RTCP call records");
+
+int lkf_sender_rtcp_get(lkf_engine *e, int32_t dt, lkf_sender_rtcp *out) {
+  if (!e || !out || dt < 0 || dt >= int32_t(e->dtp.size())) return LKF_EINVAL;
+  int rc = flush_topology(e);
+  if (rc) return rc;
+  rc = drain_streams(e);
+  if (rc) return rc;
+  D2H(out, e->dRtcp + dt, sizeof(*out), "sender rtcp copy");
+  return LKF_OK;
+}
+
+// The three calls' common frame: the sender stream is ordered after every
+// queued stage that updates RTPStatsSender (sender_after_queued), the call's
+// input goes up and its kernel runs on that stream, and the host waits for
+// the results.  The scratch buffers grow only once the stream is idle.
+static int rtcp_begin(lkf_engine *e, size_t inBytes, size_t groups, size_t outBytes) {
+  int rc = flush_topology(e);
+  if (rc) return rc;
+  HIPCHK(hipSetDevice(e->dev), "hipSetDevice");
+  rc = sender_after_queued(e);
+  if (rc) return rc;
+  if (inBytes > e->dRtcpIn.cap() || groups > e->dRtcpGroups.cap() || outBytes > e->dRtcpOut.cap()) {
+    HIPCHK(hipStreamSynchronize(e->sendS), "sync sender stream");
+    HIPCHK(e->dRtcpIn.reserve(2 * inBytes, 1 << 16), "alloc rtcp in");
+    HIPCHK(e->dRtcpGroups.reserve(2 * groups, 4096), "alloc rtcp groups");
+    HIPCHK(e->dRtcpOut.reserve(2 * outBytes, 1 << 16), "alloc rtcp out");
+  }
+  return LKF_OK;
+}
+static int rtcp_end(lkf_engine *e, void *dst, size_t bytes, std::vector<uint8_t> &tmp) {
+  tmp.resize(bytes);
+  CHKRANGE(e->dRtcpOut, bytes, "async d2h");
+  HIPCHK(hipMemcpyAsync(tmp.data(), e->dRtcpOut, bytes, hipMemcpyDeviceToHost, e->sendS), "rtcp results copy");
+  HIPCHK(hipStreamSynchronize(e->sendS), "sync");
+  std::memcpy(dst, tmp.data(), bytes);
+  return LKF_OK;
+}
+
+int lkf_rtcp_feedback(lkf_engine *e, const lkf_rtcp_fb *in, uint32_t n, int64_t now_ns, lkf_rtcp_fb_result *out) {
+  if (!e || (n && (!in || !out))) return LKF_EINVAL;
+  if (!n) return LKF_OK;
+  // groups: one per DownTrack's contiguous entries (a DownTrack must not reappear)
+  std::vector<uint32_t> g;
+  std::vector<uint8_t> seen(e->dtp.size(), 0);
+  for (uint32_t i = 0; i < n; i++) {
+    const int32_t dt = in[i].dt;
+    if (dt < 0 || dt >= int32_t(e->dtp.size())) return LKF_EINVAL;
+    if (i == 0 || in[i - 1].dt != dt) {
+      if (seen[dt]) return LKF_EORDER;
+      seen[dt] = 1;
+      g.push_back(i);
+    }
+  }
+  g.push_back(n);
+  int rc = rtcp_begin(e, size_t(n) * sizeof(lkf_rtcp_fb), g.size(), size_t(n) * sizeof(lkf_rtcp_fb_result));
+  if (rc) return rc;
+  hipStream_t s = e->sendS;
+  HIPCHK(hipMemcpyAsync(e->dRtcpIn, in, size_t(n) * sizeof(lkf_rtcp_fb), hipMemcpyHostToDevice, s), "rtcp fb copy");
+  HIPCHK(hipMemcpyAsync(e->dRtcpGroups, g.data(), g.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s),
+         "rtcp groups copy");
+  RrUpdateLaunch a;
+  a.in = reinterpret_cast<const lkf_rtcp_fb *>(e->dRtcpIn.get());
+  a.gBegin = e->dRtcpGroups;
+  a.ngroups = uint32_t(g.size() - 1);
+  a.n = n;
+  a.now = now_ns;
+  a.ss = e->dSS;
+  a.ring = e->dSSRing;
+  a.rtcp = e->dRtcp;
+  a.ndts = uint32_t(e->dtp.size());
+  a.out = reinterpret_cast<lkf_rtcp_fb_result *>(e->dRtcpOut.get());
+  HIPCHK(launch_rr_update(s, a), "rr update");
+  std::vector<uint8_t> tmp;
+  return rtcp_end(e, out, size_t(n) * sizeof(lkf_rtcp_fb_result), tmp);
+}
+
+int lkf_rtcp_sender_reports(lkf_engine *e, const lkf_rtcp_sr_req *req, uint32_t n, int64_t now_ns, lkf_rtcp_sr *out,
+                            uint8_t *wire28) {
+  if (!e || (n && (!req || !out))) return LKF_EINVAL;
+  if (!n) return LKF_OK;
+  std::vector<uint8_t> seen(e->dtp.size(), 0);
+  for (uint32_t i = 0; i < n; i++) {
+    const int32_t dt = req[i].dt;
+    if (dt < 0 || dt >= int32_t(e->dtp.size())) return LKF_EINVAL;
+    if (seen[dt]) return LKF_EORDER;  // one thread per request: a DownTrack's state has one writer
+    seen[dt] = 1;
+  }
+  // results: n records (40 B each, so the wire bytes behind them stay 4-B aligned), then 28 B per request
+  const size_t recBytes = size_t(n) * sizeof(lkf_rtcp_sr), wireBytes = wire28 ? size_t(n) * 28 : 0;
+  int rc = rtcp_begin(e, size_t(n) * sizeof(lkf_rtcp_sr_req), 0, recBytes + wireBytes);
+  if (rc) return rc;
+  hipStream_t s = e->sendS;
+  HIPCHK(hipMemcpyAsync(e->dRtcpIn, req, size_t(n) * sizeof(lkf_rtcp_sr_req), hipMemcpyHostToDevice, s),
+         "rtcp sr requests copy");
+  SrBuildLaunch a;
+  a.req = reinterpret_cast<const lkf_rtcp_sr_req *>(e->dRtcpIn.get());
+  a.n = n;
+  a.now = now_ns;
+  a.ss = e->dSS;
+  a.rtcp = e->dRtcp;
+  a.dts = e->dDTs;
+  a.ndts = uint32_t(e->dtp.size());
+  a.out = reinterpret_cast<lkf_rtcp_sr *>(e->dRtcpOut.get());
+  a.wire = wire28 ? e->dRtcpOut.get() + recBytes : nullptr;
+  HIPCHK(launch_sr_build(s, a), "sr build");
+  std::vector<uint8_t> tmp;
+  rc = rtcp_end(e, out, recBytes, tmp);
+  if (rc) return rc;
+  if (wire28) D2H(wire28, e->dRtcpOut.get() + recBytes, wireBytes, "rtcp wire copy");
+  return LKF_OK;
+}
+
+int lkf_sender_delta_info(lkf_engine *e, const int32_t *dts, uint32_t n, lkf_rtp_delta_info *out) {
+  if (!e || (n && (!dts || !out))) return LKF_EINVAL;
+  if (!n) return LKF_OK;
+  std::vector<uint8_t> seen(e->dtp.size(), 0);
+  for (uint32_t i = 0; i < n; i++) {
+    if (dts[i] < 0 || dts[i] >= int32_t(e->dtp.size())) return LKF_EINVAL;
+    if (seen[dts[i]]) return LKF_EORDER;
+    seen[dts[i]] = 1;
+  }
+  int rc = rtcp_begin(e, size_t(n) * sizeof(int32_t), 0, size_t(n) * sizeof(lkf_rtp_delta_info));
+  if (rc) return rc;
+  hipStream_t s = e->sendS;
+  HIPCHK(hipMemcpyAsync(e->dRtcpIn, dts, size_t(n) * sizeof(int32_t), hipMemcpyHostToDevice, s), "rtcp dts copy");
+  DeltaSenderLaunch a;
+  a.dts = reinterpret_cast<const int32_t *>(e->dRtcpIn.get());
+  a.n = n;
+  a.ss = e->dSS;
+  a.rtcp = e->dRtcp;
+  a.ndts = uint32_t(e->dtp.size());
+  a.out = reinterpret_cast<lkf_rtp_delta_info *>(e->dRtcpOut.get());
+  HIPCHK(launch_delta_sender(s, a), "delta sender");
+  std::vector<uint8_t> tmp;
+  return rtcp_end(e, out, size_t(n) * sizeof(lkf_rtp_delta_info), tmp);
 }
 
 int lkf_get_state(lkf_engine *e, int32_t dt, lkf_fwd_state *o) {
@@ -4494,6 +4673,13 @@ int lkf_debug_check(lkf_engine *e, uint64_t out[4], int reset) {
   unsigned long long v[4];
   hipError_t r = read_check(v, reset);
   for (int i = 0; i < 4; i++) out[i] = v[i];
+  {  // the RTCP kernels keep their own record (rtcp_kernels.hip is its own code object)
+    unsigned long long w[4];
+    if (read_check_rtcp(w, reset) == hipSuccess && w[0]) {
+      if (!out[0]) out[1] = w[1], out[2] = w[2], out[3] = w[3];
+      out[0] += w[0];
+    }
+  }
   // host-side device -> host range violations (CHKRANGE) count as well, in
   // every build; site 0xD2H marks one when the device recorded none
   // an engine's own refusals; with no engine, every engine's

@@ -336,6 +336,54 @@ struct alignas(16) SenderStats {
 };
 static_assert(sizeof(SenderStats) == 192, "SenderStats is 192 B");
 
+// The RTCP half of DownTrack.rtpStats (rtcp_device.h, rtcp_kernels.hip): what
+// RTPStatsSender.UpdateFromReceiverReport, GetRtcpSenderReport and
+// DeltaInfoSender keep (rtpstats_sender.go:137-163, rtpstats_base.go:170-191).
+// One per DownTrack, zeroed when it is added; the layout is lkf_sender_rtcp's
+// (include/lkfwd.h).  Times are ns of the engine's virtual clock, 0 = the zero
+// time.  startTime, which the engine does not keep, is SenderStats.firstTime:
+// the reference sets both at the first packet (rtpstats_sender.go:262-265).
+// endTime != 0: the handle was removed (lkf_remove_downtrack /
+// lkf_remove_track; the value is a mark, not a time).  One senderSnapshot:
+// DownTrack takes exactly one NewSenderSnapshotId, before the statistics are
+// initialized (downtrack.go:319), so it starts as the zero value (isValid 0).
+// Out of scope: the base-class snapshots / DeltaInfo(snapshotID) and the
+// wall-clock UpdatePliTime / lastPli.
+struct RtcpSrData {  // RTCPSenderReportData rtpstats_base.go:111-116 (RTPTimestamp = u32(rtpExt))
+  uint64_t ntp, rtpExt;
+  int64_t at;
+  uint32_t valid, pad;  // valid 0: the nil pointer
+};
+struct RtcpIntervalStats {  // intervalStats rtpstats_sender.go:50-61
+  uint64_t packets, bytes, headerBytes, packetsPadding, bytesPadding, headerBytesPadding;
+  uint64_t packetsLost, packetsOutOfOrder, packetsNotFound;
+  uint32_t frames, pad;
+};
+struct RtcpSnapshot {  // senderSnapshot rtpstats_sender.go:101-135
+  uint32_t isValid, frames;
+  int64_t startTime;
+  uint64_t extStartSN, bytes, headerBytes, packetsPadding, bytesPadding, headerBytesPadding;
+  uint64_t packetsDuplicate, bytesDuplicate, headerBytesDuplicate, packetsOutOfOrder, packetsLostFeed, packetsLost;
+  uint32_t nacks, plis, firs, maxRtt;
+  double maxJitterFeed, maxJitter;
+  uint64_t extLastRRSN;
+  RtcpIntervalStats intervalStats;
+};
+struct alignas(16) SenderRtcp {
+  uint64_t extHighestSNFromRR;
+  int64_t lastRRTime;
+  uint64_t packetsLostFromRR;
+  double jitterFromRR, maxJitterFromRR;
+  int64_t endTime;
+  uint32_t lastRRLastSequenceNumber, lastRRTotalLost;  // lastRR: the two fields that are read back
+  uint32_t rtt, maxRtt, nacks, plis, firs;
+  uint32_t clockSkewCount, outOfOrderSenderReportCount, metadataCacheOverflowCount;
+  RtcpSrData srFirst, srNewest;
+  RtcpSnapshot snap;
+};
+static_assert(sizeof(RtcpSrData) == 32 && sizeof(RtcpIntervalStats) == 80 && sizeof(RtcpSnapshot) == 232, "");
+static_assert(sizeof(SenderRtcp) == 384, "SenderRtcp is 384 B");
+
 // Forwarder.provisional: VideoAllocationProvisional (forwarder.go:96-106),
 // one per DownTrack, written by lkf_provisional_prepare / lkf_allocate_all
 struct alignas(16) ProvState {

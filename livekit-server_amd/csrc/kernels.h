@@ -498,4 +498,47 @@ struct SenderListLaunch {
 };
 hipError_t launch_sender_updates(hipStream_t s, const SenderListLaunch &a);
 
+// ---- the DownTrack RTCP loop (rtcp_kernels.hip) -------------------------------
+// k_rr_update: one wave per DownTrack that has entries in the call
+struct RrUpdateLaunch {
+  const lkf_rtcp_fb *in;   // grouped by DownTrack, list order within a group
+  const uint32_t *gBegin;  // ngroups + 1
+  uint32_t ngroups;
+  uint32_t n;              // entries
+  int64_t now;
+  const SenderStats *ss;
+  const uint32_t *ring;
+  SenderRtcp *rtcp;
+  uint32_t ndts;           // DownTrack handles (the three tables' rows)
+  lkf_rtcp_fb_result *out;  // per entry
+};
+hipError_t launch_rr_update(hipStream_t s, const RrUpdateLaunch &a);
+// k_sr_build: one thread per request (each DownTrack at most once)
+struct SrBuildLaunch {
+  const lkf_rtcp_sr_req *req;
+  uint32_t n;
+  int64_t now;
+  const SenderStats *ss;
+  SenderRtcp *rtcp;
+  const DevDT *dts;  // the SSRC of the wire packet
+  uint32_t ndts;
+  lkf_rtcp_sr *out;
+  uint8_t *wire;  // 28 B per request, or nullptr
+};
+hipError_t launch_sr_build(hipStream_t s, const SrBuildLaunch &a);
+// k_delta_sender: one thread per listed DownTrack (each at most once)
+struct DeltaSenderLaunch {
+  const int32_t *dts;
+  uint32_t n;
+  const SenderStats *ss;
+  SenderRtcp *rtcp;
+  uint32_t ndts;
+  lkf_rtp_delta_info *out;
+};
+hipError_t launch_delta_sender(hipStream_t s, const DeltaSenderLaunch &a);
+// -DLKF_CHECKED=1 builds of rtcp_kernels.hip: its own {violations, first site,
+// index, capacity} (sites 101 DownTrack handle, 102 ring slot, 103 entry /
+// request index); lkf_debug_check folds it into the record
+hipError_t read_check_rtcp(unsigned long long out[4], int reset);
+
 }  // namespace lkf

@@ -1,0 +1,205 @@
+// rtcp_kernels.hip — the DownTrack RTCP loop on the GPU (gfx950): the RTCP
+// half of buffer.RTPStatsSender over the snInfo ring the decide wave keeps.
+//
+//   k_rr_update     one wave per DownTrack that has entries in the call:
+//                   UpdateFromReceiverReport (rtpstats_sender.go:441-565) and
+//                   UpdateNack / UpdatePli / UpdateFir for each entry in list
+//                   order.  The scalar head runs on wave-uniform state (every
+//                   lane the same registers); getIntervalStats (:947-987) is
+//                   lane-parallel: packetsNotFound in closed form, the at most
+//                   4096 found sequence numbers as consecutive ring slots (one
+//                   256-B row per step, the start not aligned, wrapping at slot
+//                   4095), nine counters per lane, one cross-lane reduction.
+//                   No atomics, no LDS.  Lane 0 writes the state back.
+//   k_sr_build      one thread per request: GetRtcpSenderReport (:596-714), the
+//                   lkf_rtcp_sr record and, when asked, the 28-byte packet.
+//   k_delta_sender  one thread per DownTrack: DeltaInfoSender (:723-808).
+//
+// The semantics are rtcp_device.h's (shared with the host unit program).
+#include <hip/hip_runtime.h>
+
+#include "kernels.h"
+#include "rtcp_device.h"
+
+namespace lkf {
+namespace {
+using u8 = uint8_t;
+using u32 = uint32_t;
+using u64 = uint64_t;
+using i64 = int64_t;
+using namespace rtcp;
+
+// Checked builds (-DLKF_CHECKED=1, liblkfwd_checked.so): as forward_kernels.hip's
+// CHK, with this file's own record (read_check_rtcp).
+#ifndef LKF_CHECKED
+#define LKF_CHECKED 0
+#endif
+enum : u32 { CK_RTCP_DT = 101, CK_RTCP_SLOT = 102, CK_RTCP_ENTRY = 103 };
+#if LKF_CHECKED
+__device__ unsigned long long g_chk_rtcp[4];
+__device__ __noinline__ void chk_fail(u32 site, u64 idx, u64 cap) {
+  if (atomicAdd(&g_chk_rtcp[0], 1ull) == 0) {
+    g_chk_rtcp[1] = site;
+    g_chk_rtcp[2] = idx;
+    g_chk_rtcp[3] = cap;
+  }
+}
+#define CHK(cond, site, idx, cap)                   \
+  do {                                              \
+    if (!(cond)) chk_fail(site, u64(idx), u64(cap)); \
+  } while (0)
+#else
+#define CHK(cond, site, idx, cap) \
+  do {                            \
+  } while (0)
+#endif
+
+__device__ __forceinline__ u32 wave_sum(u32 v) {
+  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+  return v;
+}
+
+__global__ __launch_bounds__(64) void k_rr_update(RrUpdateLaunch A) {
+  const u32 g = blockIdx.x, lane = threadIdx.x;
+  if (g >= A.ngroups) return;
+  const u32 b = A.gBegin[g], e = A.gBegin[g + 1];
+  CHK(e <= A.n, CK_RTCP_ENTRY, e, A.n);
+  if (b >= e || e > A.n) return;
+  const u32 d = u32(A.in[b].dt);
+  CHK(d < A.ndts, CK_RTCP_DT, d, A.ndts);
+  if (d >= A.ndts) return;
+  SenderRtcp R = A.rtcp[d];
+  const SenderStats S = A.ss[d];
+  const u32 *ring = A.ring + size_t(d) * kSnInfoSize;
+  for (u32 i = b; i < e; i++) {
+    const lkf_rtcp_fb &f = A.in[i];
+    u32 rtt = 0, flags = 0;
+    if (f.flags & LKF_FB_HAS_RR) {
+      const RrIn rr = {f.last_sequence_number, f.total_lost, f.jitter, f.last_sender_report, f.delay};
+      const RrHead h = rr_head(R, S, rr, A.now);
+      rtt = h.rtt;
+      flags = LKF_FB_IGNORED;
+      if (!h.ignored) {
+        const IntervalPlan p = interval_plan(h.start, h.endEx, S.extHighestSN);
+        IntervalPart a = {};
+        for (u32 k = lane; k < p.count; k += 64) {
+          const u32 slot = u32((p.first + k) & u64(kSnInfoSize - 1));
+          CHK(slot < u32(kSnInfoSize), CK_RTCP_SLOT, slot, kSnInfoSize);
+          interval_classify(a, ring[slot]);
+        }
+        a.packets = wave_sum(a.packets);
+        a.bytes = wave_sum(a.bytes);
+        a.headerBytes = wave_sum(a.headerBytes);
+        a.packetsPadding = wave_sum(a.packetsPadding);
+        a.bytesPadding = wave_sum(a.bytesPadding);
+        a.headerBytesPadding = wave_sum(a.headerBytesPadding);
+        a.packetsLost = wave_sum(a.packetsLost);
+        a.packetsOutOfOrder = wave_sum(a.packetsOutOfOrder);
+        a.frames = wave_sum(a.frames);
+        const RtcpIntervalStats is = interval_total(a, p.notFound);
+        rr_tail(R, h, is, rr, A.now);
+        flags = rr_flags(h, is);
+      }
+    }
+    update_counts(R, f.nacks, f.plis, f.firs);  // after the report, as handleRTCP (downtrack.go:1565-1567)
+    if (lane == 0) {
+      lkf_rtcp_fb_result r;
+      r.rtt_ms = rtt;
+      r.flags = flags;
+      A.out[i] = r;
+    }
+  }
+  if (lane == 0) {
+    // what UpdateFromReceiverReport and the counter adds write: the scalars
+    // ahead of srFirst and four members of the snapshot (a whole-struct store
+    // would carry the untouched 160 B through scratch)
+    SenderRtcp &o = A.rtcp[d];
+    o.extHighestSNFromRR = R.extHighestSNFromRR;
+    o.lastRRTime = R.lastRRTime;
+    o.packetsLostFromRR = R.packetsLostFromRR;
+    o.jitterFromRR = R.jitterFromRR;
+    o.maxJitterFromRR = R.maxJitterFromRR;
+    o.lastRRLastSequenceNumber = R.lastRRLastSequenceNumber;
+    o.lastRRTotalLost = R.lastRRTotalLost;
+    o.rtt = R.rtt;
+    o.maxRtt = R.maxRtt;
+    o.nacks = R.nacks;
+    o.plis = R.plis;
+    o.firs = R.firs;
+    o.metadataCacheOverflowCount = R.metadataCacheOverflowCount;
+    o.snap.maxRtt = R.snap.maxRtt;
+    o.snap.maxJitter = R.snap.maxJitter;
+    o.snap.extLastRRSN = R.snap.extLastRRSN;
+    o.snap.intervalStats = R.snap.intervalStats;
+  }
+}
+
+__global__ void k_sr_build(SrBuildLaunch A) {
+  const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= A.n) return;
+  const lkf_rtcp_sr_req q = A.req[i];
+  const u32 d = u32(q.dt);
+  CHK(d < A.ndts, CK_RTCP_DT, d, A.ndts);
+  if (d >= A.ndts) return;
+  SenderRtcp R = A.rtcp[d];
+  const SenderStats S = A.ss[d];
+  lkf_rtcp_sr o;
+  sender_report(R, S, q.dt, q.calculated_clock_rate, A.now, o);
+  if (o.flags & LKF_SR_VALID) A.rtcp[d] = R;
+  A.out[i] = o;
+  if (A.wire) {  // 28 B per request: 4-B aligned, big-endian words
+    const u32 ssrc = A.dts[d].ssrc;
+    u32 *w = reinterpret_cast<u32 *>(A.wire + size_t(i) * 28);
+    for (int k = 0; k < 7; k++) w[k] = __builtin_bswap32(sender_report_word(o, ssrc, k));
+  }
+}
+
+__global__ void k_delta_sender(DeltaSenderLaunch A) {
+  const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= A.n) return;
+  const u32 d = u32(A.dts[i]);
+  CHK(d < A.ndts, CK_RTCP_DT, d, A.ndts);
+  if (d >= A.ndts) return;
+  SenderRtcp R = A.rtcp[d];
+  const SenderStats S = A.ss[d];
+  lkf_rtp_delta_info o;
+  delta_info_sender(R, S, o);
+  A.rtcp[d].snap = R.snap;
+  A.out[i] = o;
+}
+}  // namespace
+
+hipError_t launch_rr_update(hipStream_t s, const RrUpdateLaunch &a) {
+  if (!a.ngroups) return hipSuccess;
+  hipLaunchKernelGGL(k_rr_update, dim3(a.ngroups), dim3(64), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_sr_build(hipStream_t s, const SrBuildLaunch &a) {
+  if (!a.n) return hipSuccess;
+  hipLaunchKernelGGL(k_sr_build, dim3((a.n + 63) / 64), dim3(64), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_delta_sender(hipStream_t s, const DeltaSenderLaunch &a) {
+  if (!a.n) return hipSuccess;
+  hipLaunchKernelGGL(k_delta_sender, dim3((a.n + 63) / 64), dim3(64), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t read_check_rtcp(unsigned long long out[4], int reset) {
+#if LKF_CHECKED
+  hipError_t r = hipMemcpyFromSymbol(out, HIP_SYMBOL(g_chk_rtcp), sizeof(unsigned long long) * 4);
+  if (r == hipSuccess && reset) {
+    unsigned long long z[4] = {};
+    r = hipMemcpyToSymbol(HIP_SYMBOL(g_chk_rtcp), z, sizeof(z));
+  }
+  return r;
+#else
+  (void)reset;
+  for (int i = 0; i < 4; i++) out[i] = 0;
+  return hipErrorNotSupported;
+#endif
+}
+
+}  // namespace lkf
