@@ -1167,6 +1167,97 @@ int lkf_ingest_nacks(lkf_engine *e, lkf_rtcp_nack *out, uint32_t cap, lkf_nack_p
 /* Buffer.SetRTT (buffer.go:400-414): the NackQueue RTT of a stream from the
  * next ingest on (0 is ignored, as in the reference). */
 int lkf_stream_set_rtt(lkf_engine *e, int32_t stream, uint32_t rtt_ms);
+
+/* ---- SRTP unprotect, in front of ingress ---------------------------------- *
+ * What a publisher's PeerConnection hands the server is SRTP: in the
+ * reference every received packet is authenticated, replay-checked and
+ * decrypted before Buffer.Write sees it (pion/srtp v2.0.18 Context.DecryptRTP
+ * behind ReadStreamSRTP, go.mod:87).  These calls do that for a raw batch on
+ * the GPU; their output is the input of lkf_ingest*.
+ *
+ * pion/srtp is not part of the reference tree, so the engine defines what it
+ * computes, from RFC 3711 §3.3 and RFC 7714 with pion's ordering (replay
+ * check, then authenticate, then commit); parity unpinned, DESIGN.md §2.
+ * Profiles and keys are those of lkf_add_transport (AES-128 only, no MKI,
+ * key-derivation rate 0); SRTCP is out of scope.
+ *
+ * Per received stream, in the order the call lists that stream's datagrams:
+ *   started; s_l, the u64 index ROC << 16 | SEQ of the highest authenticated
+ *   packet; mask, a u64 whose bit k says index s_l - k was accepted.
+ * For each datagram of a stream bound to a transport:
+ *   1. Parse.  LKF_SRTP_RX_MALFORMED if off is not a multiple of 16, the
+ *      datagram is shorter than 12 bytes, its version is not 2, or it is
+ *      shorter than its header length h (12 + 4 * CC, plus 4 + 4 * length of a
+ *      one- or two-byte extension block when X is set) plus the tag length (10
+ *      for AES-CM, 16 for GCM) — and also if off + len exceeds srtp_len or the
+ *      stream handle is unknown (the engine reads no byte of such a datagram).
+ *   2. Index.  Not started: v = SEQ.  Started: v = s_l + (int16)(SEQ - (s_l &
+ *      0xffff)); if that is negative, v = SEQ.  ROC = v >> 16.  A ROC beyond
+ *      2^32 is out of scope (the low 32 bits are used).
+ *   3. Replay, when started and v <= s_l: s_l - v >= 64 is
+ *      LKF_SRTP_RX_REPLAY_OLD, a set mask bit LKF_SRTP_RX_REPLAY_DUP (window
+ *      64, pion/webrtc's default).
+ *   4. Authenticate with that ROC.  AES-CM: the first 10 bytes of HMAC-SHA1
+ *      over pkt[0 : len - 10] || ROC_be32 equal the trailing tag.  GCM: RFC
+ *      7714 open with the IV and AAD of lkf_protect.  A mismatch is
+ *      LKF_SRTP_RX_AUTH, with no state change.
+ *   5. Accept.  First packet: started = 1, s_l = v, mask = 1.  v > s_l: mask
+ *      <<= v - s_l (0 when the shift is >= 64), bit 0 set, s_l = v.  Otherwise
+ *      bit s_l - v set.  The plaintext is the unchanged header followed by the
+ *      decrypted payload, len - tag bytes.
+ * A stream bound to no transport passes through: its bytes are copied, its
+ * status is LKF_SRTP_RX_OK and its state is untouched (as unbound DownTracks in
+ * lkf_protect); only the arena bound of step 1 applies to it.  The IV uses the
+ * SSRC in the packet's header; the state is keyed by the datagram's stream
+ * handle. */
+#define LKF_SRTP_RX_OK 0
+#define LKF_SRTP_RX_MALFORMED 1
+#define LKF_SRTP_RX_REPLAY_OLD 2
+#define LKF_SRTP_RX_REPLAY_DUP 3
+#define LKF_SRTP_RX_AUTH 4
+/* Binds a received stream to the transport (lkf_add_transport, made with the
+ * remote side's write key) its datagrams are protected with; -1 unbinds.
+ * Binding resets the stream's receive state and counters. */
+int lkf_set_stream_transport(lkf_engine *e, int32_t stream, int32_t transport);
+/* Unprotects n datagrams (d_pkts[i].off / len in the arena d_srtp of srtp_len
+ * bytes; all device memory, 16-byte aligned arenas that do not overlap).
+ * Datagram i's plaintext goes to d_plain + d_pkts[i].off: the output arena has
+ * the input's size, plaintext is never longer.  d_pkts_out[i] is d_pkts[i]
+ * with the new len, or len = 0 for a rejected datagram: indices are preserved,
+ * so LKF_AT_DATAGRAM keys, lkf_ingest_twcc words and flows stay aligned with
+ * the caller's list, and a len = 0 datagram is LKF_FLOW_BAD at ingest with no
+ * state change.  The bytes of a rejected datagram's slot are unspecified.
+ * Enqueued on the engine's prep stream with no host sync, ahead of a following
+ * lkf_ingest_device of (d_pkts_out, d_plain): the inputs must be complete when
+ * it is called, and they and the outputs must stay valid until lkf_sync (or
+ * lkf_unprotect_results) returns.  The kernels read datagrams as aligned 16-B
+ * words: the 32 bytes after srtp_len must be readable device memory, as for
+ * lkf_ingest_device; nothing is written past srtp_len in d_plain. */
+int lkf_unprotect_device(lkf_engine *e, const lkf_raw_pkt *d_pkts, uint32_t n, const uint8_t *d_srtp,
+                         uint64_t srtp_len, lkf_raw_pkt *d_pkts_out, uint8_t *d_plain);
+/* The host form: copies the batch in, unprotects it into the staging
+ * lkf_ingest uses, then ingests.  Lifetime rules as lkf_ingest. */
+int lkf_ingest_srtp(lkf_engine *e, const lkf_raw_pkt *pkts, uint32_t n, const uint8_t *srtp, uint64_t srtp_len);
+/* Per datagram of the last unprotect (input order).  index is v for every
+ * datagram of a bound stream that parsed, 0 otherwise; len is the plaintext
+ * length (0 when rejected).  Synchronizes. */
+typedef struct lkf_srtp_rx_result {
+  uint64_t index;
+  uint32_t status; /* LKF_SRTP_RX_* */
+  uint32_t len;
+} lkf_srtp_rx_result;
+int lkf_unprotect_results(lkf_engine *e, lkf_srtp_rx_result *out, uint32_t cap, uint32_t *n_out);
+/* One stream's receive state and counters (waits for queued work). */
+typedef struct lkf_stream_srtp {
+  uint64_t s_l, mask;
+  uint32_t started;
+  int32_t transport; /* -1: unbound */
+  uint64_t accepted, auth_failures, replays, malformed;
+} lkf_stream_srtp;
+int lkf_stream_srtp_get(lkf_engine *e, int32_t stream, lkf_stream_srtp *out);
+/* Over the last n unprotect calls (n <= 256): the sum of the unprotect stage
+ * spans (index, crypto and commit kernels), ms. */
+int lkf_unprotect_timing_window(lkf_engine *e, uint32_t n, float *unprotect_ms);
 /* Removes a published track: WebRTCReceiver.closeTracks (receiver.go:700-716)
  * closes its DownTracks (as lkf_remove_downtrack each) and the Buffers of its
  * streams (Buffer.Close buffer.go:337-352: Write then returns io.EOF, so a

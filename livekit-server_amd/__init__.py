@@ -295,6 +295,48 @@ class Engine:
         if rc != 0:
             raise EngineError("lkf_ingest_device rc=%d: %s" % (rc, self.lib.lkf_last_error(self.h).decode()))
 
+    def set_stream_transport(self, stream, transport):
+        """lkf_set_stream_transport: the transport (lkf_add_transport handle,
+        -1: none) a received stream's datagrams are protected with."""
+        self._chk(self.api["set_stream_transport"](self.h, stream, transport), "set_stream_transport")
+
+    def unprotect_device(self, d_pkts, n, d_srtp, srtp_len, d_pkts_out, d_plain):
+        """lkf_unprotect_device: SRTP unprotect of HBM-resident datagrams into
+        (d_pkts_out, d_plain), the input of ingest_device (no host sync)."""
+        self._chk(self.api["unprotect_device"](self.h, d_pkts, n, d_srtp, srtp_len, d_pkts_out, d_plain),
+                  "unprotect_device")
+
+    def ingest_srtp(self, raws, n, srtp, srtp_len):
+        """lkf_ingest_srtp: the host form, unprotect then ingest."""
+        self._chk(self.api["ingest_srtp"](self.h, C.cast(raws, C.c_void_p), n, C.cast(srtp, C.c_void_p), srtp_len),
+                  "ingest_srtp")
+
+    def unprotect_results(self):
+        """lkf_unprotect_results -> abi.SRTP_RX_RESULT_DTYPE array, one row per datagram of the last unprotect."""
+        n = C.c_uint32()
+        rc = self.api["unprotect_results"](self.h, None, 0, C.byref(n))
+        if rc not in (0, -28):
+            self._chk(rc, "unprotect_results probe")
+        out = np.zeros(n.value, dtype=abi.SRTP_RX_RESULT_DTYPE)
+        self._chk(self.api["unprotect_results"](self.h, out.ctypes.data, n.value, C.byref(n)), "unprotect_results")
+        return out
+
+    def stream_srtp(self, stream):
+        """lkf_stream_srtp_get -> (s_l, mask, started, transport, accepted, auth_failures, replays, malformed)."""
+        st = abi.lkf_stream_srtp()
+        self._chk(self.api["stream_srtp_get"](self.h, stream, C.byref(st)), "stream_srtp_get")
+        return st.as_tuple()
+
+    def unprotect_timing_window(self, n):
+        ms = C.c_float()
+        self._chk(self.api["unprotect_timing_window"](self.h, n, C.byref(ms)), "unprotect_timing_window")
+        return ms.value
+
+    def protect_timing_window(self, n):
+        ms = C.c_float()
+        self._chk(self.api["protect_timing_window"](self.h, n, C.byref(ms)), "protect_timing_window")
+        return ms.value
+
     def flows(self):
         return flows_array(self.api, self.h)
 

@@ -453,6 +453,25 @@ LKF_FLOW_NOT_HANDLED, LKF_FLOW_DUPLICATE, LKF_FLOW_OUT_OF_ORDER, LKF_FLOW_HAS_LO
 LKF_FLOW_PADDING, LKF_FLOW_FORWARD, LKF_FLOW_BAD, LKF_FLOW_BUCKET = 0x10, 0x20, 0x40, 0x80
 LKF_TWCC_MARKER = 0x00010000
 SRTP_TAG_LEN = 10
+# SRTP unprotect (lkf_unprotect_device / lkf_ingest_srtp): per-datagram status, results and per-stream state
+LKF_SRTP_RX_OK, LKF_SRTP_RX_MALFORMED, LKF_SRTP_RX_REPLAY_OLD, LKF_SRTP_RX_REPLAY_DUP, LKF_SRTP_RX_AUTH = 0, 1, 2, 3, 4
+SRTP_RX_RESULT_DTYPE = np.dtype([("index", "<u8"), ("status", "<u4"), ("len", "<u4")])
+assert SRTP_RX_RESULT_DTYPE.itemsize == 16
+RAW_PKT_DTYPE = np.dtype([("arrival_ns", "<i8"), ("stream", "<u4"), ("off", "<u4"), ("len", "<u4"),
+                          ("reserved", "<u4")])
+assert RAW_PKT_DTYPE.itemsize == 24
+
+
+class lkf_stream_srtp(C.Structure):
+    _fields_ = [("s_l", C.c_uint64), ("mask", C.c_uint64), ("started", C.c_uint32), ("transport", C.c_int32),
+                ("accepted", C.c_uint64), ("auth_failures", C.c_uint64), ("replays", C.c_uint64),
+                ("malformed", C.c_uint64)]
+
+    def as_tuple(self):
+        return tuple(getattr(self, n) for n, _ in self._fields_)
+
+
+assert C.sizeof(lkf_stream_srtp) == 56
 
 
 class lkf_seq_meta(C.Structure):
@@ -626,6 +645,20 @@ def bind_engine_api(lib, prefix):
     api["set_downtrack_transport"] = _bind(lib, prefix + "set_downtrack_transport", C.c_int, [e, C.c_int32, C.c_int32])
     api["protect"] = _bind(lib, prefix + "protect", C.c_int, [e, C.c_int64])
     api["drain_protected"] = _bind(lib, prefix + "drain_protected", C.c_int, [e, C.c_void_p, C.c_uint64, P(C.c_uint64)])
+    if hasattr(lib, prefix + "unprotect_device"):  # engine only: SRTP unprotect in front of ingress
+        api["set_stream_transport"] = _bind(lib, prefix + "set_stream_transport", C.c_int, [e, C.c_int32, C.c_int32])
+        api["unprotect_device"] = _bind(lib, prefix + "unprotect_device", C.c_int,
+                                        [e, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p])
+        api["ingest_srtp"] = _bind(lib, prefix + "ingest_srtp", C.c_int,
+                                   [e, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64])
+        api["unprotect_results"] = _bind(lib, prefix + "unprotect_results", C.c_int,
+                                         [e, C.c_void_p, C.c_uint32, P(C.c_uint32)])
+        api["stream_srtp_get"] = _bind(lib, prefix + "stream_srtp_get", C.c_int, [e, C.c_int32, P(lkf_stream_srtp)])
+        api["unprotect_timing_window"] = _bind(lib, prefix + "unprotect_timing_window", C.c_int,
+                                               [e, C.c_uint32, P(C.c_float)])
+    if hasattr(lib, prefix + "protect_timing_window"):
+        api["protect_timing_window"] = _bind(lib, prefix + "protect_timing_window", C.c_int,
+                                             [e, C.c_uint32, P(C.c_float)])
     if not hasattr(lib, prefix + "padding"):  # (an older build, e.g. an A/B baseline library)
         return api
     api["padding"] = _bind(lib, prefix + "padding", C.c_int,

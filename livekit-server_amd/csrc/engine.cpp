@@ -453,6 +453,18 @@ struct lkf_engine {
   DevBuf<SrtpDT> dSrtpDT;
   Event protRing[256][2];        // k_srtp_roc start / k_srtp_protect end per run (timing)
   std::vector<uint8_t> protRun;  // per ring slot: that run was protected
+  // SRTP unprotect (allocated with the first lkf_set_stream_transport or
+  // unprotect call): per-stream receive state and its speculated copy, each
+  // stream's datagram range of the call, per-datagram scratch and results
+  DevBuf<SrtpRx> dSrtpRx, dSrtpRxSpec;
+  DevBuf<uint32_t> dRxRange, dRxAuth;
+  DevBuf<SrtpRxSpec> dRxSpec;
+  DevBuf<lkf_srtp_rx_result> dRxRes;
+  DevBuf<uint8_t> dSrtpStage;       // lkf_ingest_srtp's copy of the protected arena
+  DevBuf<lkf_raw_pkt> dSrtpPktsIn;  // ... and of its descriptors
+  Event rxRing[256][2];             // unprotect stage start / end per call (timing)
+  uint64_t nUnprotects = 0;
+  uint32_t lastUnprotectN = 0;
   // ingress (one buffer.Buffer per stream) + speakers
   uint32_t maxStreams = 0;
   DevBuf<DevStream> dStreams;
@@ -4176,13 +4188,9 @@ static int ingest_common(lkf_engine *e, BatchCtx &x, const lkf_raw_pkt *dRaws, u
   return LKF_OK;
 }
 
-int lkf_ingest(lkf_engine *e, const lkf_raw_pkt *pkts, uint32_t n, const uint8_t *raw, uint64_t raw_len) {
-  if (!e || (n && (!pkts || !raw))) return LKF_EINVAL;
-  if (n > e->cfg.max_batch_pkts || raw_len > e->cfg.max_batch_arena) return LKF_ENOSPC;
-  int rc = flush_topology(e);
-  if (rc) return rc;
-  HIPCHK(hipSetDevice(e->dev), "hipSetDevice");
-  BatchCtx &x = e->ctx[e->nRuns % lkf_engine::kCtx];
+// The ingest stream waits for what still reads the context's staging buffers
+// (dRawPkts, dArenaOwn) before a host-form ingest overwrites them.
+static int ingest_staging_waits(lkf_engine *e, BatchCtx &x) {
   if (x.used) HIPCHK(hipStreamWaitEvent(e->ingS, x.emitted, 0), "wait emit");  // batch n-3 reads these buffers
   if (e->haveBatch && e->curPkts == x.dPktsOwn) {
     // a second ingest into this context before lkf_run: the previous ingest's
@@ -4192,6 +4200,18 @@ int lkf_ingest(lkf_engine *e, const lkf_raw_pkt *pkts, uint32_t n, const uint8_t
     if (e->sidePending[lp]) HIPCHK(hipStreamWaitEvent(e->ingS, e->sideDone[lp], 0), "wait nack queues");
     if (e->bktPending[lp]) HIPCHK(hipStreamWaitEvent(e->ingS, e->bktDone[lp], 0), "wait bucket copies");
   }
+  return LKF_OK;
+}
+
+int lkf_ingest(lkf_engine *e, const lkf_raw_pkt *pkts, uint32_t n, const uint8_t *raw, uint64_t raw_len) {
+  if (!e || (n && (!pkts || !raw))) return LKF_EINVAL;
+  if (n > e->cfg.max_batch_pkts || raw_len > e->cfg.max_batch_arena) return LKF_ENOSPC;
+  int rc = flush_topology(e);
+  if (rc) return rc;
+  HIPCHK(hipSetDevice(e->dev), "hipSetDevice");
+  BatchCtx &x = e->ctx[e->nRuns % lkf_engine::kCtx];
+  rc = ingest_staging_waits(e, x);
+  if (rc) return rc;
   if (n) HIPCHK(hipMemcpyAsync(x.dRawPkts, pkts, size_t(n) * sizeof(lkf_raw_pkt), hipMemcpyHostToDevice, e->ingS),
                 "raw pkts");
   if (raw_len) HIPCHK(hipMemcpyAsync(x.dArenaOwn, raw, raw_len, hipMemcpyHostToDevice, e->ingS), "raw arena");
@@ -4215,6 +4235,155 @@ int lkf_ingest_device(lkf_engine *e, const lkf_raw_pkt *d_pkts, uint32_t n, cons
     e->hp[8] += 1;
   }
   return rc;
+}
+
+// ---- SRTP unprotect (in front of ingress) ---------------------------------------
+static int srtp_rx_init(lkf_engine *e) {
+  int rc = srtp_init(e);
+  if (rc) return rc;
+  if (e->dSrtpRx) return LKF_OK;
+  const uint32_t mp = e->cfg.max_batch_pkts;
+  HIPCHK(e->dSrtpRxSpec.alloc(e->maxStreams), "alloc srtp rx spec state");
+  HIPCHK(e->dRxRange.alloc(2 * size_t(e->maxStreams)), "alloc srtp rx ranges");
+  HIPCHK(e->dRxAuth.alloc(mp), "alloc srtp rx auth");
+  HIPCHK(e->dRxSpec.alloc(mp), "alloc srtp rx spec");
+  HIPCHK(e->dRxRes.alloc(mp), "alloc srtp rx results");
+  for (auto &r : e->rxRing)
+    for (auto &ev : r) HIPCHK(ev.create(true), "unprotect event");
+  HIPCHK(e->dSrtpRx.alloc(e->maxStreams), "alloc srtp rx state");
+  HIPCHK(hipMemsetAsync(e->dSrtpRx, 0, sizeof(SrtpRx) * e->maxStreams, e->own), "srtp rx init");
+  HIPCHK(hipStreamSynchronize(e->own), "srtp rx init sync");
+  return LKF_OK;
+}
+
+int lkf_set_stream_transport(lkf_engine *e, int32_t stream, int32_t t) {
+  if (!e || stream < 0 || stream >= int32_t(e->streams.size()) || t < -1 || t >= int32_t(e->transports.size()))
+    return LKF_EINVAL;
+  int rc = srtp_rx_init(e);
+  if (rc) return rc;
+  rc = drain_streams(e);  // queued unprotect stages read the binding and the state
+  if (rc) return rc;
+  SrtpRx v;
+  std::memset(&v, 0, sizeof(v));
+  v.tp1 = uint32_t(t + 1);
+  HIPCHK(hipMemcpy(e->dSrtpRx + stream, &v, sizeof(v), hipMemcpyHostToDevice), "srtp rx bind");
+  return LKF_OK;
+}
+
+// Enqueues the unprotect stage on the ingest stream (no host sync).
+static int unprotect_common(lkf_engine *e, const lkf_raw_pkt *dPkts, uint32_t n, const uint8_t *dSrtp,
+                            uint64_t srtpLen, lkf_raw_pkt *dPktsOut, uint8_t *dPlain) {
+  SrtpRxArgs a;
+  a.tab = e->dAesTab;
+  a.pkts = dPkts;
+  a.n = n;
+  a.nstreams = uint32_t(e->streams.size());
+  a.srtp = dSrtp;
+  a.srtpLen = srtpLen;
+  a.pktsOut = dPktsOut;
+  a.plain = dPlain;
+  a.rx = e->dSrtpRx;
+  a.rxSpec = e->dSrtpRxSpec;
+  a.range = e->dRxRange;
+  a.keys = e->dSrtpKeys;
+  a.spec = e->dRxSpec;
+  a.auth = e->dRxAuth;
+  a.res = e->dRxRes;
+  const size_t slot = e->nUnprotects % 256;
+  HIPCHK(hipEventRecord(e->rxRing[slot][0], e->ingS), "event");
+  HIPCHK(launch_srtp_unprotect(e->ingS, a), "unprotect");
+  HIPCHK(hipEventRecord(e->rxRing[slot][1], e->ingS), "event");
+  e->nUnprotects++;
+  e->lastUnprotectN = n;
+  return LKF_OK;
+}
+
+int lkf_unprotect_device(lkf_engine *e, const lkf_raw_pkt *d_pkts, uint32_t n, const uint8_t *d_srtp,
+                         uint64_t srtp_len, lkf_raw_pkt *d_pkts_out, uint8_t *d_plain) {
+  if (!e || (n && (!d_pkts || !d_srtp || !d_pkts_out || !d_plain))) return LKF_EINVAL;
+  if (n > e->cfg.max_batch_pkts) return LKF_ENOSPC;
+  if (n) {
+    const uintptr_t s0 = reinterpret_cast<uintptr_t>(d_srtp), p0 = reinterpret_cast<uintptr_t>(d_plain);
+    if ((s0 | p0) & 15) {
+      e->err = "lkf_unprotect_device: the arenas must be 16-byte aligned";
+      return LKF_EINVAL;
+    }
+    if (s0 < p0 + srtp_len && p0 < s0 + srtp_len) {
+      e->err = "lkf_unprotect_device: the plaintext arena overlaps the input";
+      return LKF_EINVAL;
+    }
+  }
+  int rc = srtp_rx_init(e);
+  if (rc) return rc;
+  HIPCHK(hipSetDevice(e->dev), "hipSetDevice");
+  return unprotect_common(e, d_pkts, n, d_srtp, srtp_len, d_pkts_out, d_plain);
+}
+
+int lkf_ingest_srtp(lkf_engine *e, const lkf_raw_pkt *pkts, uint32_t n, const uint8_t *srtp, uint64_t srtp_len) {
+  if (!e || (n && (!pkts || !srtp))) return LKF_EINVAL;
+  if (n > e->cfg.max_batch_pkts || srtp_len > e->cfg.max_batch_arena) return LKF_ENOSPC;
+  int rc = flush_topology(e);
+  if (rc) return rc;
+  rc = srtp_rx_init(e);
+  if (rc) return rc;
+  HIPCHK(hipSetDevice(e->dev), "hipSetDevice");
+  if (!e->dSrtpStage) {
+    HIPCHK(e->dSrtpStage.alloc(e->cfg.max_batch_arena + 64), "alloc srtp staging");
+    HIPCHK(e->dSrtpPktsIn.alloc(e->cfg.max_batch_pkts), "alloc srtp staging");
+  }
+  BatchCtx &x = e->ctx[e->nRuns % lkf_engine::kCtx];
+  rc = ingest_staging_waits(e, x);
+  if (rc) return rc;
+  if (n) HIPCHK(hipMemcpyAsync(e->dSrtpPktsIn, pkts, size_t(n) * sizeof(lkf_raw_pkt), hipMemcpyHostToDevice, e->ingS),
+                "srtp pkts");
+  if (srtp_len) HIPCHK(hipMemcpyAsync(e->dSrtpStage, srtp, srtp_len, hipMemcpyHostToDevice, e->ingS), "srtp arena");
+  HIPCHK(hipStreamSynchronize(e->ingS), "ingest copy sync");  // the host buffers are reusable on return
+  rc = unprotect_common(e, e->dSrtpPktsIn, n, e->dSrtpStage, srtp_len, x.dRawPkts, x.dArenaOwn);
+  if (rc) return rc;
+  return ingest_common(e, x, x.dRawPkts, n, x.dArenaOwn, srtp_len);
+}
+
+int lkf_unprotect_results(lkf_engine *e, lkf_srtp_rx_result *out, uint32_t cap, uint32_t *n_out) {
+  if (!e || !n_out) return LKF_EINVAL;
+  *n_out = e->lastUnprotectN;
+  if (cap < e->lastUnprotectN) return LKF_ENOSPC;
+  HIPCHK(hipSetDevice(e->dev), "hipSetDevice");
+  HIPCHK(hipStreamSynchronize(e->ingS), "sync");
+  if (e->lastUnprotectN) D2H(out, e->dRxRes, size_t(e->lastUnprotectN) * sizeof(lkf_srtp_rx_result), "unprotect results");
+  return LKF_OK;
+}
+
+int lkf_stream_srtp_get(lkf_engine *e, int32_t stream, lkf_stream_srtp *out) {
+  if (!e || !out || stream < 0 || stream >= int32_t(e->streams.size())) return LKF_EINVAL;
+  std::memset(out, 0, sizeof(*out));
+  out->transport = -1;
+  if (!e->dSrtpRx) return LKF_OK;  // no stream was ever bound
+  int rc = drain_streams(e);
+  if (rc) return rc;
+  SrtpRx s;
+  D2H(&s, e->dSrtpRx + stream, sizeof(s), "srtp rx state copy");
+  out->s_l = s.sl;
+  out->mask = s.mask;
+  out->started = s.started;
+  out->transport = int32_t(s.tp1) - 1;
+  out->accepted = s.accepted;
+  out->auth_failures = s.authFail;
+  out->replays = s.replay;
+  out->malformed = s.malformed;
+  return LKF_OK;
+}
+
+int lkf_unprotect_timing_window(lkf_engine *e, uint32_t n, float *unprotect_ms) {
+  if (!e || n == 0 || n > 256 || n > e->nUnprotects) return LKF_EINVAL;
+  float sum = 0;
+  for (uint64_t r = e->nUnprotects - n; r < e->nUnprotects; r++) {
+    HIPCHK(hipEventSynchronize(e->rxRing[r % 256][1]), "evsync");
+    float a = 0;
+    HIPCHK(hipEventElapsedTime(&a, e->rxRing[r % 256][0], e->rxRing[r % 256][1]), "elapsed");
+    sum += a;
+  }
+  if (unprotect_ms) *unprotect_ms = sum;
+  return LKF_OK;
 }
 
 int lkf_ingest_flows(lkf_engine *e, lkf_flow *out, uint32_t cap, uint32_t *n_out) {

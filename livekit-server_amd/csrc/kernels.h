@@ -5,6 +5,7 @@
 
 #include "../../include/lkfwd.h"
 #include "fwd_state.h"
+#include "srtp_rx_device.h"
 
 namespace lkf {
 
@@ -334,6 +335,31 @@ hipError_t launch_srtp_keys(hipStream_t s, const lkf_transport_params *in, uint3
                             const uint32_t *tab, SrtpKeys *keys);
 hipError_t launch_srtp_protect(hipStream_t s, const SrtpProtectArgs &a, uint32_t ndts, const uint32_t *perm,
                                const uint64_t *recBase, const uint32_t *fwdCnt);
+
+// ---- SRTP unprotect (srtp_kernels.hip; the recurrence is srtp_rx_device.h) ----
+struct SrtpRxSpec {  // per datagram, k_srtp_rx_index -> k_srtp_unprotect / k_srtp_rx_commit
+  uint64_t v;        // the speculated packet index
+  uint32_t st;       // the verdict before authentication (LKF_SRTP_RX_*)
+  uint32_t h;        // header length
+};
+struct SrtpRxArgs {  // the three kernels' arguments
+  const uint32_t *tab;  // AES te[256] + S-box
+  const lkf_raw_pkt *pkts;
+  uint32_t n;
+  uint32_t nstreams;
+  const uint8_t *srtp;
+  uint64_t srtpLen;
+  lkf_raw_pkt *pktsOut;
+  uint8_t *plain;
+  SrtpRx *rx;        // per stream: the committed state
+  SrtpRx *rxSpec;    // per stream: the state if every checked packet authenticates
+  uint32_t *range;   // per stream: first datagram of the call, ~last (0xffffffff each: none)
+  const SrtpKeys *keys;
+  SrtpRxSpec *spec;  // per datagram
+  uint32_t *auth;    // per datagram: 1 = the tag matched under spec.v's ROC
+  lkf_srtp_rx_result *res;
+};
+hipError_t launch_srtp_unprotect(hipStream_t s, const SrtpRxArgs &a);
 
 hipError_t launch_seq_lookup(hipStream_t s, DTHot *hot, SeqMeta *seq, uint32_t seqSize, uint8_t *srm,
                              uint64_t srmStride, uint32_t srmCap, uint32_t d,

@@ -24,6 +24,9 @@
 //                  written packet + ROC and the 10-byte tag.  The work is
 //                  VALU/LDS-bound (≈10 AES rounds per 16 B and 80 SHA-1 rounds
 //                  per 64 B), not HBM-bound.
+// The receive direction (unprotect in front of ingress: k_srtp_rx_index,
+// k_srtp_unprotect, k_srtp_rx_commit) follows the protect kernel below and
+// shares its AES, SHA-1 and GHASH code.
 // =============================================================================
 #include <hip/hip_runtime.h>
 
@@ -601,6 +604,464 @@ __global__ void __launch_bounds__(SRTP_T) k_srtp_protect(SrtpProtectArgs A) {
   gcm_ghash_wave(A.keys, g, gcm, sGt[tid >> 6], sL4);
 }
 
+// ---- unprotect ----------------------------------------------------------------
+// The receive direction (include/lkfwd.h "SRTP unprotect"): per stream a serial
+// recurrence (index estimate, replay window) around per-packet crypto.
+//   k_srtp_rx_range   one lane per datagram: each bound stream's first and last
+//                     datagram of the call (atomic min)
+//   k_srtp_rx_index   one wave per stream over that range, 64 datagrams at a
+//                     time: lane-parallel parse, then the recurrence over the
+//                     stream's lanes in order (wave-uniform, state in
+//                     registers) under the speculation that every checked
+//                     packet authenticates; writes each datagram's speculated
+//                     index and verdict and the stream's speculated state
+//   k_srtp_unprotect  one lane per datagram, the mirror of k_srtp_protect: one
+//                     pass in 64-byte blocks, SHA-1 over the ciphertext as
+//                     loaded, keystream XORed for the store, all tag bytes
+//                     compared; GCM through the per-wave GHASH tables; every
+//                     datagram that parsed, whatever its replay verdict
+//   k_srtp_rx_commit  one wave per stream: nothing failed -> the speculated
+//                     state becomes the state; otherwise one forward walk over
+//                     the stream's datagrams with the true outcomes, a datagram
+//                     whose index did not change keeping its crypto result
+//                     (k_srtp_unprotect opens replay-rejected datagrams too, so
+//                     one that was speculatively a duplicate of a packet that
+//                     then failed has one), any other authenticated and
+//                     decrypted there (the rare path within the rare path:
+//                     one lane, the T-table read from global memory)
+using srtprx::Parsed;
+
+__device__ __forceinline__ u32 rx_tag_len(const SrtpKeys *K) {
+  return K->profile == LKF_SRTP_AEAD_AES_128_GCM ? 16u : 10u;
+}
+
+// Stores the first `valid` bytes of the 16-B chunk at byte `base` of the
+// packet (never a byte past them: the output arena ends where the input's does)
+__device__ __forceinline__ void store_chunk(u8 *dstB, u32 base, uint4 ch, u32 valid) {
+  if (valid >= 16) {
+    *reinterpret_cast<uint4 *>(dstB + base) = ch;
+    return;
+  }
+#pragma unroll
+  for (u32 j = 0; j < 4; j++) {
+    const u32 w = j == 0 ? ch.x : j == 1 ? ch.y : j == 2 ? ch.z : ch.w;
+    if (4 * j + 4 <= valid) {
+      *reinterpret_cast<u32 *>(dstB + base + 4 * j) = w;
+    } else {
+      for (u32 k = 0; k < 4; k++)
+        if (4 * j + k < valid) dstB[base + 4 * j + k] = u8(w >> (8 * k));
+    }
+  }
+}
+
+// AES_CM_128_HMAC_SHA1_80 of one datagram with rollover counter `roc`: true if
+// the tag matches.  The plaintext (header || payload, len - 10 bytes) is
+// written either way.
+template <class Tab>
+__device__ bool unprotect_cm(const Tab &tb, const SrtpKeys *K, const u8 *srcB, u8 *dstB, u32 len, u32 hw, u32 roc) {
+  const uint4 *src = reinterpret_cast<const uint4 *>(srcB);
+  const RkG rk{K->rk};
+  const u32 M = len - 10;  // the authenticated portion
+  const uint4 c0v = src[0];
+  const u32 ssrc = bswap(c0v.z), seq = bswap(c0v.x) & 0xFFFF;
+  const u32 ctr0 = K->salt[0], ctr1 = K->salt[1] ^ ssrc, ctr2 = K->salt[2] ^ roc, ctr3 = K->salt[3] ^ (seq << 16);
+  u32 hs[5];
+  for (int k = 0; k < 5; k++) hs[k] = K->ih[k];
+  const u32 sft = (0u - hw) & 3;   // keystream window offset of message word 0
+  int blk0 = -int((hw + 3) >> 2);  // AES block index of window slot 0
+  u32 win[20];
+#pragma unroll
+  for (int k = 0; k < 4; k++) win[k] = 0;
+  const u64 L = u64(M) + 4;
+  const u64 bits = (64 + L) * 8;
+  const u32 nb = u32((L + 9 + 63) / 64);
+  const u64 tail = (u64(roc) << 32) | 0x80000000ull;
+  for (u32 b = 0; b < nb; b++) {
+    uint4 ch[4];
+#pragma unroll
+    for (int c = 0; c < 4; c++) ch[c] = (64 * b + 16 * c < M) ? src[4 * b + c] : make_uint4(0, 0, 0, 0);
+#pragma unroll
+    for (int k = 1; k <= 4; k++) {
+      u32 a0 = ctr0, a1 = ctr1, a2 = ctr2, a3 = ctr3 + u32(blk0 + k);
+      aes_encrypt(tb, rk, a0, a1, a2, a3);
+      win[4 * k] = a0;
+      win[4 * k + 1] = a1;
+      win[4 * k + 2] = a2;
+      win[4 * k + 3] = a3;
+    }
+    // inner HMAC message words from the ciphertext as loaded:
+    // packet[0 : M] || ROC || 0x80 || 0... || length
+    u32 W[16];
+#pragma unroll
+    for (int j = 0; j < 16; j++) {
+      const u32 v = (j & 3) == 0 ? ch[j >> 2].x : (j & 3) == 1 ? ch[j >> 2].y : (j & 3) == 2 ? ch[j >> 2].z : ch[j >> 2].w;
+      const long long dlt = (long long)M - 4ll * (16ll * b + j);
+      if (dlt >= 4) {
+        W[j] = bswap(v);
+      } else if (dlt > 0) {
+        W[j] = (bswap(v) & (0xFFFFFFFFu << (8 * (4 - int(dlt))))) | u32(tail >> (32 + 8 * int(dlt)));
+      } else {
+        const long long q = -dlt;
+        W[j] = q < 8 ? u32((tail << (8 * int(q))) >> 32) : 0u;
+      }
+    }
+    if (b == nb - 1) {
+      W[14] = u32(bits >> 32);
+      W[15] = u32(bits);
+    }
+    // plaintext
+#pragma unroll
+    for (int j = 0; j < 16; j++) {
+      u32 &v = (j & 3) == 0 ? ch[j >> 2].x : (j & 3) == 1 ? ch[j >> 2].y : (j & 3) == 2 ? ch[j >> 2].z : ch[j >> 2].w;
+      if (16 * b + u32(j) >= hw) {
+        const u32 ks = sft == 0 ? win[j] : sft == 1 ? win[j + 1] : sft == 2 ? win[j + 2] : win[j + 3];
+        v ^= bswap(ks);
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < 4; c++) {
+      const u32 base = 64 * b + 16 * c;
+      if (base < M) store_chunk(dstB, base, ch[c], M - base);
+    }
+    sha1_block(hs, W);
+#pragma unroll
+    for (int k = 0; k < 4; k++) win[k] = win[16 + k];
+    blk0 += 4;
+  }
+  u32 ho[5] = {K->oh[0], K->oh[1], K->oh[2], K->oh[3], K->oh[4]};
+  {
+    u32 w[16] = {hs[0], hs[1], hs[2], hs[3], hs[4], 0x80000000u, 0, 0, 0, 0, 0, 0, 0, 0, 0, (64 + 20) * 8};
+    sha1_block(ho, w);
+  }
+  const u8 *tag = srcB + M;
+  u32 diff = 0;
+#pragma unroll
+  for (int k = 0; k < 10; k++) diff |= u32(tag[k]) ^ ((ho[k / 4] >> (24 - 8 * (k & 3))) & 255);
+  return diff == 0;
+}
+
+// AEAD_AES_128_GCM open of one datagram, CTR half (the mirror of protect_gcm):
+// writes the plaintext (len - 16 bytes) and leaves E(K, J0) and the GHASH
+// inputs — the header and the ciphertext where they were received — in g.
+template <class Tab>
+__device__ void open_gcm(const Tab &tb, const SrtpKeys *K, const u8 *srcB, u8 *dstB, u32 len, u32 hw, u32 roc,
+                         GcmDefer &g) {
+  const uint4 *src = reinterpret_cast<const uint4 *>(srcB);
+  const RkG rk{K->rk};
+  const u32 M = len - 16;
+  const uint4 c0v = src[0];
+  const u32 ssrc = bswap(c0v.z), seq = bswap(c0v.x) & 0xFFFF;
+  const u32 iv0 = (ssrc >> 16) ^ K->salt[0], iv1 = ((ssrc << 16) | (roc >> 16)) ^ K->salt[1],
+            iv2 = ((roc << 16) | seq) ^ K->salt[2];
+  const u32 ch0 = (hw + 3) >> 2, sft = 4 * ch0 - hw;
+  u32 win[8];
+  auto ks = [&](int q, u32 *o) {
+    u32 a0 = iv0, a1 = iv1, a2 = iv2, a3 = u32(2 + q);
+    aes_encrypt(tb, rk, a0, a1, a2, a3);
+    o[0] = a0, o[1] = a1, o[2] = a2, o[3] = a3;
+  };
+  ks(-int(ch0), win);
+  ks(1 - int(ch0), win + 4);
+  const u32 nch = (M + 15) / 16;
+  for (u32 c = 0; c < nch; c++) {
+    if (c) {
+#pragma unroll
+      for (int k = 0; k < 4; k++) win[k] = win[4 + k];
+      ks(int(c) + 1 - int(ch0), win + 4);
+    }
+    uint4 ch = c ? src[c] : c0v;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      u32 &v = j == 0 ? ch.x : j == 1 ? ch.y : j == 2 ? ch.z : ch.w;
+      if (4 * c + u32(j) >= hw) {
+        const u32 kw = sft + u32(j);
+        v ^= bswap(kw == 0 ? win[0] : kw == 1 ? win[1] : kw == 2 ? win[2] : kw == 3 ? win[3] : kw == 4 ? win[4]
+                                                                                                 : kw == 5 ? win[5] : win[6]);
+      }
+    }
+    store_chunk(dstB, 16 * c, ch, M - 16 * c);
+  }
+  u32 e0 = iv0, e1 = iv1, e2 = iv2, e3 = 1u;  // E(K, J0)
+  aes_encrypt(tb, rk, e0, e1, e2, e3);
+  g.dst = const_cast<uint4 *>(src);  // read only
+  g.len = M;
+  g.hw = hw;
+  g.ej[0] = e0, g.ej[1] = e1, g.ej[2] = e2, g.ej[3] = e3;
+}
+
+// GHASH(H, A = header, C) of the wave's deferred GCM datagrams as
+// gcm_ghash_wave computes it, each compared (all 16 bytes) with the tag that
+// follows its ciphertext.  Every lane of the wave calls it; true: the tag matches.
+__device__ bool gcm_verify_wave(const SrtpKeys *keys, const GcmDefer &g, bool on, uint4 *M, const u32 *L4) {
+  const u32 lane = threadIdx.x & 63;
+  u64 pend = __ballot(on);
+  bool ok = false;
+  while (pend) {
+    const u32 key = __shfl(g.key, __ffsll((long long)pend) - 1);
+    if (lane < 16) {  // this transport's table: lane n builds M[n]
+      const SrtpKeys &K = keys[key];
+      u32 b[4] = {K.ih[0], K.ih[1], K.ih[2], K.ih[3]};  // H = M[8]
+      u32 m[4] = {0, 0, 0, 0};
+#pragma unroll
+      for (int bit = 3; bit >= 0; bit--) {
+        if ((lane >> bit) & 1) m[0] ^= b[0], m[1] ^= b[1], m[2] ^= b[2], m[3] ^= b[3];
+        const u32 r = 0xE1000000u & (0u - (b[3] & 1u));  // * x
+        b[3] = (b[3] >> 1) | (b[2] << 31);
+        b[2] = (b[2] >> 1) | (b[1] << 31);
+        b[1] = (b[1] >> 1) | (b[0] << 31);
+        b[0] = (b[0] >> 1) ^ r;
+      }
+      M[lane] = make_uint4(m[0], m[1], m[2], m[3]);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    const bool mine = on && g.key == key;
+    if (mine) {
+      const u32 *ow = reinterpret_cast<const u32 *>(g.dst);
+      const u32 hw = g.hw, lc = g.len - 4 * g.hw;  // ciphertext bytes
+      u32 y[4] = {0, 0, 0, 0};
+      for (u32 blk = 0; 4 * blk < hw; blk++) {
+#pragma unroll
+        for (int j = 0; j < 4; j++) y[j] ^= (4 * blk + j < hw) ? bswap(ow[4 * blk + j]) : 0u;
+        gf_mul_tab(y, M, L4);
+      }
+      for (u32 blk = 0; 16 * blk < lc; blk++) {
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+          const int left = int(lc) - int(16 * blk + 4 * j);  // bytes of this word inside the ciphertext
+          const u32 v = left > 0 ? bswap(ow[hw + 4 * blk + j]) : 0u;
+          y[j] ^= left >= 4 ? v : left > 0 ? (v & (0xFFFFFFFFu << (8 * (4 - left)))) : 0u;
+        }
+        gf_mul_tab(y, M, L4);
+      }
+      y[1] ^= 32u * hw;  // len(A) || len(C) in bits
+      y[3] ^= 8u * lc;
+      gf_mul_tab(y, M, L4);
+      const u8 *tag = reinterpret_cast<const u8 *>(g.dst) + g.len;
+      u32 diff = 0;
+#pragma unroll
+      for (int k = 0; k < 16; k++) diff |= u32(tag[k]) ^ (((g.ej[k / 4] ^ y[k / 4]) >> (24 - 8 * (k & 3))) & 255);
+      ok = diff == 0;
+    }
+    pend &= ~__ballot(mine);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // table reads done before the next rebuild
+    __builtin_amdgcn_wave_barrier();
+  }
+  return ok;
+}
+
+__global__ void k_srtp_rx_range(SrtpRxArgs A) {
+  const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= A.n) return;
+  const u32 s = A.pkts[i].stream;
+  if (s >= A.nstreams || A.rx[s].tp1 == 0) return;
+  atomicMin(A.range + 2 * s, i);
+  atomicMin(A.range + 2 * s + 1, ~i);
+}
+
+// the stream of wave `s` and its datagram range [lo, hi) of the call; false: nothing to do
+__device__ __forceinline__ bool rx_stream_range(const SrtpRxArgs &A, u32 s, u32 &lo, u32 &hi) {
+  if (s >= A.nstreams || A.rx[s].tp1 == 0) return false;
+  lo = A.range[2 * s];
+  if (lo == 0xffffffffu) return false;
+  hi = ~A.range[2 * s + 1] + 1;
+  return hi <= A.n;
+}
+
+__global__ void __launch_bounds__(64) k_srtp_rx_index(SrtpRxArgs A) {
+  const u32 s = blockIdx.x, lane = threadIdx.x;
+  u32 lo, hi;
+  if (!rx_stream_range(A, s, lo, hi)) return;
+  SrtpRx st = A.rx[s];
+  const u32 tag = rx_tag_len(A.keys + (st.tp1 - 1));
+  for (u32 base = lo; base < hi; base += 64) {
+    const u32 i = base + lane;
+    bool mine = false;
+    Parsed pr{1, 0, 0};
+    if (i < hi) {
+      const lkf_raw_pkt rp = A.pkts[i];
+      mine = rp.stream == s;
+      if (mine) pr = srtprx::parse(A.srtp, A.srtpLen, rp.off, rp.len, tag);
+    }
+    u64 m = __ballot(mine);
+    u64 myV = 0;
+    u32 mySt = LKF_SRTP_RX_MALFORMED;
+    while (m) {  // the stream's datagrams of this chunk, in order (wave-uniform)
+      const u32 k = u32(__ffsll((long long)m)) - 1;
+      m &= m - 1;
+      const u32 mal = __shfl(pr.malformed, k), seq = __shfl(pr.seq, k);
+      u64 v = 0;
+      u32 stt = LKF_SRTP_RX_MALFORMED;
+      if (!mal) stt = srtprx::check(st, seq, v);
+      if (stt == LKF_SRTP_RX_OK)
+        srtprx::accept(st, v);
+      else
+        srtprx::count_reject(st, stt);
+      if (lane == k) {
+        myV = v;
+        mySt = stt;
+      }
+    }
+    if (mine) A.spec[i] = SrtpRxSpec{myV, mySt, pr.h};
+  }
+  if (lane == 0) A.rxSpec[s] = st;
+}
+
+// One datagram's crypto for lane `on` lanes of the wave (every lane calls it:
+// the GCM tag check is a wave pass): true if it authenticates under `roc`.
+template <class Tab>
+__device__ bool rx_crypto_wave(const SrtpRxArgs &A, const Tab &tb, bool on, const lkf_raw_pkt &rp, u32 h, u32 roc,
+                               u32 key, uint4 *sGt, const u32 *sL4) {
+  GcmDefer g{};
+  bool ok = false, gcm = false;
+  if (on) {
+    const SrtpKeys *K = A.keys + key;
+    if (K->profile == LKF_SRTP_AEAD_AES_128_GCM) {
+      open_gcm(tb, K, A.srtp + rp.off, A.plain + rp.off, rp.len, h / 4, roc, g);
+      g.key = key;
+      gcm = true;
+    } else {
+      ok = unprotect_cm(tb, K, A.srtp + rp.off, A.plain + rp.off, rp.len, h / 4, roc);
+    }
+  }
+  const bool gok = gcm_verify_wave(A.keys, g, gcm, sGt, sL4);
+  return gcm ? gok : ok;
+}
+
+__global__ void __launch_bounds__(SRTP_T) k_srtp_unprotect(SrtpRxArgs A) {
+  __shared__ u32 sTe[256 * 32];
+  __shared__ uint4 sGt[SRTP_T / 64][16];  // per-wave GHASH table
+  __shared__ u32 sL4[16];
+  const u32 tid = threadIdx.x;
+  for (u32 k = tid; k < 256 * 32; k += SRTP_T) sTe[k] = A.tab[k >> 5];
+  if (tid < 16)
+    sL4[tid] = ((tid & 1) ? 0x1C20u : 0u) ^ ((tid & 2) ? 0x3840u : 0u) ^ ((tid & 4) ? 0x7080u : 0u) ^
+               ((tid & 8) ? 0xE100u : 0u);
+  __syncthreads();
+  const u32 i = blockIdx.x * SRTP_T + tid;
+  const AesLds tb{sTe, tid & 31};
+  lkf_raw_pkt rp{};
+  SrtpRxSpec sp{0, LKF_SRTP_RX_MALFORMED, 0};
+  bool crypt = false;
+  u32 key = 0, tag = 0;
+  if (i < A.n) {
+    rp = A.pkts[i];
+    const u32 tp1 = rp.stream < A.nstreams ? A.rx[rp.stream].tp1 : 0xffffffffu;
+    if (tp1 == 0) {  // unbound: the datagram passes through
+      if (u64(rp.off) + rp.len <= A.srtpLen) {
+        if ((rp.off & 15) == 0) {
+          for (u32 b = 0; b < rp.len; b += 16)
+            store_chunk(A.plain + rp.off, b, *reinterpret_cast<const uint4 *>(A.srtp + rp.off + b), rp.len - b);
+        } else {
+          for (u32 k = 0; k < rp.len; k++) A.plain[rp.off + k] = A.srtp[rp.off + k];
+        }
+        sp.st = LKF_SRTP_RX_OK;
+      }
+    } else if (tp1 != 0xffffffffu) {
+      sp = A.spec[i];
+      key = tp1 - 1;
+      tag = rx_tag_len(A.keys + key);
+      // replay-rejected datagrams are opened as well (their verdict stands):
+      // should an earlier packet fail to authenticate, the commit walk finds
+      // their crypto result instead of opening them one lane at a time
+      crypt = sp.st != LKF_SRTP_RX_MALFORMED;
+    }
+  }
+  const bool ok = rx_crypto_wave(A, tb, crypt, rp, sp.h, u32(sp.v >> 16), key, sGt[tid >> 6], sL4);
+  if (i >= A.n) return;
+  if (crypt) {
+    A.auth[i] = ok ? 1u : 0u;
+    if (!ok && sp.st == LKF_SRTP_RX_OK) sp.st = LKF_SRTP_RX_AUTH;
+  }
+  const u32 outLen = sp.st == LKF_SRTP_RX_OK ? rp.len - tag : 0u;
+  A.res[i] = lkf_srtp_rx_result{sp.v, sp.st, outLen};
+  rp.len = outLen;
+  A.pktsOut[i] = rp;
+}
+
+__global__ void __launch_bounds__(64) k_srtp_rx_commit(SrtpRxArgs A) {
+  __shared__ uint4 sGt[16];
+  __shared__ u32 sL4[16];
+  const u32 s = blockIdx.x, lane = threadIdx.x;
+  u32 lo, hi;
+  if (!rx_stream_range(A, s, lo, hi)) return;
+  bool fail = false;
+  for (u32 base = lo; base < hi; base += 64) {
+    const u32 i = base + lane;
+    if (i < hi && A.pkts[i].stream == s && A.spec[i].st == LKF_SRTP_RX_OK && !A.auth[i]) fail = true;
+  }
+  if (__ballot(fail) == 0) {  // the speculation held
+    if (lane == 0) A.rx[s] = A.rxSpec[s];
+    return;
+  }
+  // a failed authentication: the walk with the true outcomes
+  if (lane < 16)
+    sL4[lane] = ((lane & 1) ? 0x1C20u : 0u) ^ ((lane & 2) ? 0x3840u : 0u) ^ ((lane & 4) ? 0x7080u : 0u) ^
+                ((lane & 8) ? 0xE100u : 0u);
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  const AesTab tb{A.tab, reinterpret_cast<const u8 *>(A.tab + 256)};
+  SrtpRx st = A.rx[s];
+  const u32 key = st.tp1 - 1;
+  const u32 tag = rx_tag_len(A.keys + key);
+  for (u32 base = lo; base < hi; base += 64) {
+    const u32 i = base + lane;
+    bool mine = false;
+    Parsed pr{1, 0, 0};
+    lkf_raw_pkt rp{};
+    SrtpRxSpec sp{0, LKF_SRTP_RX_MALFORMED, 0};
+    u32 au = 0;
+    if (i < hi) {
+      rp = A.pkts[i];
+      mine = rp.stream == s;
+      if (mine) {
+        pr = srtprx::parse(A.srtp, A.srtpLen, rp.off, rp.len, tag);
+        sp = A.spec[i];
+        au = A.auth[i];
+      }
+    }
+    u64 m = __ballot(mine);
+    u64 myV = 0;
+    u32 mySt = LKF_SRTP_RX_MALFORMED;
+    while (m) {
+      const u32 k = u32(__ffsll((long long)m)) - 1;
+      m &= m - 1;
+      const u32 mal = __shfl(pr.malformed, k), seq = __shfl(pr.seq, k);
+      const u64 sv = (u64(__shfl(u32(sp.v >> 32), k)) << 32) | __shfl(u32(sp.v), k);
+      u64 v = 0;
+      u32 stt = LKF_SRTP_RX_MALFORMED;
+      if (!mal) stt = srtprx::check(st, seq, v);
+      if (stt == LKF_SRTP_RX_OK) {
+        u32 ok;
+        if (sv == v) {  // the index, so the ROC, is the one k_srtp_unprotect opened it with: the result stands
+          ok = __shfl(au, k);
+        } else {
+          ok = rx_crypto_wave(A, tb, lane == k, rp, pr.h, u32(v >> 16), key, sGt, sL4) ? 1u : 0u;
+          ok = __shfl(ok, k);
+        }
+        if (!ok) stt = LKF_SRTP_RX_AUTH;
+      }
+      if (stt == LKF_SRTP_RX_OK)
+        srtprx::accept(st, v);
+      else
+        srtprx::count_reject(st, stt);
+      if (lane == k) {
+        myV = v;
+        mySt = stt;
+      }
+    }
+    if (mine) {
+      const u32 outLen = mySt == LKF_SRTP_RX_OK ? rp.len - tag : 0u;
+      A.res[i] = lkf_srtp_rx_result{myV, mySt, outLen};
+      rp.len = outLen;
+      A.pktsOut[i] = rp;
+    }
+  }
+  if (lane == 0) A.rx[s] = st;
+}
+
 }  // namespace
 
 hipError_t launch_aes_tables(hipStream_t s, uint32_t *tab) {
@@ -620,6 +1081,19 @@ hipError_t launch_srtp_protect(hipStream_t s, const SrtpProtectArgs &a, uint32_t
   if (ndts) hipLaunchKernelGGL(k_srtp_roc, dim3((ndts + 255) / 256), dim3(256), 0, s, a.sd, perm, recBase, fwdCnt, a.out, ndts);
   const u64 g = (a.cap + SRTP_T - 1) / SRTP_T;
   if (g) hipLaunchKernelGGL(k_srtp_protect, dim3(u32(g)), dim3(SRTP_T), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_srtp_unprotect(hipStream_t s, const SrtpRxArgs &a) {
+  if (!a.n) return hipSuccess;
+  if (a.nstreams) {
+    const hipError_t r = hipMemsetAsync(a.range, 0xff, sizeof(u32) * 2 * a.nstreams, s);
+    if (r != hipSuccess) return r;
+    hipLaunchKernelGGL(k_srtp_rx_range, dim3((a.n + 255) / 256), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_srtp_rx_index, dim3(a.nstreams), dim3(64), 0, s, a);
+  }
+  hipLaunchKernelGGL(k_srtp_unprotect, dim3((a.n + SRTP_T - 1) / SRTP_T), dim3(SRTP_T), 0, s, a);
+  if (a.nstreams) hipLaunchKernelGGL(k_srtp_rx_commit, dim3(a.nstreams), dim3(64), 0, s, a);
   return hipGetLastError();
 }
 
