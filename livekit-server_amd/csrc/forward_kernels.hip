@@ -162,7 +162,14 @@ __device__ __forceinline__ uint4 rfl(uint4 v) {  // wave-uniform copy (SGPRs)
 // state is wave-uniform, so the rare-path helpers below spread their loops
 // over the 64 lanes (every lane calls them with the same arguments).
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ u32 lane_id() { return threadIdx.x & 63u; }
+// (volatile: a value derived from the lane index is computed again where it is
+// used, one or two VALU instructions, not hoisted to the kernel's entry and held
+// — or spilled — across the whole DownTrack loop)
+__device__ __forceinline__ u32 lane_id() {
+  u32 l;
+  asm volatile("v_and_b32 %0, 63, %1" : "=v"(l) : "v"(threadIdx.x));
+  return l;
+}
 __device__ __forceinline__ u32 rl32(u32 v, u32 l) { return __builtin_amdgcn_readlane(v, l); }
 __device__ __forceinline__ u64 rl64(u64 v, u32 l) {
   return (u64(rl32(u32(v >> 32), l)) << 32) | u64(rl32(u32(v), l));
@@ -1145,9 +1152,12 @@ struct __attribute__((aligned(8))) U4x8 {  // 16 B at an 8-B aligned address (on
 };
 // a forwarded record (FwdRec): one dwordx4 + one dwordx2 store; its full SN /
 // TS go to the wide side array too when they lie 2^31 or more from the base
+__device__ __forceinline__ bool wide_rec(u64 bSN, u64 bTS, u64 sn, u64 ts) {
+  return (((sn - bSN) + 0x80000000ull) >> 32) != 0 || (((ts - bTS) + 0x80000000ull) >> 32) != 0;
+}
 __device__ __forceinline__ void store_fwd(FwdRec *dst, FwdBase *wdst, u64 bSN, u64 bTS, u64 sn, u64 ts, u32 pkt,
                                           u32 relOff, u32 outLen, u32 flags, u32 ddLen, u32 aux) {
-  if ((((sn - bSN) + 0x80000000ull) >> 32) != 0 || (((ts - bTS) + 0x80000000ull) >> 32) != 0) {
+  if (wide_rec(bSN, bTS, sn, ts)) {
     flags |= T_WIDE;
     *wdst = FwdBase{sn, ts};
   }
@@ -1710,13 +1720,24 @@ struct SsEnt {
   u32 sn, ts;   // low 32 bits of the munged extended SN / TS (widened against FwdBase)
   i64 t;        // arrival (the virtual clock of sendingPacket)
   u32 hp;       // incoming header size | forwarded payload << 16
-  u32 fl;       // 1 marker, 2 key frame
+  u32 fl;       // 1 marker, 2 key frame, 4 wide: SN / TS from the T_WIDE side array at slot fl >> 3
 };
 static_assert(sizeof(SsEnt) == 24, "SsEnt is 24 B");
-__device__ __forceinline__ void ss_put(SsEnt *e, u64 sn, u64 ts, i64 t, u32 hdr, u32 pay, bool marker, bool kf) {
+// (rel: the tuple's slot past the DownTrack's first, where store_fwd put a
+// T_WIDE record's full SN / TS: an entry 2^31 or more from the batch's base
+// cannot be widened from its low 32 bits and is read back from there; the
+// slot shares the flags word: a DownTrack's batch stays far below 2^29 tuples)
+__device__ __forceinline__ void ss_put(SsEnt *e, const LaneOut &o, u32 rel, u64 sn, u64 ts, i64 t, u32 hdr, u32 pay,
+                                       bool marker, bool kf) {
+  const u32 wide = wide_rec(o.bSN, o.bTS, sn, ts) ? 4u | (rel << 3) : 0u;
   *reinterpret_cast<uint2 *>(e) = make_uint2(u32(sn), u32(ts));
   reinterpret_cast<uint2 *>(e)[1] = make_uint2(u32(u64(t)), u32(u64(t) >> 32));
-  reinterpret_cast<uint2 *>(e)[2] = make_uint2(hdr | (pay << 16), (marker ? 1u : 0u) | (kf ? 2u : 0u));
+  reinterpret_cast<uint2 *>(e)[2] = make_uint2(hdr | (pay << 16), (marker ? 1u : 0u) | (kf ? 2u : 0u) | wide);
+}
+__device__ __forceinline__ void ss_wide(const FwdBase *wide, u32 fl, u64 &esn, u64 &ets) {
+  const FwdBase w = wide[fl >> 3];
+  esn = w.sn;
+  ets = w.ts;
 }
 
 // The fold of m entries, lane = entry.  A segment of in-order entries — each
@@ -1733,12 +1754,16 @@ __device__ __forceinline__ void ss_put(SsEnt *e, u64 sn, u64 ts, i64 t, u32 hdr,
 #define LKF_SS_SCALAR 0  // (3 measured slower: headline +1.5 %, tick +1.2 %; r5 A/B)
 #endif
 __device__ __forceinline__ void ss_flush(SenderStats &S, u32 *ring, u32 *gap, const SsEnt *buf, u32 m, u64 bSN,
-                                      u64 bTS) {
+                                      u64 bTS, const FwdBase *wide) {
   if (m <= u32(LKF_SS_SCALAR)) {  // a short chunk (the short ticks): the scalar Update per entry,
     for (u32 i = 0; i < m; i++) {  // cheaper than the segment's cross-lane reductions
       const SsEnt &e = buf[i];
-      ss::ss_update(S, ring, gap, e.t, widen32(bSN, e.sn), widen32(bTS, e.ts), (e.fl & 1) != 0, e.hp & 0xffffu,
-                    e.hp >> 16, 0);
+      u64 esn = widen32(bSN, e.sn), ets = widen32(bTS, e.ts);
+      if (e.fl & 4) {
+        __threadfence();
+        ss_wide(wide, e.fl, esn, ets);
+      }
+      ss::ss_update(S, ring, gap, e.t, esn, ets, (e.fl & 1) != 0, e.hp & 0xffffu, e.hp >> 16, 0);
       if (e.fl & 2) S.keyFrames++;  // UpdateKeyFrame(1) rtpstats_base.go:429-439
       wave_lds_sync();
     }
@@ -1751,6 +1776,7 @@ __device__ __forceinline__ void ss_flush(SenderStats &S, u32 *ring, u32 *gap, co
   i64 t = 0;
   u32 hdr = 0, pay = 0;
   bool marker = false, kf = false;
+  u32 efl = 0;
   if (valid) {
     const SsEnt &e = buf[lane];
     esn = widen32(bSN, e.sn);
@@ -1758,8 +1784,13 @@ __device__ __forceinline__ void ss_flush(SenderStats &S, u32 *ring, u32 *gap, co
     t = e.t;
     hdr = e.hp & 0xffffu;
     pay = e.hp >> 16;
-    marker = e.fl & 1;
-    kf = e.fl & 2;
+    efl = e.fl;
+    marker = efl & 1;
+    kf = efl & 2;
+  }
+  if (__ballot(efl & 4)) {  // (rare) the side array's entries were stored by this wave's lanes in the runs before
+    __threadfence();
+    if (efl & 4) ss_wide(wide, efl, esn, ets);
   }
   const u64 pEsn = sh64(esn, lane ? int(lane) - 1 : 0), pEts = sh64(ets, lane ? int(lane) - 1 : 0);
   u32 pos = 0;
@@ -2009,7 +2040,8 @@ __device__ __forceinline__ void decide_step(Lane &L, const PktV &p, u32 k, LaneO
   // incoming header's size (getTranslatedRTPHeader keeps its extensions) and
   // the forwarded payload, folded at the end of the chunk (ss_flush)
   if (lane_id() == 0)
-    ss_put(o.ssBuf + o.ssN, f.osn, f.ots, p.arr, p.poff, u32(payLen), marker, (p.flags & LKF_PKT_KEYFRAME) != 0);
+    ss_put(o.ssBuf + o.ssN, o, u32(o.nFwd), f.osn, f.ots, p.arr, p.poff, u32(payLen), marker,
+           (p.flags & LKF_PKT_KEYFRAME) != 0);
   o.ssN++;
   o.nFwd++;
   o.nBytes += u64(hdrLen + payLen);
@@ -2066,6 +2098,14 @@ __device__ __forceinline__ void vm_drain() {
 __device__ __forceinline__ void pin_loaded(const uint4 &a, const uint4 &b, const uint4 &c, const uint4 &d) {
   asm volatile("" ::"v"(a.x), "v"(a.y), "v"(a.z), "v"(a.w), "v"(b.x), "v"(b.y), "v"(b.z), "v"(b.w), "v"(c.x),
                "v"(c.y), "v"(c.z), "v"(c.w), "v"(d.x), "v"(d.y), "v"(d.z), "v"(d.w));
+}
+
+// The chunk's raw descriptors, opaque again at the head of every run: what is
+// decoded from them is then computed in the run that uses it (a few bit-field
+// extracts) and is not live, next to the raw registers, across the whole chunk.
+__device__ __forceinline__ void relaunder(uint4 &a, uint4 &b, uint4 &c, uint4 &d) {
+  asm volatile("" : "+v"(a.x), "+v"(a.y), "+v"(a.z), "+v"(a.w), "+v"(b.x), "+v"(b.y), "+v"(b.z), "+v"(b.w),
+                 "+v"(c.x), "+v"(c.y), "+v"(c.z), "+v"(c.w), "+v"(d.x), "+v"(d.y), "+v"(d.z), "+v"(d.w));
 }
 
 __device__ __forceinline__ bool steady_state(const Lane &L) {
@@ -2671,7 +2711,7 @@ __device__ __forceinline__ u32 svc_run(Lane &L, LaneOut &o, const PktV &p, u32 p
       store_rec(L.seq + x2, SeqMeta{});
     }
   }
-  if (f) ss_put(o.ssBuf + o.ssN + j, osn, ots, p.arr, p.poff, p.plen, mk, kf);
+  if (f) ss_put(o.ssBuf + o.ssN + j, o, u32(o.nFwd) + j, osn, ots, p.arr, p.poff, p.plen, mk, kf);
   o.ssN += u32(__popcll(fwR));
   const u32 sumLen = wave_sum_u32(outLen);
   sentAcc += f ? i32(p.poff) - hdrLen : 0;
@@ -2772,12 +2812,28 @@ __device__ __forceinline__ void dd_restage(Lane &L, const DDState *sDD, u8 *sDDS
   if (LKF_DD_RESTAGE && moved) dd_stage_struct(L, sDD, sDDSRaw, lane);
 }
 
+// k_decide_dt reads its arguments where it uses them.  DecideArgs is 368
+// bytes: loaded at the kernel's entry they are live across the whole
+// DownTrack body, far more than the SGPR file holds, and most of them were
+// spilled to VGPR lanes there and read back in the prologue, the chunk loop
+// and the epilogue.  The kernarg segment (DecideArgs is the first argument,
+// at offset 0) is read through the scalar cache instead; the pointer is made
+// opaque again in every scope (prologue, chunk, control ops, epilogue), so a
+// load stays in its scope and is not hoisted to where it would be held.
+typedef const DecideArgs __attribute__((address_space(4))) *DecideArgsK;
+__device__ __forceinline__ DecideArgsK decide_args() {
+  DecideArgsK k = (DecideArgsK)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(k));
+  return k;
+}
+
 constexpr u32 kDecideMaxK = 8;  // schedule slots per decide wave (LKF_DECIDE_K is clamped to it; 8 and 16 measured slower than 4)
 #ifndef LKF_DEC_PREFETCH  // a single-chunk track's packets loaded with the DownTrack's state
 #define LKF_DEC_PREFETCH 0  // (measured: the headline 1.3 % slower with it, the tick flat; r5 A/B)
 #endif
 template <bool DDK>
-__global__ void __launch_bounds__(64) DECIDE_ATTR k_decide_dt(DecideArgs A, const lkf_pkt *__restrict__ pkts) {
+__global__ void __launch_bounds__(64) DECIDE_ATTR k_decide_dt(DecideArgs A_, const lkf_pkt *__restrict__ pkts) {
+  DecideArgsK A = decide_args();  // (A_ itself is not read: its bytes are, through the kernarg segment)
   __shared__ i32 sDrop[kSetCap];
   __shared__ i32 sEx[kSetCap];
   __shared__ i32 sMissKey[kMissCap];
@@ -2804,19 +2860,19 @@ __global__ void __launch_bounds__(64) DECIDE_ATTR k_decide_dt(DecideArgs A, cons
   __shared__ uint4 sSlot[2 * kDecideMaxK];
   u64 todo;
   {
-    const u32 K = A.perWave, lane = threadIdx.x;
-    const u32 wj = A.waveBase + ((blockIdx.x >> 3) * K + lane) * 8 + (blockIdx.x & 7);
+    const u32 K = A->perWave, lane = threadIdx.x;
+    const u32 wj = A->waveBase + ((blockIdx.x >> 3) * K + lane) * 8 + (blockIdx.x & 7);
     u32 dj = 0xffffffffu, tj = 0, ej = 0, eej = 0, pbj = 0, pej = 0, cj = 0;
-    if (lane < K && wj < A.waveEnd) {
-      dj = A.sched[wj];
-      tj = A.waveTrack[wj];
-      ej = A.evOff[wj];
-      eej = A.evOff[wj + 1];
+    if (lane < K && wj < A->waveEnd) {
+      dj = A->sched[wj];
+      tj = A->waveTrack[wj];
+      ej = A->evOff[wj];
+      eej = A->evOff[wj + 1];
     }
     if (dj != 0xffffffffu) {  // (0xffffffff: padding slot of the per-XCD schedule)
-      pbj = A.tBegin[tj];
-      pej = A.tEnd[tj];
-      cj = A.tracks[tj].codec;  // (the VP8 maps are then loaded with the hot state)
+      pbj = A->tBegin[tj];
+      pej = A->tEnd[tj];
+      cj = A->tracks[tj].codec;  // (the VP8 maps are then loaded with the hot state)
     }
     todo = __ballot(dj != 0xffffffffu && (pbj < pej || ej < eej));
     if (lane < K) {
@@ -2828,6 +2884,7 @@ __global__ void __launch_bounds__(64) DECIDE_ATTR k_decide_dt(DecideArgs A, cons
   while (todo) {
   const u32 jw = u32(__ffsll(static_cast<long long>(todo))) - 1;
   todo &= todo - 1;
+  const DecideArgsK A = decide_args();  // (the prologue's reads)
 #if LKF_SVC_STATS
   // per-phase cycles of the SVC DownTracks (g_svc[4..9]: prologue, runs,
   // full steps after runs, chunk tails, epilogue, DownTracks)
@@ -2850,19 +2907,19 @@ __global__ void __launch_bounds__(64) DECIDE_ATTR k_decide_dt(DecideArgs A, cons
   const u32 track = __builtin_amdgcn_readfirstlane(sa.z);
   u32 ev = __builtin_amdgcn_readfirstlane(sa.w);
   const u32 evEnd = __builtin_amdgcn_readfirstlane(sb.x);
-  CHK(d < A.maxDts, CK_DEC_DT, d, A.maxDts);
-  CHK(track < A.maxTracks, CK_DEC_TRACK, track, A.maxTracks);
-  CHK(evEnd <= A.nev, CK_DEC_EVENT, evEnd, A.nev);
-  const DevDT dt = A.dts[d];
+  CHK(d < A->maxDts, CK_DEC_DT, d, A->maxDts);
+  CHK(track < A->maxTracks, CK_DEC_TRACK, track, A->maxTracks);
+  CHK(evEnd <= A->nev, CK_DEC_EVENT, evEnd, A->nev);
+  const DevDT dt = A->dts[d];
   const u32 pb = __builtin_amdgcn_readfirstlane(sb.y);
   u32 pe = __builtin_amdgcn_readfirstlane(sb.z);
-  const u64 slot0 = A.slotBase[d];
+  const u64 slot0 = A->slotBase[d];
   // A track with at most 64 packets in the batch is one chunk: its packets
   // are loaded together with the DownTrack's state (one round trip fewer)
   bool pre = LKF_DEC_PREFETCH && pe - pb <= 64u;  // (cleared once the chunk takes them)
   uint4 r0 = make_uint4(0, 0, 0, 0), r1 = r0, r2 = r0, r3 = r0;
   if (pre && lane < pe - pb) {
-    CHK(pb + lane < A.npkts, CK_DEC_PKT, pb + lane, A.npkts);
+    CHK(pb + lane < A->npkts, CK_DEC_PKT, pb + lane, A->npkts);
     const uint4 *ps = reinterpret_cast<const uint4 *>(pkts) + u64(pb + lane) * 4;
     r0 = ps[0];
     r1 = ps[1];
@@ -2881,36 +2938,36 @@ __global__ void __launch_bounds__(64) DECIDE_ATTR k_decide_dt(DecideArgs A, cons
   __shared__ u32 sHot0[64];  // the state as loaded: only the dwords the batch changes go back
   Lane L{sHot};
   {
-    const u32 h0 = reinterpret_cast<const u32 *>(A.hot + d)[lane];  // 64 dwords
+    const u32 h0 = reinterpret_cast<const u32 *>(A->hot + d)[lane];  // 64 dwords
     reinterpret_cast<u32 *>(&sHot)[lane] = h0;
     sHot0[lane] = h0;
   }
   if (lane < sizeof(SenderStats) / 16)
-    reinterpret_cast<uint4 *>(&sSS)[lane] = reinterpret_cast<const uint4 *>(A.ss + d)[lane];
+    reinterpret_cast<uint4 *>(&sSS)[lane] = reinterpret_cast<const uint4 *>(A->ss + d)[lane];
   // VP8 munger maps live in LDS for the batch: the picture-id sets here, the
   // live entries of the missing-picture ring once the hot state is in
   const bool vp8Track = __builtin_amdgcn_readfirstlane(sb.w) == LKF_CODEC_VP8;
   if (vp8Track && lane < u32(kSetCap)) {
-    sDrop[lane] = A.vc[d].dropKey[lane];
-    sEx[lane] = A.vc[d].exKey[lane];
+    sDrop[lane] = A->vc[d].dropKey[lane];
+    sEx[lane] = A->vc[d].exKey[lane];
   }
   __shared__ __attribute__((aligned(16))) SsEnt sSsBuf[64];  // one chunk's forwarded tuples (ss_flush)
   o.ss = &sSS;
   o.ssBuf = sSsBuf;
   o.ssN = 0;
-  o.ssRing = A.ssRing + size_t(d) * kSnInfoSize;
-  o.ssGap = A.ssGap + size_t(d) * kGapWords;
+  o.ssRing = A->ssRing + size_t(d) * kSnInfoSize;
+  o.ssGap = A->ssGap + size_t(d) * kGapWords;
   __syncthreads();
 #if LKF_SVC_STATS
   const u64 tPa = __builtin_amdgcn_s_memtime();
 #endif
-  RangeEntry *const rmG = A.rm + size_t(d) * kRangeCap;
+  RangeEntry *const rmG = A->rm + size_t(d) * kRangeCap;
   L.rm = sRm;
   L.rmG = rmG;
   L.rmNew = 0;
   L.rmLoaded = false;
   L.vcDirty = false;
-  L.vc = A.vc + d;
+  L.vc = A->vc + d;
   L.dropKey = sDrop;
   L.exKey = sEx;
   L.missKey = sMissKey;
@@ -2922,63 +2979,63 @@ __global__ void __launch_bounds__(64) DECIDE_ATTR k_decide_dt(DecideArgs A, cons
       sMissVal[idx] = L.vc->missVal[idx];
     }
   }
-  if (slot0 + (pe - pb) > A.tupleCap) {  // tuple slots exhausted: skip, flag
-    if (lane == 0) atomicOr(A.err, 8u);
+  if (slot0 + (pe - pb) > A->tupleCap) {  // tuple slots exhausted: skip, flag
+    if (lane == 0) atomicOr(A->err, 8u);
     pe = pb;
   }
   __syncthreads();
-  L.seq = A.seq + size_t(d) * A.seqSize;
-  L.seqSize = A.seqSize;
-  L.srm = DDK ? reinterpret_cast<SeqRM *>(A.srm + size_t(d) * A.srmStride) : nullptr;  // (only <true> reads it)
-  L.srmCap = A.srmCap;
-  const DevTrack &tk = A.tracks[track];
+  L.seq = A->seq + size_t(d) * A->seqSize;
+  L.seqSize = A->seqSize;
+  L.srm = DDK ? reinterpret_cast<SeqRM *>(A->srm + size_t(d) * A->srmStride) : nullptr;  // (only <true> reads it)
+  L.srmCap = A->srmCap;
+  const DevTrack &tk = A->tracks[track];
   L.kind = tk.kind;
   L.codec = tk.codec;
   L.hasRefTS = tk.hasRefTS;
   L.clockRate = tk.clockRate;
-  L.offs = A.dtOffs + size_t(d) * kDTOffsWords;
+  L.offs = A->dtOffs + size_t(d) * kDTOffsWords;
   L.extPlayout = dt.extPlayout;
   L.extAbs = dt.extAbs;
   L.extDD = dt.extDD;
   L.extTcc = dt.extTcc;
-  L.err = A.err;
-  L.ddPkts = A.ddPkts;
+  L.err = A->err;
+  L.ddPkts = A->ddPkts;
   __shared__ __attribute__((aligned(16))) DDPkt sDDPkt;
   L.ddPktL = &sDDPkt;
-  L.ddSpill = A.ddSpill;
+  L.ddSpill = A->ddSpill;
   L.ddRing = nullptr;
   L.ddS = reinterpret_cast<DDStruct *>(sDDSRaw);
   L.ddSSlot = 0xffffffffu;
   L.dd = sDD;
   L.ddBuf = sDDBuf;
-  o.ddArena = A.ddArena;
-  o.ddUsed = A.ddUsed;
-  o.ddCap = A.ddCap;
+  o.ddArena = A->ddArena;
+  o.ddUsed = A->ddUsed;
+  o.ddCap = A->ddCap;
 #if LKF_CHECKED
   o.tupBase = slot0;
-  o.tupCap = A.tupleCap;
-  CHK(pe <= A.npkts, CK_DEC_PKT, pe, A.npkts);
+  o.tupCap = A->tupleCap;
+  CHK(pe <= A->npkts, CK_DEC_PKT, pe, A->npkts);
 #endif
-  const bool ddDT = DDK && (L.h.flags & F_DD) && A.ddState;
+  const bool ddDT = DDK && (L.h.flags & F_DD) && A->ddState;
   if (ddDT) {  // the DD selector state lives in LDS for the batch
-    L.ddRing = A.ddStructs + size_t(tk.ddIdx) * kDDSlots;
-    const uint4 *g = reinterpret_cast<const uint4 *>(A.ddState + d);
+    L.ddRing = A->ddStructs + size_t(tk.ddIdx) * kDDSlots;
+    const uint4 *g = reinterpret_cast<const uint4 *>(A->ddState + d);
     uint4 *l = reinterpret_cast<uint4 *>(sDD);
     // the head and the expectFrames rows of the chains in use (a structure
     // update zeroes every row's count, so rows past them are never read first)
-    const u32 nc0 = __builtin_amdgcn_readfirstlane(u32(A.ddState[d].numChains));
+    const u32 nc0 = __builtin_amdgcn_readfirstlane(u32(A->ddState[d].numChains));
     const u32 nDD = (kDDStateHead + nc0 * kDDExpRow * 8) / 16;
     for (u32 i = lane; i < nDD; i += 64) l[i] = g[i];
     __syncthreads();
     if (sDD->flags & DS_KF_VALID) dd_stage_struct(L, sDD, sDDSRaw, lane);
   }
-  o.outT = A.recs + slot0;
-  o.outW = A.wide + slot0;
+  o.outT = A->recs + slot0;
+  o.outW = A->wide + slot0;
   // SVC DownTracks (one SSRC, every packet relevant to the selector): svc_run
   // (the host schedules them in k_decide_dt<true>)
   const bool svcDT = DDK && (L.h.flags & F_VIDEO) && !(L.h.flags & F_SIMULCAST) &&
                      ((L.h.flags & F_VP9) || ((L.h.flags & F_DD) && ddDT));
-  u32 nextAt = ev < evEnd ? A.events[ev].at : 0xffffffffu;
+  u32 nextAt = ev < evEnd ? A->events[ev].at : 0xffffffffu;
   const uint4 *src = reinterpret_cast<const uint4 *>(pkts);
 
   u32 kpos = pb;  // first packet of the track not yet decided
@@ -2986,13 +3043,15 @@ __global__ void __launch_bounds__(64) DECIDE_ATTR k_decide_dt(DecideArgs A, cons
   const u64 tP1 = __builtin_amdgcn_s_memtime();
 #endif
   while (kpos < pe) {
+    const DecideArgsK A = decide_args();  // (the chunk's reads)
 #if LKF_SVC_STATS
     const u64 tc0 = __builtin_amdgcn_s_memtime();
 #endif
     if (nextAt <= kpos) {
+      const DecideArgsK A = decide_args();
       while (nextAt <= kpos) {
-        apply_ctl(L, A.events[ev++]);
-        nextAt = ev < evEnd ? A.events[ev].at : 0xffffffffu;
+        apply_ctl(L, A->events[ev++]);
+        nextAt = ev < evEnd ? A->events[ev].at : 0xffffffffu;
       }
       vm_drain();
     }
@@ -3008,10 +3067,10 @@ __global__ void __launch_bounds__(64) DECIDE_ATTR k_decide_dt(DecideArgs A, cons
     u32 pi, n, lim;  // lane -> packet index; packets in the chunk; packet index after it
     if (steady) {
       const u32 ls = u32(L.h.curS);
-      CHK(size_t(ls) * A.pktStride + kpos < 3 * size_t(A.pktStride), CK_DEC_LAYER, size_t(ls) * A.pktStride + kpos,
-          3 * size_t(A.pktStride));
-      const u32 j = A.layerBefore[size_t(ls) * A.pktStride + kpos] + lane;
-      pi = j < A.layerCnt[track * 3 + ls] ? A.layerList[size_t(ls) * A.pktStride + pb + j] : 0xffffffffu;
+      CHK(size_t(ls) * A->pktStride + kpos < 3 * size_t(A->pktStride), CK_DEC_LAYER, size_t(ls) * A->pktStride + kpos,
+          3 * size_t(A->pktStride));
+      const u32 j = A->layerBefore[size_t(ls) * A->pktStride + kpos] + lane;
+      pi = j < A->layerCnt[track * 3 + ls] ? A->layerList[size_t(ls) * A->pktStride + pb + j] : 0xffffffffu;
       const u32 stopAt = min(nextAt, pe);
       n = u32(__popcll(__ballot(pi < stopAt)));  // list is increasing: a prefix of the lanes
       lim = n == 64 ? rl32(pi, 63) + 1 : stopAt;
@@ -3024,7 +3083,7 @@ __global__ void __launch_bounds__(64) DECIDE_ATTR k_decide_dt(DecideArgs A, cons
     if (!pre) {  // (pre: the prefetched chunk, pi = pb + lane)
       r0 = r1 = r2 = r3 = make_uint4(0, 0, 0, 0);
       if (valid) {
-        CHK(pi < A.npkts, CK_DEC_PKT, pi, A.npkts);
+        CHK(pi < A->npkts, CK_DEC_PKT, pi, A->npkts);
         const u64 q = u64(pi) * 4;
         r0 = src[q];
         r1 = src[q + 1];
@@ -3042,14 +3101,16 @@ __global__ void __launch_bounds__(64) DECIDE_ATTR k_decide_dt(DecideArgs A, cons
       tLoad += tl0 - tc0;
     }
 #endif
-    const PktV p = decode_pkt(r0, r1, r2, r3);
     u32 pos = 0;
     u32 own = n;  // packets of the chunk decided (steady: the rest of the range is skipped drops)
     while (pos < n) {
+      relaunder(r0, r1, r2, r3);
+      const PktV p = decode_pkt(r0, r1, r2, r3);
       if (nextAt <= rl32(pi, pos)) {
+        const DecideArgsK A = decide_args();
         while (nextAt <= rl32(pi, pos)) {
-          apply_ctl(L, A.events[ev++]);
-          nextAt = ev < evEnd ? A.events[ev].at : 0xffffffffu;
+          apply_ctl(L, A->events[ev++]);
+          nextAt = ev < evEnd ? A->events[ev].at : 0xffffffffu;
         }
         vm_drain();
       }
@@ -3285,7 +3346,7 @@ __global__ void __launch_bounds__(64) DECIDE_ATTR k_decide_dt(DecideArgs A, cons
         fwd_base(o, fwR, osn, ots);
         if (fwd) {
 #if LKF_CHECKED
-          CHK(slot0 + o.nFwd + j < A.tupleCap, CK_DEC_TUPLE, slot0 + o.nFwd + j, A.tupleCap);
+          CHK(slot0 + o.nFwd + j < A->tupleCap, CK_DEC_TUPLE, slot0 + o.nFwd + j, A->tupleCap);
 #endif
           store_fwd(o.outT + o.nFwd + j, o.outW + o.nFwd + j, o.bSN, o.bTS, osn, ots, pi, o.relOff + relEx, outLen,
                     ((p.flags & LKF_PKT_KEYFRAME) ? LKF_OUT_KEYFRAME : 0) | (marker ? LKF_OUT_MARKER : 0) |
@@ -3308,7 +3369,7 @@ __global__ void __launch_bounds__(64) DECIDE_ATTR k_decide_dt(DecideArgs A, cons
           CHK(slot < L.seqSize, CK_DEC_SEQ, slot, L.seqSize);
           store_rec(L.seq + slot, m);
         }
-        if (fwd) ss_put(o.ssBuf + o.ssN + j, osn, ots, p.arr, p.poff, u32(payLen), marker, kf);
+        if (fwd) ss_put(o.ssBuf + o.ssN + j, o, u32(o.nFwd) + j, osn, ots, p.arr, p.poff, u32(payLen), marker, kf);
         o.ssN += u32(__popcll(fwR));
         const u32 sumLen = wave_sum_u32(outLen);
         sentAcc += fwd ? i32(p.poff) - hdrLen : 0;  // (reduced once per DownTrack)
@@ -3432,7 +3493,7 @@ __global__ void __launch_bounds__(64) DECIDE_ATTR k_decide_dt(DecideArgs A, cons
 #if LKF_SVC_STATS
       const u64 ts0 = __builtin_amdgcn_s_memtime();
 #endif
-      ss_flush(sSS, o.ssRing, o.ssGap, sSsBuf, o.ssN, o.bSN, o.bTS);
+      ss_flush(sSS, o.ssRing, o.ssGap, sSsBuf, o.ssN, o.bSN, o.bTS, o.outW);
 #if LKF_SVC_STATS
       tSs += __builtin_amdgcn_s_memtime() - ts0;
 #endif
@@ -3443,14 +3504,16 @@ __global__ void __launch_bounds__(64) DECIDE_ATTR k_decide_dt(DecideArgs A, cons
 #if LKF_SVC_STATS
   const u64 tP2 = __builtin_amdgcn_s_memtime();
 #endif
-  while (ev < evEnd) apply_ctl(L, A.events[ev++]);
+  {  // (the epilogue's reads)
+  const DecideArgsK A = decide_args();
+  while (ev < evEnd) apply_ctl(L, A->events[ev++]);
   __syncthreads();
   {
     const u32 h1 = reinterpret_cast<const u32 *>(&sHot)[lane];
-    if (h1 != sHot0[lane]) reinterpret_cast<u32 *>(A.hot + d)[lane] = h1;
+    if (h1 != sHot0[lane]) reinterpret_cast<u32 *>(A->hot + d)[lane] = h1;
   }
   if (o.nFwd && lane < sizeof(SenderStats) / 16)  // (only a forwarded packet changes it)
-    reinterpret_cast<uint4 *>(A.ss + d)[lane] = reinterpret_cast<const uint4 *>(&sSS)[lane];
+    reinterpret_cast<uint4 *>(A->ss + d)[lane] = reinterpret_cast<const uint4 *>(&sSS)[lane];
   if (L.rmNew) {  // the ranges appended this batch (the ring's newest): the older ones are unchanged in HBM
     wave_lds_sync();
     const u32 nc = L.h.rmCount, nn = min(L.rmNew, nc);
@@ -3461,7 +3524,7 @@ __global__ void __launch_bounds__(64) DECIDE_ATTR k_decide_dt(DecideArgs A, cons
   }
   if (ddDT) {
     wave_lds_sync();
-    uint4 *g = reinterpret_cast<uint4 *>(A.ddState + d);
+    uint4 *g = reinterpret_cast<uint4 *>(A->ddState + d);
     const uint4 *l = reinterpret_cast<const uint4 *>(sDD);
     const u32 nDD = (kDDStateHead + u32(sDD->numChains) * kDDExpRow * 8) / 16;
     for (u32 i = lane; i < nDD; i += 64) g[i] = l[i];
@@ -3479,25 +3542,26 @@ __global__ void __launch_bounds__(64) DECIDE_ATTR k_decide_dt(DecideArgs A, cons
   }
   const i32 sentRun = i32(wave_sum_u32(u32(sentAcc)));  // (every lane: a cross-lane reduction)
   if (lane == 0) {
-    A.fwdCnt[d] = u32(o.nFwd);
-    A.fwdBytes[d] = o.relOff;
-    if (o.nFwd) A.fbase[d] = FwdBase{o.bSN, o.bTS};
+    A->fwdCnt[d] = u32(o.nFwd);
+    A->fwdBytes[d] = o.relOff;
+    if (o.nFwd) A->fbase[d] = FwdBase{o.bSN, o.bTS};
     // DownTrack.sendingPacket: bytesSent += header + payload (downtrack.go:1934-1940)
     // (atomics without return: the wave does not wait for a read of the old totals)
-    if (o.nFwd) atomicAdd((unsigned long long *)&A.dtCum[d].packets, (unsigned long long)o.nFwd);
+    if (o.nFwd) atomicAdd((unsigned long long *)&A->dtCum[d].packets, (unsigned long long)o.nFwd);
     const u64 nSent = o.nBytes + u64(i64(sentRun) + o.sentDiff);
-    if (nSent) atomicAdd((unsigned long long *)&A.dtCum[d].bytes, (unsigned long long)nSent);
-    A.dtCum[d].flags = L.h.flags;
+    if (nSent) atomicAdd((unsigned long long *)&A->dtCum[d].bytes, (unsigned long long)nSent);
+    A->dtCum[d].flags = L.h.flags;
     // counters: one of kStatCopies partial copies per wave (same-address
     // atomics from every wave would serialise in one L2 channel); k_stats_reduce
     // folds the copies after the kernel
-    u64 *st = A.stats + size_t(1 + (w % kStatCopies)) * kStatWords;
+    u64 *st = A->stats + size_t(1 + (w % kStatCopies)) * kStatWords;
     if (o.nTuples) atomicAdd((unsigned long long *)&st[0], (unsigned long long)o.nTuples);
     if (o.nFwd) atomicAdd((unsigned long long *)&st[1], (unsigned long long)o.nFwd);
     if (o.nBytes) atomicAdd((unsigned long long *)&st[2], (unsigned long long)o.nBytes);
 #pragma unroll
     for (int i = 0; i < LKF_DROP_NREASONS; i++)
       if (o.drops[i]) atomicAdd((unsigned long long *)&st[4 + i], (unsigned long long)o.drops[i]);
+  }
   }
 #if LKF_SVC_STATS
   if (DDK && lane == 0 && (L.h.flags & (F_DD | F_VP9))) {

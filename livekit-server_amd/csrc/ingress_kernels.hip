@@ -955,7 +955,7 @@ struct BktCtx {
   u64 *store;      // per datagram of the batch
   u32 *sOwn;       // LDS owner map (rings up to kBktLds)
   u64 ep;          // ingest epoch << 32
-  bool lds;
+  u32 lds, pad;    // (no tail padding: a copy of the struct is whole dwords, not bytes through the stack)
 };
 __device__ __forceinline__ int bkt_wrap(int x, int M) {
   x %= M;
@@ -1048,11 +1048,16 @@ __device__ __forceinline__ void rx_jitter(StreamHot &h, u32 clockRate, u64 ets, 
 // batch's arrays and the bucket context from LDS: references to the caller's
 // per-lane copies put them on every lane's private stack — 400 B of scratch a
 // lane, written by every wave of the stream kernel, r4's tick WRITE_SIZE)
-template <int HS>
-__device__ __noinline__ lkf_flow ing_step(StreamHot &h, u64 *hs, RangeEntry *ring, const DevStream *sg,
-                                         const IngParsed *pg, const lkf_raw_pkt *rg, u32 ic, lkf_flow *flows,
-                                         u32 *fwd, IngDD *ingDD, const u8 *raw, DDIngState *dds,
-                                         DDStruct *ddStructs, u32 *err, const BktCtx *bkg, bool bkOn, u32 *gap) {
+// (DD false: a stream without a dependency-descriptor parser.  The body then
+// calls nothing that takes a reference to its locals, and the plain stream
+// wave inlines it: an out-of-line ing_step saves the callee-saved VGPRs it
+// uses, and passes its last argument, on every lane's private stack.)
+template <int HS, bool DD>
+__device__ __forceinline__ lkf_flow ing_step_body(StreamHot &h, u64 *hs, RangeEntry *ring, const DevStream *sg,
+                                                  const IngParsed *pg, const lkf_raw_pkt *rg, u32 ic, lkf_flow *flows,
+                                                  u32 *fwd, IngDD *ingDD, const u8 *raw, DDIngState *dds,
+                                                  DDStruct *ddStructs, u32 *err, const BktCtx *bkg, bool bkOn,
+                                                  u32 *gap) {
   const DevStream s = *sg;
   const IngParsed p = *pg;
   const lkf_raw_pkt rp = *rg;
@@ -1154,7 +1159,7 @@ __device__ __noinline__ lkf_flow ing_step(StreamHot &h, u64 *hs, RangeEntry *rin
     if (bkOn && bkt_add_one(bk, u16(f.ext_sn), rp.len, ic) < 0) break;
     f.flags |= LKF_FLOW_BUCKET;
     // getExtPacket (buffer.go:599-671): the dependency descriptor first
-    if (payloadSize > 0 && s.ddIdx != 0xffffffffu && p.ddLen) {
+    if (DD && payloadSize > 0 && s.ddIdx != 0xffffffffu && p.ddLen) {
       bool limit = false;
       if (!dd_ingest(*dds, ddStructs + size_t(s.ddIdx) * 2, raw + rp.off + p.ddOff, p.ddLen,
                      u16(f.ext_sn), dv, limit)) {
@@ -1175,8 +1180,24 @@ __device__ __noinline__ lkf_flow ing_step(StreamHot &h, u64 *hs, RangeEntry *rin
   } while (false);
   flows[ic] = f;
   fwd[ic] = forward;
-  if (ingDD) ingDD[ic] = dv;
+  if (ingDD) {
+    if (DD) {
+      ingDD[ic] = dv;
+    } else {  // (no descriptor: the 32-B record is zeros, two whole stores)
+      static_assert(sizeof(IngDD) == 32, "IngDD is two 16-B words");
+      reinterpret_cast<uint4 *>(ingDD + ic)[0] = make_uint4(0, 0, 0, 0);
+      reinterpret_cast<uint4 *>(ingDD + ic)[1] = make_uint4(0, 0, 0, 0);
+    }
+  }
   return f;
+}
+template <int HS>
+__device__ __noinline__ lkf_flow ing_step(StreamHot &h, u64 *hs, RangeEntry *ring, const DevStream *sg,
+                                         const IngParsed *pg, const lkf_raw_pkt *rg, u32 ic, lkf_flow *flows,
+                                         u32 *fwd, IngDD *ingDD, const u8 *raw, DDIngState *dds,
+                                         DDStruct *ddStructs, u32 *err, const BktCtx *bkg, bool bkOn, u32 *gap) {
+  return ing_step_body<HS, true>(h, hs, ring, sg, pg, rg, ic, flows, fwd, ingDD, raw, dds, ddStructs, err, bkg, bkOn,
+                                 gap);
 }
 
 // The datagrams of a closed stream (lkf_remove_track): not handled, no state
@@ -1376,8 +1397,11 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(LKF_ING
     const u32 end = bad ? u32(__ffsll(static_cast<long long>(bad)) - 1) : 64u;  // the run is [pos, end)
     if (end == pos) {  // the datagram at pos through the serial Buffer.calc step
       if (lane == pos && rp.stream == sid) {
-        const lkf_flow fo = ing_step<1>(sh, sHist, ring, streams + sid, q + ic, raws + ic, ic, flows, fwd, ingDD, raw,
-                                        dds, ddStructs, err, &sBk, bkOn, gap);
+        const lkf_flow fo =
+            DDK ? ing_step<1>(sh, sHist, ring, streams + sid, q + ic, raws + ic, ic, flows, fwd, ingDD, raw, dds,
+                              ddStructs, err, &sBk, bkOn, gap)
+                : ing_step_body<1, false>(sh, sHist, ring, streams + sid, q + ic, raws + ic, ic, flows, fwd, ingDD,
+                                          raw, dds, ddStructs, err, &sBk, bkOn, gap);
         nkSnFl = nk_snfl(p, fo);
         nkS0 = u32(u16(fo.loss_start));
         nkLen = u32(min<u64>(fo.loss_end - fo.loss_start, 0xffffffffull));
