@@ -840,6 +840,124 @@ int lkf_rtx_emit(lkf_engine *e, const lkf_rtx *rtx, uint32_t n, const lkf_raw_pk
 int lkf_rtx_emit_bucket(lkf_engine *e, const lkf_rtx *rtx, uint32_t n, lkf_out *out, uint8_t *out_arena,
                         uint64_t out_cap, uint32_t *n_out, uint64_t *out_len);
 
+/* ---- RTCP ingress: DownTrack.handleRTCP from the bytes ------------------ *
+ * rtcp.Unmarshal(bytes) and the switch over packet types
+ * (downtrack.go:1474-1563) for many DownTracks at once: the compound packets
+ * as pion's RTPSender.Read hands them to each DownTrack (SRTCP already
+ * removed) are parsed on the GPU, every reception report and counter is
+ * applied as lkf_rtcp_feedback would apply it, and the NACKed sequence numbers
+ * stay on the device for lkf_rtx_lookup_ingested.
+ *
+ * pion/rtcp (v1.2.13) is not part of the reference tree and no reference test
+ * feeds handleRTCP; what follows is what the engine computes (parity
+ * unpinned).
+ *
+ * Framing.  An entry is a sequence of packets, each a 4-byte header (V:2 P:1
+ * C:5 | PT:8 | length:16, big-endian) and size = 4 * (length + 1) bytes with
+ * the header; C is the report count (RR, SR) or the format (205, 206).  The
+ * whole entry is MALFORMED and changes nothing when: len == 0; fewer than 4
+ * bytes are left; the version is not 2; size is greater than the bytes left;
+ * or a size check of the table fails.  The P bit is ignored: pad bytes belong
+ * to the packet body.
+ *
+ *   PT / C    packet      size check               what the engine does
+ *   201       RR          size >= 8 + 24 * C       each 24-byte report block (from byte 8; SSRC, fraction
+ *                                                  lost:8, total lost:24, last sequence number, jitter,
+ *                                                  LSR, DLSR) whose SSRC is the DownTrack's yields one
+ *                                                  report, in order; other blocks and the profile
+ *                                                  extension are ignored
+ *   200       SR          size >= 28 + 24 * C      ignored otherwise (handleRTCP has no case for it: its
+ *                                                  report blocks are not applied)
+ *   205 / 1   NACK        size >= 12               (size - 12) / 4 pairs (PID:16, BLP:16) from byte 12;
+ *                                                  the sequence numbers of a pair are the PID, then
+ *                                                  PID + i + 1 (16-bit wrap) for each set BLP bit i,
+ *                                                  ascending.  The media SSRC is not compared (the
+ *                                                  reference does not).  nacks = sequence numbers
+ *   205 / 15  TransportLayerCC  size >= 20         a REF_TWCC record when bytes 8..11 are the DownTrack's
+ *                                                  SSRC; the body is not validated
+ *   206 / 1   PLI         size >= 12               plis += 1
+ *   206 / 4   FIR         size >= 12 and           firs += 1 per packet
+ *                         (size - 12) % 8 == 0
+ *   206 / 15  REMB        size >= 20, bytes 12..15 a REF_REMB record (not filtered by SSRC)
+ *                         "REMB", size >= 20 +
+ *                         4 * byte 16 (numSSRC)
+ *   others                none beyond framing      skipped by size, body not validated (SDES, BYE, APP,
+ *                                                  XR, SLI, RRR, unknown types and formats)
+ *
+ * Divergences: pion validates the bodies of SDES / XR / TransportLayerCC and
+ * drops the whole compound on a bad one, the engine does not; the NACK count
+ * without an SSRC filter and the FIR count per packet are the reference's.
+ *
+ * Within an OK entry the reports are applied in packet order, then the
+ * counters are added once (downtrack.go:1565-1567).  The entry yields exactly
+ * max(1, reports) lkf_rtcp_fb records: one per report (LKF_FB_HAS_RR), the
+ * counts on the last one and zero on the others; without a report one record
+ * with no LKF_FB_HAS_RR carries the counts.  A MALFORMED entry yields none. */
+typedef struct lkf_rtcp_raw { /* one handleRTCP(bytes) call on DownTrack dt; 12 B */
+  int32_t dt;
+  uint32_t off, len; /* the compound packet in the call's arena; len <= LKF_RTCP_MAX_LEN */
+} lkf_rtcp_raw;
+#define LKF_RTCP_MAX_LEN 65535u /* one datagram: an entry's counts (at most 17 * len / 4 sequence numbers) fit 32 bits */
+#define LKF_RTCP_IN_OK 0
+#define LKF_RTCP_IN_MALFORMED 1 /* nothing applied: handleRTCP returns on the Unmarshal error */
+typedef struct lkf_rtcp_in_result { /* 48 B */
+  uint32_t status;
+  uint32_t rtt_ms;               /* rttToReport: the rtt of the entry's last report with RTT_CHANGED; 0: none */
+  uint32_t fb_first, fb_count;   /* its lkf_rtcp_fb entries in the call's fb list */
+  uint32_t reports;              /* reception reports with SSRC == d.ssrc */
+  uint32_t nacks, plis, firs;    /* numNACKs (sequence numbers), numPLIs, numFIRs of the compound */
+  uint32_t nack_first;           /* its sequence numbers in the call's NACK list */
+  int32_t pli_layer;             /* layer for Receiver.SendPLI: the request spatial layer if plis + firs > 0
+                                    and it is valid, else -1 (sendPliOnce / CheckSync) */
+  uint32_t ref_first, ref_count; /* its pass-through records */
+} lkf_rtcp_in_result;
+#define LKF_RTCP_REF_REMB 1 /* every REMB packet (OnREMB, not filtered by SSRC) */
+#define LKF_RTCP_REF_TWCC 2 /* every TransportLayerCC whose media SSRC == d.ssrc (OnTransportCCFeedback) */
+typedef struct lkf_rtcp_ref {
+  uint32_t entry, kind;
+  uint32_t off, len; /* the packet inside the arena, for the host's stream allocator */
+} lkf_rtcp_ref;
+/* Entries grouped by DownTrack (a DownTrack's entries contiguous and in
+ * arrival order; LKF_EORDER otherwise, as lkf_rtcp_feedback).  Several entries
+ * may name the same bytes: pion delivers one compound packet to every
+ * DownTrack whose SSRC it addresses.  An entry with off + len beyond
+ * arena_len, with len above LKF_RTCP_MAX_LEN, or a handle out of range, is
+ * LKF_EINVAL before anything runs.
+ * Waits for queued runs as the three RTCP calls above do, applies every
+ * report and counter (k_rr_update, the semantics of lkf_rtcp_feedback), and
+ * returns in input order: out[i] for in[i]; the parsed lkf_rtcp_fb records
+ * with their results (fb_out[k] answers fb[k]; the host's
+ * OnRTCPReceiverReport listeners read the report fields there) and the
+ * pass-through records.  n_fb / n_refs / n_nacks (n_nacks may be NULL): the
+ * lengths of the three lists.  fb_cap < *n_fb or ref_cap < *n_refs returns
+ * LKF_ENOSPC with the needed counts and out[] filled; the state HAS been
+ * applied then (as lkf_rtx_lookup's records are bumped when its cap is
+ * short), so do not repeat the call: size the arrays by max(1, len / 24)
+ * records per entry and len / 20 refs per entry, which always suffice.
+ * pli_layer is the DownTrack's request spatial layer as of every run queued
+ * before the call.  playoudDelayAcked stays the host's LKF_CTL_PLAYOUT_ACKED
+ * op: out[i].reports > 0 is its trigger.
+ *
+ * The NACK list: lkf_nack {dt, sn} grouped by DownTrack; within a DownTrack
+ * entry, then packet, then pair, then the PID first and the BLP bits
+ * ascending (out[i].nack_first / nacks index it).  It stays on the device
+ * until the next lkf_rtcp_ingest. */
+int lkf_rtcp_ingest(lkf_engine *e, const lkf_rtcp_raw *in, uint32_t n, const uint8_t *arena, uint64_t arena_len,
+                    int64_t now_ns, lkf_rtcp_in_result *out, lkf_rtcp_fb *fb, lkf_rtcp_fb_result *fb_out,
+                    uint32_t fb_cap, uint32_t *n_fb, lkf_rtcp_ref *refs, uint32_t ref_cap, uint32_t *n_refs,
+                    uint32_t *n_nacks);
+/* The last lkf_rtcp_ingest's NACK list read back (tests, and hosts that want
+ * it); *n_out its length, LKF_ENOSPC if cap is short. */
+int lkf_rtcp_ingested_nacks(lkf_engine *e, lkf_nack *out, uint32_t cap, uint32_t *n_out);
+/* lkf_rtx_lookup on the device-resident NACK list of the last lkf_rtcp_ingest,
+ * with no host copy of the NACKs: the same FilterRTX, the same
+ * getExtPacketMetas side effects, the RTX time set to now_ns; a DownTrack
+ * removed since answers nothing.  cap < *n_out returns LKF_ENOSPC (the
+ * records' NACK counts have been bumped then).  Each call looks the whole list
+ * up again, as a second lkf_rtx_lookup of the same list would.  The records
+ * feed lkf_rtx_emit / lkf_rtx_emit_bucket unchanged. */
+int lkf_rtx_lookup_ingested(lkf_engine *e, int64_t now_ns, lkf_rtx *out, uint32_t cap, uint32_t *n_out);
+
 /* ---- padding and blank frames ---------------------- *
  * One request per DownTrack per call (distinct DownTracks; LKF_EINVAL
  * otherwise).  Both wait for queued runs and change the DownTrack's

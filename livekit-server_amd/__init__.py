@@ -358,6 +358,55 @@ class Engine:
                   "rtcp_feedback")
         return out
 
+    def rtcp_ingest(self, raws, arena, now_ns):
+        """lkf_rtcp_ingest: `raws` an abi.RTCP_RAW_DTYPE array grouped by
+        DownTrack, `arena` the compound packets' bytes (bytes or a uint8
+        array) -> (abi.RTCP_IN_RESULT_DTYPE per entry, abi.RTCP_FB_DTYPE
+        records, their abi.RTCP_FB_RESULT_DTYPE results, abi.RTCP_REF_DTYPE
+        records, the NACK list's length).  The lists are sized from the bytes
+        (a report block is 24 bytes, a pass-through packet at least 20)."""
+        rw = np.ascontiguousarray(raws, dtype=abi.RTCP_RAW_DTYPE)
+        ar = np.frombuffer(arena, dtype=np.uint8) if isinstance(arena, (bytes, bytearray)) else \
+            np.ascontiguousarray(arena, dtype=np.uint8)
+        ln = rw["len"].astype(np.int64)
+        fb_cap = int(np.maximum(1, ln // 24).sum())
+        ref_cap = int((ln // 20).sum())
+        out = np.zeros(len(rw), dtype=abi.RTCP_IN_RESULT_DTYPE)
+        fb = np.zeros(max(1, fb_cap), dtype=abi.RTCP_FB_DTYPE)
+        fbo = np.zeros(max(1, fb_cap), dtype=abi.RTCP_FB_RESULT_DTYPE)
+        refs = np.zeros(max(1, ref_cap), dtype=abi.RTCP_REF_DTYPE)
+        nfb, nref, nn = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        self._chk(self.api["rtcp_ingest"](self.h, rw.ctypes.data, len(rw), ar.ctypes.data if len(ar) else None,
+                                          len(ar), now_ns, out.ctypes.data, fb.ctypes.data, fbo.ctypes.data,
+                                          len(fb), C.byref(nfb), refs.ctypes.data, len(refs), C.byref(nref),
+                                          C.byref(nn)), "rtcp_ingest")
+        return out, fb[:nfb.value], fbo[:nfb.value], refs[:nref.value], nn.value
+
+    def _ingested_nack_count(self):
+        k = C.c_uint32()
+        rc = self.api["rtcp_ingested_nacks"](self.h, None, 0, C.byref(k))
+        if rc != -28:  # LKF_ENOSPC: the list is not empty
+            self._chk(rc, "rtcp_ingested_nacks")
+        return k.value
+
+    def rtcp_ingested_nacks(self):
+        """lkf_rtcp_ingested_nacks: the last rtcp_ingest's NACK list -> abi.NACK_DTYPE array."""
+        k = C.c_uint32(self._ingested_nack_count())
+        out = np.zeros(k.value, dtype=abi.NACK_DTYPE)
+        if k.value:
+            self._chk(self.api["rtcp_ingested_nacks"](self.h, out.ctypes.data, len(out), C.byref(k)),
+                      "rtcp_ingested_nacks")
+        return out
+
+    def rtx_lookup_ingested(self, now_ns):
+        """lkf_rtx_lookup_ingested: the RTX records of the device-resident NACK
+        list -> abi.RTX_DTYPE array (one lookup: at most one record per NACK)."""
+        k = C.c_uint32()
+        out = np.zeros(max(1, self._ingested_nack_count()), dtype=abi.RTX_DTYPE)
+        self._chk(self.api["rtx_lookup_ingested"](self.h, now_ns, out.ctypes.data, len(out), C.byref(k)),
+                  "rtx_lookup_ingested")
+        return out[:k.value]
+
     def rtcp_sender_reports(self, reqs, now_ns, wire=False):
         """lkf_rtcp_sender_reports: `reqs` an abi.RTCP_SR_REQ_DTYPE array ->
         abi.RTCP_SR_DTYPE array, and with wire=True also a uint8 [n, 28] array

@@ -194,6 +194,21 @@ class lkf_rtcp_sr_req(C.Structure):
     _fields_ = [("dt", C.c_int32), ("calculated_clock_rate", C.c_uint32)]
 
 
+# RTCP ingress (lkf_rtcp_ingest)
+class lkf_rtcp_raw(C.Structure):
+    _fields_ = [("dt", C.c_int32), ("off", C.c_uint32), ("len", C.c_uint32)]
+
+
+class lkf_rtcp_in_result(C.Structure):
+    _fields_ = ([(f, C.c_uint32) for f in ("status", "rtt_ms", "fb_first", "fb_count", "reports", "nacks", "plis",
+                                           "firs", "nack_first")]
+                + [("pli_layer", C.c_int32), ("ref_first", C.c_uint32), ("ref_count", C.c_uint32)])
+
+
+class lkf_rtcp_ref(C.Structure):
+    _fields_ = [(f, C.c_uint32) for f in ("entry", "kind", "off", "len")]
+
+
 class lkf_rtcp_sr(C.Structure):
     _fields_ = [("dt", C.c_int32), ("flags", C.c_uint32), ("ntp", C.c_uint64), ("rtp_ext", C.c_uint64),
                 ("rtp", C.c_uint32), ("packet_count", C.c_uint32), ("octet_count", C.c_uint32),
@@ -234,6 +249,15 @@ RTCP_FB_RESULT_DTYPE = _dtype_of(lkf_rtcp_fb_result)
 RTCP_SR_REQ_DTYPE = _dtype_of(lkf_rtcp_sr_req)
 RTCP_SR_DTYPE = _dtype_of(lkf_rtcp_sr)
 RTP_DELTA_INFO_DTYPE = _dtype_of(lkf_rtp_delta_info)
+LKF_RTCP_IN_OK, LKF_RTCP_IN_MALFORMED = 0, 1
+LKF_RTCP_MAX_LEN = 65535
+LKF_RTCP_REF_REMB, LKF_RTCP_REF_TWCC = 1, 2
+RTCP_RAW_DTYPE = _dtype_of(lkf_rtcp_raw)
+RTCP_IN_RESULT_DTYPE = _dtype_of(lkf_rtcp_in_result)
+RTCP_REF_DTYPE = _dtype_of(lkf_rtcp_ref)
+assert C.sizeof(lkf_rtcp_raw) == 12 == RTCP_RAW_DTYPE.itemsize
+assert C.sizeof(lkf_rtcp_in_result) == 48 == RTCP_IN_RESULT_DTYPE.itemsize
+assert C.sizeof(lkf_rtcp_ref) == 16 == RTCP_REF_DTYPE.itemsize
 assert C.sizeof(lkf_sender_rtcp) == 384 == SENDER_RTCP_DTYPE.itemsize, C.sizeof(lkf_sender_rtcp)
 assert C.sizeof(lkf_rtcp_fb) == 48 == RTCP_FB_DTYPE.itemsize
 assert C.sizeof(lkf_rtcp_fb_result) == 8 == RTCP_FB_RESULT_DTYPE.itemsize
@@ -714,6 +738,15 @@ def bind_engine_api(lib, prefix):
         api["sender_delta_info"] = _bind(lib, prefix + "sender_delta_info", C.c_int,
                                          [e, C.c_void_p, C.c_uint32, C.c_void_p])
         api["sender_rtcp_get"] = _bind(lib, prefix + "sender_rtcp_get", C.c_int, [e, C.c_int32, C.c_void_p])
+    if hasattr(lib, prefix + "rtcp_ingest"):  # engine only: RTCP ingress
+        api["rtcp_ingest"] = _bind(lib, prefix + "rtcp_ingest", C.c_int,
+                                   [e, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_int64, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_uint32, P(C.c_uint32), C.c_void_p, C.c_uint32,
+                                    P(C.c_uint32), P(C.c_uint32)])
+        api["rtcp_ingested_nacks"] = _bind(lib, prefix + "rtcp_ingested_nacks", C.c_int,
+                                           [e, C.c_void_p, C.c_uint32, P(C.c_uint32)])
+        api["rtx_lookup_ingested"] = _bind(lib, prefix + "rtx_lookup_ingested", C.c_int,
+                                           [e, C.c_int64, C.c_void_p, C.c_uint32, P(C.c_uint32)])
     api["blank_frames"] = _bind(lib, prefix + "blank_frames", C.c_int,
                                 [e, C.c_void_p, C.c_uint32, C.c_int64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64,
                                  P(C.c_uint32), P(C.c_uint64)])

@@ -322,6 +322,26 @@ struct lkf_engine {
   DevBuf<uint8_t> dRtcpIn;
   DevBuf<uint32_t> dRtcpGroups;
   DevBuf<uint8_t> dRtcpOut;
+  // RTCP ingress (lkf_rtcp_ingest): one call's entries, bytes, DownTrack group
+  // starts, per-entry counts / offsets / results and scan state (sized by the
+  // entries), and the parsed lists (sized by the count pass's totals).  The
+  // NACK list stays for lkf_rtx_lookup_ingested: riNacks sequence numbers, and
+  // on the host each DownTrack's non-empty share of it (from the results).
+  DevBuf<lkf_rtcp_raw> dRiIn;
+  DevBuf<uint8_t> dRiArena;
+  DevBuf<uint32_t> dRiGEntry, dRiFbG, dRiFbCnt, dRiRefCnt;
+  DevBuf<uint64_t> dRiNackCnt, dRiFbOff, dRiNackOff, dRiRefOff, dRiTot, dRiScan;
+  DevBuf<lkf_rtcp_in_result> dRiRes;
+  DevBuf<lkf_rtcp_fb> dRiFb;
+  DevBuf<lkf_rtcp_fb_result> dRiFbOut;
+  DevBuf<lkf_nack> dRiNacks;
+  DevBuf<lkf_rtcp_ref> dRiRefs;
+  uint32_t riNacks = 0;
+  struct RiGroup {
+    int32_t dt;
+    uint32_t begin, end;
+  };
+  std::vector<RiGroup> riGroups;
   int64_t rtxNow = 0;  // now_ns of the last lkf_rtx_lookup (the RTX packets' sendingPacket time)
   // sequencer ddBytes (sequencer.go:198-199) of the DownTracks that can forward
   // a dependency descriptor: [ring index][slot] kSeqDDBytes, grown on demand
@@ -2987,6 +3007,30 @@ static int rtx_reserve(lkf_engine *e, uint32_t n) {
   return LKF_OK;
 }
 
+// The lookup itself on stream s: m NACKs at `list` in ngroups non-empty
+// DownTrack groups (bounds in dNackG), the records compacted on the host.
+static int rtx_lookup_run(lkf_engine *e, hipStream_t s, const lkf_nack *list, uint32_t ngroups, uint32_t m,
+                          int64_t now_ns, lkf_rtx *out, uint32_t cap, uint32_t *n_out) {
+  HIPCHK(launch_rtx_lookup(s, e->dHot, e->dSeq, e->cfg.seq_size, e->dSrm, e->srmStride, e->srmCap, list, e->dNackG,
+                           ngroups, now_ns / 1000000, e->dRtx, e->dNackValid),
+         "rtx lookup");
+  std::vector<lkf_rtx> r(m);
+  std::vector<uint32_t> v(m);
+  CHKRANGE(e->dRtx, m * sizeof(lkf_rtx), "async d2h");
+  HIPCHK(hipMemcpyAsync(r.data(), e->dRtx, m * sizeof(lkf_rtx), hipMemcpyDeviceToHost, s), "rtx copy");
+  CHKRANGE(e->dNackValid, m * sizeof(uint32_t), "async d2h");
+  HIPCHK(hipMemcpyAsync(v.data(), e->dNackValid, m * sizeof(uint32_t), hipMemcpyDeviceToHost, s), "valid copy");
+  HIPCHK(hipStreamSynchronize(s), "sync");
+  uint32_t k = 0;
+  for (uint32_t i = 0; i < m; i++) k += v[i];
+  *n_out = k;
+  if (cap < k) return LKF_ENOSPC;
+  k = 0;
+  for (uint32_t i = 0; i < m; i++)
+    if (v[i]) out[k++] = r[i];
+  return LKF_OK;
+}
+
 int lkf_rtx_lookup(lkf_engine *e, const lkf_nack *nacks, uint32_t n, int64_t now_ns, lkf_rtx *out, uint32_t cap,
                    uint32_t *n_out) {
   if (!e || !n_out || (n && !nacks)) return LKF_EINVAL;
@@ -3033,24 +3077,213 @@ int lkf_rtx_lookup(lkf_engine *e, const lkf_nack *nacks, uint32_t n, int64_t now
   HIPCHK(hipMemcpyAsync(e->dNacks, packed.data(), m * sizeof(lkf_nack), hipMemcpyHostToDevice, s), "nacks copy");
   HIPCHK(hipMemcpyAsync(e->dNackG, gb.data(), gb.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s),
          "groups copy");
-  HIPCHK(launch_rtx_lookup(s, e->dHot, e->dSeq, e->cfg.seq_size, e->dSrm, e->srmStride, e->srmCap, e->dNacks,
-                           e->dNackG, uint32_t(gStart.size()), now_ns / 1000000, e->dRtx, e->dNackValid),
-         "rtx lookup");
-  std::vector<lkf_rtx> r(m);
-  std::vector<uint32_t> v(m);
-  CHKRANGE(e->dRtx, m * sizeof(lkf_rtx), "async d2h");
-  HIPCHK(hipMemcpyAsync(r.data(), e->dRtx, m * sizeof(lkf_rtx), hipMemcpyDeviceToHost, s), "rtx copy");
-  CHKRANGE(e->dNackValid, m * sizeof(uint32_t), "async d2h");
-  HIPCHK(hipMemcpyAsync(v.data(), e->dNackValid, m * sizeof(uint32_t), hipMemcpyDeviceToHost, s), "valid copy");
-  HIPCHK(hipStreamSynchronize(s), "sync");
-  uint32_t k = 0;
-  for (uint32_t i = 0; i < m; i++) k += v[i];
-  *n_out = k;
-  if (cap < k) return LKF_ENOSPC;
-  k = 0;
-  for (uint32_t i = 0; i < m; i++)
-    if (v[i]) out[k++] = r[i];
+  return rtx_lookup_run(e, s, e->dNacks, uint32_t(gStart.size()), m, now_ns, out, cap, n_out);
+}
+
+// ---- RTCP ingress (rtcp_kernels.hip k_rtcp_in_*; the parse is rtcp_in_device.h) ----
+static_assert(sizeof(lkf_rtcp_raw) == 12 && sizeof(lkf_rtcp_in_result) == 48 && sizeof(lkf_rtcp_ref) == 16,
+              "RTCP ingress records");
+
+// The call frame is the three RTCP calls' (rtcp_begin): the sender stream
+// ordered after every queued stage, the buffers grown only while it is idle.
+// Count pass -> scans -> the totals back on the host (the lists are sized by
+// them, never by a guess about the bytes) -> write pass -> k_rr_update on the
+// device-resident fb list -> the fold of its results into the entries.
+int lkf_rtcp_ingest(lkf_engine *e, const lkf_rtcp_raw *in, uint32_t n, const uint8_t *arena, uint64_t arena_len,
+                    int64_t now_ns, lkf_rtcp_in_result *out, lkf_rtcp_fb *fb, lkf_rtcp_fb_result *fb_out,
+                    uint32_t fb_cap, uint32_t *n_fb, lkf_rtcp_ref *refs, uint32_t ref_cap, uint32_t *n_refs,
+                    uint32_t *n_nacks) {
+  if (!e || !n_fb || !n_refs || (n && (!in || !out)) || (fb_cap && (!fb || !fb_out)) || (ref_cap && !refs) ||
+      (arena_len && !arena))
+    return LKF_EINVAL;
+  *n_fb = *n_refs = 0;
+  if (n_nacks) *n_nacks = 0;
+  // groups: one per DownTrack's contiguous entries (a DownTrack must not reappear)
+  std::vector<uint32_t> g;
+  std::vector<uint8_t> seen(e->dtp.size(), 0);
+  for (uint32_t i = 0; i < n; i++) {
+    const int32_t dt = in[i].dt;
+    if (dt < 0 || dt >= int32_t(e->dtp.size())) return LKF_EINVAL;
+    if (in[i].len > LKF_RTCP_MAX_LEN || uint64_t(in[i].off) + in[i].len > arena_len) return LKF_EINVAL;
+    if (i == 0 || in[i - 1].dt != dt) {
+      if (seen[dt]) return LKF_EORDER;
+      seen[dt] = 1;
+      g.push_back(i);
+    }
+  }
+  const uint32_t ngroups = uint32_t(g.size());
+  g.push_back(n);
+  int rc = flush_topology(e);
+  if (rc) return rc;
+  HIPCHK(hipSetDevice(e->dev), "hipSetDevice");
+  rc = sender_after_queued(e);
+  if (rc) return rc;
+  hipStream_t s = e->sendS;
+  e->riNacks = 0;  // the last call's NACK list ends here
+  e->riGroups.clear();
+  if (!n) return LKF_OK;
+  // The per-entry buffers grow together, dRiRefOff last: its capacity is what
+  // all of them hold (0 after a failed grow, which the next call retries).
+  if (n > e->dRiRefOff.cap()) {
+    HIPCHK(hipStreamSynchronize(s), "sync sender stream");
+    const uint64_t m = 2 * uint64_t(n);
+    release_all(e->dRiIn, e->dRiGEntry, e->dRiFbG, e->dRiFbCnt, e->dRiRefCnt, e->dRiNackCnt, e->dRiFbOff,
+                e->dRiNackOff, e->dRiRes, e->dRiTot, e->dRiScan, e->dRiRefOff);
+    HIPCHK(e->dRiIn.reserve(m, 4096), "alloc rtcp raw");
+    HIPCHK(e->dRiGEntry.reserve(m + 1, 4097), "alloc rtcp group starts");
+    HIPCHK(e->dRiFbG.reserve(m + 1, 4097), "alloc rtcp fb groups");
+    HIPCHK(e->dRiFbCnt.reserve(m, 4096), "alloc rtcp counts");
+    HIPCHK(e->dRiRefCnt.reserve(m, 4096), "alloc rtcp counts");
+    HIPCHK(e->dRiNackCnt.reserve(m, 4096), "alloc rtcp counts");
+    HIPCHK(e->dRiFbOff.reserve(m, 4096), "alloc rtcp offsets");
+    HIPCHK(e->dRiNackOff.reserve(m, 4096), "alloc rtcp offsets");
+    HIPCHK(e->dRiRes.reserve(m, 4096), "alloc rtcp results");
+    HIPCHK(e->dRiTot.reserve(4, 4), "alloc rtcp totals");
+    const size_t words = scan_state_words(uint32_t(std::min<uint64_t>(std::max<uint64_t>(m, 4096), 0xffffffffu)));
+    HIPCHK(e->dRiScan.alloc(words), "alloc rtcp scan state");
+    HIPCHK(hipMemsetAsync(e->dRiScan, 0, words * sizeof(uint64_t), s), "rtcp scan state reset");
+    HIPCHK(e->dRiRefOff.reserve(m, 4096), "alloc rtcp offsets");
+  }
+  if (arena_len > e->dRiArena.cap()) {  // (on its own: empty after a failed grow, retried then)
+    HIPCHK(hipStreamSynchronize(s), "sync sender stream");
+    HIPCHK(e->dRiArena.reserve(2 * arena_len, 1 << 16), "alloc rtcp arena");
+  }
+  HIPCHK(hipMemcpyAsync(e->dRiIn, in, size_t(n) * sizeof(lkf_rtcp_raw), hipMemcpyHostToDevice, s), "rtcp raw copy");
+  if (arena_len) HIPCHK(hipMemcpyAsync(e->dRiArena, arena, arena_len, hipMemcpyHostToDevice, s), "rtcp arena copy");
+  HIPCHK(hipMemcpyAsync(e->dRiGEntry, g.data(), g.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s),
+         "rtcp groups copy");
+  RtcpInLaunch a{};
+  a.in = e->dRiIn;
+  a.n = n;
+  a.arena = e->dRiArena;
+  a.arenaLen = arena_len;
+  a.dts = e->dDTs;
+  a.hot = e->dHot;
+  a.ndts = uint32_t(e->dtp.size());
+  a.res = e->dRiRes;
+  a.fbCnt = e->dRiFbCnt;
+  a.refCnt = e->dRiRefCnt;
+  a.nackCnt = e->dRiNackCnt;
+  a.fbOff = e->dRiFbOff;
+  a.nackOff = e->dRiNackOff;
+  a.refOff = e->dRiRefOff;
+  a.totals = e->dRiTot;
+  a.gEntry = e->dRiGEntry;
+  a.ngroups = ngroups;
+  a.fbG = e->dRiFbG;
+  HIPCHK(launch_rtcp_in_count(s, a), "rtcp count");
+  // input-order offsets: (fb records, sequence numbers) in one scan, the refs in another
+  HIPCHK(launch_scan(s, 1, nullptr, nullptr, nullptr, e->dRiFbCnt, e->dRiNackCnt, n, e->dRiScan, nullptr, e->dRiFbOff,
+                     e->dRiNackOff, e->dRiTot, e->dRiTot + 1, nullptr),
+         "rtcp scan");
+  HIPCHK(launch_scan(s, 2, nullptr, nullptr, nullptr, e->dRiRefCnt, nullptr, n, e->dRiScan, nullptr, e->dRiRefOff,
+                     nullptr, e->dRiTot + 2, nullptr, nullptr),
+         "rtcp ref scan");
+  uint64_t tot[3] = {};
+  CHKRANGE(e->dRiTot, sizeof(tot), "async d2h");
+  HIPCHK(hipMemcpyAsync(tot, e->dRiTot, sizeof(tot), hipMemcpyDeviceToHost, s), "rtcp totals copy");
+  HIPCHK(hipStreamSynchronize(s), "sync sender stream");
+  for (uint64_t t : tot)
+    if (t > 0xffffffffull) {  // (or a scan that gave up: ~0)
+      e->err = "RTCP ingest: a list of one call exceeds 2^32 - 1 records";
+      return LKF_EINVAL;
+    }
+  // the lists, sized by the counts (the stream is idle here)
+  HIPCHK(e->dRiFb.reserve(tot[0], 4096), "alloc rtcp fb");
+  HIPCHK(e->dRiFbOut.reserve(tot[0], 4096), "alloc rtcp fb results");
+  HIPCHK(e->dRiNacks.reserve(tot[1], 4096), "alloc rtcp nacks");
+  HIPCHK(e->dRiRefs.reserve(tot[2], 1024), "alloc rtcp refs");
+  a.fb = e->dRiFb;
+  a.nacks = e->dRiNacks;
+  a.refs = e->dRiRefs;
+  a.fbCap = tot[0];
+  a.nackCap = tot[1];
+  a.refCap = tot[2];
+  a.fbOut = e->dRiFbOut;
+  HIPCHK(launch_rtcp_in_write(s, a), "rtcp write");
+  RrUpdateLaunch u;
+  u.in = e->dRiFb;
+  u.gBegin = e->dRiFbG;
+  u.ngroups = ngroups;
+  u.n = uint32_t(tot[0]);
+  u.now = now_ns;
+  u.ss = e->dSS;
+  u.ring = e->dSSRing;
+  u.rtcp = e->dRtcp;
+  u.ndts = uint32_t(e->dtp.size());
+  u.out = e->dRiFbOut;
+  HIPCHK(launch_rr_update(s, u), "rr update");
+  HIPCHK(launch_rtcp_in_fold(s, a), "rtcp fold");
+  HIPCHK(hipStreamSynchronize(s), "sync sender stream");
+  D2H(out, e->dRiRes, size_t(n) * sizeof(lkf_rtcp_in_result), "rtcp results copy");
+  *n_fb = uint32_t(tot[0]);
+  *n_refs = uint32_t(tot[2]);
+  if (n_nacks) *n_nacks = uint32_t(tot[1]);
+  // each DownTrack's share of the NACK list, for lkf_rtx_lookup_ingested
+  e->riNacks = uint32_t(tot[1]);
+  for (uint32_t k = 0; k < ngroups; k++) {
+    const uint32_t b = out[g[k]].nack_first, en = k + 1 < ngroups ? out[g[k + 1]].nack_first : uint32_t(tot[1]);
+    if (en > b) e->riGroups.push_back({in[g[k]].dt, b, en});
+  }
+  if (tot[0] > fb_cap || tot[2] > ref_cap) return LKF_ENOSPC;
+  if (tot[0]) {
+    D2H(fb, e->dRiFb, size_t(tot[0]) * sizeof(lkf_rtcp_fb), "rtcp fb copy");
+    D2H(fb_out, e->dRiFbOut, size_t(tot[0]) * sizeof(lkf_rtcp_fb_result), "rtcp fb results copy");
+  }
+  if (tot[2]) D2H(refs, e->dRiRefs, size_t(tot[2]) * sizeof(lkf_rtcp_ref), "rtcp refs copy");
   return LKF_OK;
+}
+
+int lkf_rtcp_ingested_nacks(lkf_engine *e, lkf_nack *out, uint32_t cap, uint32_t *n_out) {
+  if (!e || !n_out) return LKF_EINVAL;
+  *n_out = e->riNacks;
+  if (cap < e->riNacks) return LKF_ENOSPC;
+  if (!e->riNacks) return LKF_OK;
+  if (!out) return LKF_EINVAL;
+  HIPCHK(hipSetDevice(e->dev), "hipSetDevice");
+  D2H(out, e->dRiNacks, size_t(e->riNacks) * sizeof(lkf_nack), "rtcp nacks copy");  // (the ingest left its stream idle)
+  return LKF_OK;
+}
+
+int lkf_rtx_lookup_ingested(lkf_engine *e, int64_t now_ns, lkf_rtx *out, uint32_t cap, uint32_t *n_out) {
+  if (!e || !n_out) return LKF_EINVAL;
+  *n_out = 0;
+  e->rtxNow = now_ns;
+  // k_rtx_lookup's groups are non-empty and contiguous: the DownTracks without
+  // a NACK are not in riGroups, and while no listed DownTrack has been removed
+  // the list is looked up where the ingest wrote it.  Otherwise the kept
+  // DownTracks' shares are packed device to device into the lookup's own list.
+  std::vector<uint32_t> gb;
+  std::vector<const lkf_engine::RiGroup *> keep;
+  uint32_t m = 0;
+  for (const auto &q : e->riGroups)
+    if (e->active[q.dt]) {  // a removed DownTrack answers no NACK
+      keep.push_back(&q);
+      gb.push_back(m);
+      m += q.end - q.begin;
+    }
+  if (keep.empty()) return LKF_OK;
+  gb.push_back(m);
+  const bool inPlace = keep.size() == e->riGroups.size();
+  int rc = flush_topology(e);
+  if (rc) return rc;
+  hipStream_t s = e->decS;  // as lkf_rtx_lookup: behind the queued decides
+  HIPCHK(hipSetDevice(e->dev), "hipSetDevice");
+  if (m > rtx_cap(e)) HIPCHK(hipStreamSynchronize(s), "sync decide stream");  // (rtx_reserve reallocates)
+  rc = rtx_reserve(e, m);
+  if (rc) return rc;
+  HIPCHK(hipEventRecord(e->inEv, e->own), "event");
+  HIPCHK(hipStreamWaitEvent(s, e->inEv, 0), "wait own stream");
+  HIPCHK(hipEventRecord(e->inEv, e->sendS), "event");  // the ingest's write pass
+  HIPCHK(hipStreamWaitEvent(s, e->inEv, 0), "wait sender stream");
+  if (!inPlace)
+    for (size_t k = 0; k < keep.size(); k++)
+      HIPCHK(hipMemcpyAsync(e->dNacks + gb[k], e->dRiNacks + keep[k]->begin,
+                            size_t(keep[k]->end - keep[k]->begin) * sizeof(lkf_nack), hipMemcpyDeviceToDevice, s),
+             "nacks pack");
+  HIPCHK(hipMemcpyAsync(e->dNackG, gb.data(), gb.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s), "groups copy");
+  return rtx_lookup_run(e, s, inPlace ? e->dRiNacks.get() : e->dNacks.get(), uint32_t(keep.size()), m, now_ns, out, cap,
+                        n_out);
 }
 
 static int rtx_emit_common(lkf_engine *e, const lkf_rtx *rtx, uint32_t n, const uint8_t *srcArena,

@@ -562,9 +562,41 @@ struct DeltaSenderLaunch {
   lkf_rtp_delta_info *out;
 };
 hipError_t launch_delta_sender(hipStream_t s, const DeltaSenderLaunch &a);
+// RTCP ingress (lkf_rtcp_ingest; the parse is rtcp_in_device.h), one lane per
+// entry: k_rtcp_in_count validates an entry and counts what it yields (res and
+// the three count arrays, which the engine scans into fbOff / nackOff / refOff
+// and totals); k_rtcp_in_write writes the lists at those offsets, the
+// DownTrack group bounds of the fb list (fbG, k_rr_update's gBegin) and the
+// rest of res; k_rtcp_in_fold, after k_rr_update, folds fbOut into res.rtt_ms.
+struct RtcpInLaunch {
+  const lkf_rtcp_raw *in;  // grouped by DownTrack
+  uint32_t n;
+  const uint8_t *arena;
+  uint64_t arenaLen;
+  const DevDT *dts;  // the SSRC
+  const DTHot *hot;  // the request spatial layer
+  uint32_t ndts;
+  lkf_rtcp_in_result *res;  // per entry
+  uint32_t *fbCnt, *refCnt;
+  uint64_t *nackCnt;
+  const uint64_t *fbOff, *nackOff, *refOff;  // per entry: exclusive scans of the counts
+  const uint64_t *totals;                    // [0] fb records, [1] sequence numbers, [2] refs
+  const uint32_t *gEntry;                    // first entry of each DownTrack group
+  uint32_t ngroups;
+  lkf_rtcp_fb *fb;  // totals[0] records (fbCap allocated, and so on)
+  lkf_nack *nacks;
+  lkf_rtcp_ref *refs;
+  uint64_t fbCap, nackCap, refCap;
+  uint32_t *fbG;  // ngroups + 1
+  const lkf_rtcp_fb_result *fbOut;
+};
+hipError_t launch_rtcp_in_count(hipStream_t s, const RtcpInLaunch &a);
+hipError_t launch_rtcp_in_write(hipStream_t s, const RtcpInLaunch &a);
+hipError_t launch_rtcp_in_fold(hipStream_t s, const RtcpInLaunch &a);
 // -DLKF_CHECKED=1 builds of rtcp_kernels.hip: its own {violations, first site,
 // index, capacity} (sites 101 DownTrack handle, 102 ring slot, 103 entry /
-// request index); lkf_debug_check folds it into the record
+// request index, 104 arena byte, 105 / 106 / 107 fb / NACK / ref list index);
+// lkf_debug_check folds it into the record
 hipError_t read_check_rtcp(unsigned long long out[4], int reset);
 
 }  // namespace lkf

@@ -14,12 +14,19 @@
 //   k_sr_build      one thread per request: GetRtcpSenderReport (:596-714), the
 //                   lkf_rtcp_sr record and, when asked, the 28-byte packet.
 //   k_delta_sender  one thread per DownTrack: DeltaInfoSender (:723-808).
+//   k_rtcp_in_*     RTCP ingress (lkf_rtcp_ingest), one lane per compound
+//                   packet: count what the entry yields, write its fb records,
+//                   NACKed sequence numbers and pass-through records at the
+//                   scanned offsets (input order, no cursors), fold the
+//                   reports' results into the entry's rtt_ms.
 //
-// The semantics are rtcp_device.h's (shared with the host unit program).
+// The semantics are rtcp_device.h's and rtcp_in_device.h's (shared with the
+// host unit programs).
 #include <hip/hip_runtime.h>
 
 #include "kernels.h"
 #include "rtcp_device.h"
+#include "rtcp_in_device.h"
 
 namespace lkf {
 namespace {
@@ -34,7 +41,15 @@ using namespace rtcp;
 #ifndef LKF_CHECKED
 #define LKF_CHECKED 0
 #endif
-enum : u32 { CK_RTCP_DT = 101, CK_RTCP_SLOT = 102, CK_RTCP_ENTRY = 103 };
+enum : u32 {
+  CK_RTCP_DT = 101,
+  CK_RTCP_SLOT = 102,
+  CK_RTCP_ENTRY = 103,
+  CK_RTCP_ARENA = 104,
+  CK_RTCP_FB = 105,
+  CK_RTCP_NACK = 106,
+  CK_RTCP_REF = 107
+};
 #if LKF_CHECKED
 __device__ unsigned long long g_chk_rtcp[4];
 __device__ __noinline__ void chk_fail(u32 site, u64 idx, u64 cap) {
@@ -167,6 +182,124 @@ __global__ void k_delta_sender(DeltaSenderLaunch A) {
   A.rtcp[d].snap = R.snap;
   A.out[i] = o;
 }
+
+// ---- RTCP ingress (lkf_rtcp_ingest): rtcp_in_device.h's walk, one lane per entry
+__global__ void k_rtcp_in_count(RtcpInLaunch A) {
+  const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= A.n) return;
+  const lkf_rtcp_raw r = A.in[i];
+  const u32 d = u32(r.dt);
+  CHK(d < A.ndts, CK_RTCP_DT, d, A.ndts);
+  CHK(u64(r.off) + r.len <= A.arenaLen, CK_RTCP_ARENA, u64(r.off) + r.len, A.arenaLen);
+  lkf_rtcp_in_result o = {};
+  o.status = LKF_RTCP_IN_MALFORMED;
+  o.pli_layer = -1;
+  if (d < A.ndts && u64(r.off) + r.len <= A.arenaLen) {
+    rtcpin::Counts c;
+    if (rtcpin::walk(A.arena + r.off, r.len, A.dts[d].ssrc, c) == LKF_RTCP_IN_OK) {
+      o.status = LKF_RTCP_IN_OK;
+      o.fb_count = c.reports ? c.reports : 1;
+      o.reports = c.reports;
+      o.nacks = c.nacks;
+      o.plis = c.plis;
+      o.firs = c.firs;
+      o.ref_count = c.refs;
+    }
+  }
+  A.res[i] = o;
+  A.fbCnt[i] = o.fb_count;
+  A.nackCnt[i] = o.nacks;
+  A.refCnt[i] = o.ref_count;
+}
+
+// the write pass's sink: each list's cursor and end (the entry's share, from the scans)
+struct RtcpInWriter {
+  lkf_rtcp_fb *fb, *fbEnd;
+  lkf_nack *nk, *nkEnd;
+  lkf_rtcp_ref *rf, *rfEnd;
+  int32_t dt;
+  u32 entry, off;
+  __device__ void report(const u8 *b) {
+    if (fb >= fbEnd) return;
+    lkf_rtcp_fb f = {};
+    f.dt = dt;
+    f.flags = LKF_FB_HAS_RR;
+    rtcpin::read_report(b, f);
+    *fb++ = f;
+  }
+  __device__ void pair(u32 pid, u32 blp) {
+    rtcpin::pair_expand(pid, blp, [&](uint16_t sn) {
+      if (nk >= nkEnd) return;
+      lkf_nack x;
+      x.dt = dt;
+      x.sn = sn;
+      x.reserved = 0;
+      *nk++ = x;
+    });
+  }
+  __device__ void pli() {}
+  __device__ void fir() {}
+  __device__ void ref(u32 kind, u32 at, u32 size) {
+    if (rf >= rfEnd) return;
+    lkf_rtcp_ref x;
+    x.entry = entry;
+    x.kind = kind;
+    x.off = off + at;
+    x.len = size;
+    *rf++ = x;
+  }
+};
+
+__global__ void k_rtcp_in_write(RtcpInLaunch A) {
+  const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i <= A.ngroups)  // the fb list's DownTrack group bounds
+    A.fbG[i] = i < A.ngroups ? u32(A.fbOff[A.gEntry[i]]) : u32(A.totals[0]);
+  if (i >= A.n) return;
+  const lkf_rtcp_raw r = A.in[i];
+  const u32 d = u32(r.dt);
+  const u64 f0 = A.fbOff[i], n0 = A.nackOff[i], r0 = A.refOff[i];
+  lkf_rtcp_in_result &o = A.res[i];
+  const u32 fbc = o.fb_count, reports = o.reports, nacks = o.nacks, plis = o.plis, firs = o.firs, refc = o.ref_count;
+  o.fb_first = u32(f0);
+  o.nack_first = u32(n0);
+  o.ref_first = u32(r0);
+  if (o.status != LKF_RTCP_IN_OK || d >= A.ndts) return;
+  CHK(f0 + fbc <= A.fbCap, CK_RTCP_FB, f0 + fbc, A.fbCap);
+  CHK(n0 + nacks <= A.nackCap, CK_RTCP_NACK, n0 + nacks, A.nackCap);
+  CHK(r0 + refc <= A.refCap, CK_RTCP_REF, r0 + refc, A.refCap);
+  if (f0 + fbc > A.fbCap || n0 + nacks > A.nackCap || r0 + refc > A.refCap) return;
+  if (plis + firs) {  // sendPliOnce: CheckSync's layer, the request spatial layer
+    const int32_t req = A.hot[d].reqS;
+    o.pli_layer = req >= 0 ? req : -1;
+  }
+  lkf_rtcp_fb *fb = A.fb + f0;
+  if (!reports) {
+    lkf_rtcp_fb f = {};
+    f.dt = r.dt;
+    *fb = f;
+  }
+  RtcpInWriter w;
+  w.fb = fb, w.fbEnd = fb + reports;
+  w.nk = A.nacks + n0, w.nkEnd = w.nk + nacks;
+  w.rf = A.refs + r0, w.rfEnd = w.rf + refc;
+  w.dt = r.dt, w.entry = i, w.off = r.off;
+  rtcpin::walk(A.arena + r.off, r.len, A.dts[d].ssrc, w);
+  lkf_rtcp_fb &last = fb[fbc - 1];  // the counts ride on the entry's last record
+  last.nacks = nacks;
+  last.plis = plis;
+  last.firs = firs;
+}
+
+__global__ void k_rtcp_in_fold(RtcpInLaunch A) {
+  const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= A.n) return;
+  const u32 b = A.res[i].fb_first, c = A.res[i].fb_count;
+  u32 rtt = 0;
+  if (u64(b) + c <= A.fbCap)
+    for (u32 k = b; k < b + c; k++)
+      if (A.fbOut[k].flags & LKF_FB_RTT_CHANGED) rtt = A.fbOut[k].rtt_ms;  // rttToReport (downtrack.go:1529-1531)
+  A.res[i].rtt_ms = rtt;
+}
 }  // namespace
 
 hipError_t launch_rr_update(hipStream_t s, const RrUpdateLaunch &a) {
@@ -184,6 +317,24 @@ hipError_t launch_sr_build(hipStream_t s, const SrBuildLaunch &a) {
 hipError_t launch_delta_sender(hipStream_t s, const DeltaSenderLaunch &a) {
   if (!a.n) return hipSuccess;
   hipLaunchKernelGGL(k_delta_sender, dim3((a.n + 63) / 64), dim3(64), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_rtcp_in_count(hipStream_t s, const RtcpInLaunch &a) {
+  if (!a.n) return hipSuccess;
+  hipLaunchKernelGGL(k_rtcp_in_count, dim3((a.n + 63) / 64), dim3(64), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_rtcp_in_write(hipStream_t s, const RtcpInLaunch &a) {
+  if (!a.n) return hipSuccess;
+  hipLaunchKernelGGL(k_rtcp_in_write, dim3((a.n + 64) / 64), dim3(64), 0, s, a);  // n + 1 lanes: the group bounds
+  return hipGetLastError();
+}
+
+hipError_t launch_rtcp_in_fold(hipStream_t s, const RtcpInLaunch &a) {
+  if (!a.n) return hipSuccess;
+  hipLaunchKernelGGL(k_rtcp_in_fold, dim3((a.n + 63) / 64), dim3(64), 0, s, a);
   return hipGetLastError();
 }
 
