@@ -3932,6 +3932,7 @@ __global__ void __launch_bounds__(EMIT_T) k_emit(EmitArgs A) {
       const u32 ji = cur + 1 + lane;
       const u32 st = ji < nrec ? sCs[ji] : 0xffffffffu;
       u64 inW = __ballot(st < wEnd);
+      // (not reachable while EMIT_G is 64: lane 63 names record cur + 64, past the group, so its st is never < wEnd)
       if (inW == ~0ull) {  // more than 63 records start in the window: cut it
         wEnd = rl32(st, 63);
         inW = __ballot(st < wEnd);
