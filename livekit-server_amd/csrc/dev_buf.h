@@ -1,5 +1,5 @@
 // dev_buf.h — an owning device buffer: pointer + element capacity in one
-// move-only value.  No HIP header: the two allocation functions below are
+// move-only value, and the families of such buffers that grow together.  No HIP header: the two allocation functions below are
 // defined by engine.cpp (hipMalloc / hipFree + the range registry) and by a
 // malloc-backed fake in host_unit.cpp; a status is the hipError_t value as an
 // int (0: success).
@@ -68,6 +68,38 @@ class DevBuf {
 template <typename... B>
 void release_all(B &...b) {
   (void)(..., b.reset());
+}
+
+// A buffer of a scratch family (buffers that one call uses together): `need`
+// elements now; when the family regrows it gets max(size, floor) elements,
+// size = need unless given (headroom for the next, larger call).
+template <typename T>
+struct Want {
+  DevBuf<T> &b;
+  uint64_t need, size;
+};
+template <typename T>
+Want<T> want(DevBuf<T> &b, uint64_t need, uint64_t floor, uint64_t size = 0) {
+  if (!size) size = need;
+  return {b, need, size > floor ? size : floor};
+}
+
+template <typename... T>
+bool family_short(const Want<T> &...w) {
+  return (... || (w.need > w.b.cap()));
+}
+
+// Frees the whole family, then allocates every buffer again in the order
+// listed, none smaller than it was: calls that share a family with different
+// shapes settle on one size instead of reallocating in turn.  Stops at the
+// first failure and returns its status (the buffers behind it stay empty).
+template <typename... T>
+int regrow_family(Want<T>... w) {
+  (void)(..., (w.size = w.size > w.b.cap() ? w.size : w.b.cap()));
+  release_all(w.b...);
+  int r = 0;
+  (void)(... && ((r = w.b.alloc(w.size)) == 0));
+  return r;
 }
 
 }  // namespace lkf

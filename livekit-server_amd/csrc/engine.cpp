@@ -38,6 +38,7 @@
 #include "ctl_csr.h"
 #include "dev_buf.h"
 #include "fwd_state.h"
+#include "handles.h"
 #include "hip_own.h"
 #include "kernels.h"
 
@@ -927,6 +928,108 @@ static int flush_topology(lkf_engine *e) {
   return upload_done(e);
 }
 
+// Every queued stage waited for, behind the pending topology (the tracker
+// calls, which no topology change reaches, pass flush = false).
+static int quiesce(lkf_engine *e, bool flush = true) {
+  if (flush)
+    if (const int rc = flush_topology(e)) return rc;
+  return drain_streams(e);
+}
+
+// One row of a per-handle table written back from the host (the engine quiesced).
+template <typename T>
+static int write_row(lkf_engine *e, T *dst, const T &row, const char *what) {
+  HIPCHK(hipMemcpy(dst, &row, sizeof(T), hipMemcpyHostToDevice), what);
+  return upload_done(e);
+}
+
+// ---- the control calls' frame ------------------------------------------------
+// A control-rate call checks its handles, orders a stream, grows its scratch,
+// uploads a short request list, runs one or two small kernels and hands the
+// results back.  The stream and what precedes the call is one of three orders:
+//   Quiesced      the engine's own stream, every stream drained first; blocking
+//                 uploads, closed by uploaded() (upload_done)
+//   BehindDecide  the decide stream, behind the queued decides and whatever an
+//                 earlier control call left on the own stream.  The host waits
+//                 for that stream alone: queued emits, sender statistics and
+//                 protect stages keep overlapping the call
+//   BehindSender  the sender stream, behind every queued stage that updates
+//                 RTPStatsSender (sender_after_queued)
+static int rebuild_twcc(lkf_engine *e);
+enum class Order { Quiesced, BehindDecide, BehindSender };
+
+struct Frame {
+  lkf_engine *e;
+  Order order;
+  hipStream_t s;
+  bool grew = false;  // the last grow() reallocated its family
+
+  Frame(lkf_engine *eng, Order o)
+      : e(eng),
+        order(o),
+        s(o == Order::Quiesced ? eng->own.get() : o == Order::BehindDecide ? eng->decS.get() : eng->sendS.get()) {}
+
+  // flush: the pending topology first; twcc: then the transport-wide counters'
+  // lists of a transport-cc DownTrack added or bound since the last run
+  int open(bool flush = true, bool twcc = false) {
+    if (order == Order::Quiesced) return quiesce(e, flush);
+    if (flush)
+      if (const int rc = flush_topology(e)) return rc;
+    HIPCHK(hipSetDevice(e->dev), "hipSetDevice");
+    if (twcc && e->twccDirty)
+      if (const int rc = rebuild_twcc(e)) return rc;
+    if (order == Order::BehindSender) return sender_after_queued(e);
+    HIPCHK(hipEventRecord(e->inEv, e->own), "event");
+    HIPCHK(hipStreamWaitEvent(s, e->inEv, 0), "wait own stream");
+    return LKF_OK;
+  }
+
+  // A scratch family is freed only when nothing queued can still read it: if
+  // any of its buffers is too small, the frame's stream is waited for once,
+  // the whole family released, and every buffer allocated again, none smaller
+  // than it was (regrow_family, dev_buf.h).  The last-listed buffer's capacity
+  // is what all of them hold (the *_cap() helpers read it): after a failed
+  // grow it is 0 and the next call retries.
+  template <typename... T>
+  int grow(const char *what, Want<T>... w) {
+    grew = family_short(w...);
+    if (!grew) return LKF_OK;
+    HIPCHK(hipStreamSynchronize(s), "sync before a scratch family regrows");
+    const int r = regrow_family(w...);
+    return r ? fail(e, what, static_cast<hipError_t>(r)) : LKF_OK;
+  }
+
+  // host -> device: ahead of the frame's kernels on its stream; Quiesced: a
+  // blocking copy (uploaded() after the last one, before the first launch)
+  int up(void *dst, const void *src, size_t bytes, const char *what) {
+    if (order == Order::Quiesced)
+      HIPCHK(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice), what);
+    else
+      HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s), what);
+    return LKF_OK;
+  }
+  int uploaded() { return order == Order::Quiesced ? upload_done(e) : LKF_OK; }
+
+  // device -> host, range-checked, behind the frame's kernels: dst holds the
+  // bytes after wait().  (Once the stream is idle a call may also copy with
+  // D2H, through the pinned bounce buffer.)
+  int down(void *dst, const void *src, size_t bytes, const char *what) {
+    CHKRANGE(src, bytes, what);
+    HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s), what);
+    return LKF_OK;
+  }
+  int wait() {
+    HIPCHK(hipStreamSynchronize(s), "sync");
+    return LKF_OK;
+  }
+};
+// a step of a frame (or any call that returns a code): return its failure
+#define STEP(call)                 \
+  do {                             \
+    const int _rc = (call);        \
+    if (_rc) return _rc;           \
+  } while (0)
+
 extern "C" {
 
 const char *lkf_version(void) { return "lkfwd 0.2 (gfx950)"; }
@@ -1305,28 +1408,21 @@ static int rtcp_stop(lkf_engine *e, size_t dt) {
 
 int lkf_remove_downtrack(lkf_engine *e, int32_t dt) {
   if (!e || dt < 0 || dt >= int32_t(e->dtp.size())) return LKF_EINVAL;
-  int rc = flush_topology(e);
-  if (rc) return rc;
-  rc = drain_streams(e);
-  if (rc) return rc;
+  STEP(quiesce(e));
   e->active[dt] = 0;
   e->topoGen++;
   uint8_t zero = 0;
   HIPCHK(hipMemcpy(reinterpret_cast<uint8_t *>(e->dDTs + dt) + offsetof(DevDT, active), &zero, 1,
                    hipMemcpyHostToDevice),
          "remove copy");
-  rc = rtcp_stop(e, size_t(dt));
-  if (rc) return rc;
+  STEP(rtcp_stop(e, size_t(dt)));
   e->schedDirty = true;
   return upload_done(e);
 }
 
 int lkf_remove_track(lkf_engine *e, int32_t track) {
   if (!e || track < 0 || track >= int32_t(e->tracks.size())) return LKF_EINVAL;
-  int rc = flush_topology(e);
-  if (rc) return rc;
-  rc = drain_streams(e);
-  if (rc) return rc;
+  STEP(quiesce(e));
   if (!e->trackActive[track]) return LKF_OK;
   e->trackActive[track] = 0;
   const uint8_t zero = 0, one = 1;
@@ -1337,8 +1433,7 @@ int lkf_remove_track(lkf_engine *e, int32_t track) {
       HIPCHK(hipMemcpy(reinterpret_cast<uint8_t *>(e->dDTs + d) + offsetof(DevDT, active), &zero, 1,
                        hipMemcpyHostToDevice),
              "remove copy");
-      rc = rtcp_stop(e, d);
-      if (rc) return rc;
+      STEP(rtcp_stop(e, d));
     }
   for (size_t sid = 0; sid < e->streams.size(); sid++)  // Buffer.Close of its streams
     if (e->streams[sid].track == track)
@@ -2670,10 +2765,7 @@ int lkf_drain_protected(lkf_engine *e, uint8_t *arena, uint64_t cap, uint64_t *a
 
 int lkf_sender_stats_get(lkf_engine *e, int32_t dt, lkf_sender_stats *out) {
   if (!e || !out || dt < 0 || dt >= int32_t(e->dtp.size())) return LKF_EINVAL;
-  int rc = flush_topology(e);
-  if (rc) return rc;
-  rc = drain_streams(e);
-  if (rc) return rc;
+  STEP(quiesce(e));
   SenderStats s;
   D2H(&s, e->dSS + dt, sizeof(s), "sender stats copy");
   std::memset(out, 0, sizeof(*out));
@@ -2707,10 +2799,7 @@ int lkf_sender_stats_get(lkf_engine *e, int32_t dt, lkf_sender_stats *out) {
 
 int lkf_sender_sninfo(lkf_engine *e, int32_t dt, uint64_t esn, uint32_t *out) {
   if (!e || !out || dt < 0 || dt >= int32_t(e->dtp.size())) return LKF_EINVAL;
-  int rc = flush_topology(e);
-  if (rc) return rc;
-  rc = drain_streams(e);
-  if (rc) return rc;
+  STEP(quiesce(e));
   D2H(out, e->dSSRing + size_t(dt) * kSnInfoSize + (esn & (kSnInfoSize - 1)), sizeof(uint32_t), "sninfo copy");
   return LKF_OK;
 }
@@ -2718,10 +2807,7 @@ int lkf_sender_sninfo(lkf_engine *e, int32_t dt, uint64_t esn, uint32_t *out) {
 int lkf_sender_stats_seed(lkf_engine *e, int32_t dt, int32_t from_dt) {
   if (!e || dt < 0 || dt >= int32_t(e->dtp.size()) || from_dt < 0 || from_dt >= int32_t(e->dtp.size()))
     return LKF_EINVAL;
-  int rc = flush_topology(e);
-  if (rc) return rc;
-  rc = drain_streams(e);
-  if (rc) return rc;
+  STEP(quiesce(e));
   SenderStats from, to;
   D2H(&from, e->dSS + from_dt, sizeof(from), "sender stats copy");
   if (!from.initialized) return LKF_OK;  // rtpStatsBase.seed: from must be initialized
@@ -2761,39 +2847,18 @@ static_assert(sizeof(lkf_rtcp_fb) == 48 && sizeof(lkf_rtcp_sr) == 40 && sizeof(l
 
 int lkf_sender_rtcp_get(lkf_engine *e, int32_t dt, lkf_sender_rtcp *out) {
   if (!e || !out || dt < 0 || dt >= int32_t(e->dtp.size())) return LKF_EINVAL;
-  int rc = flush_topology(e);
-  if (rc) return rc;
-  rc = drain_streams(e);
-  if (rc) return rc;
+  STEP(quiesce(e));
   D2H(out, e->dRtcp + dt, sizeof(*out), "sender rtcp copy");
   return LKF_OK;
 }
 
-// The three calls' common frame: the sender stream is ordered after every
-// queued stage that updates RTPStatsSender (sender_after_queued), the call's
-// input goes up and its kernel runs on that stream, and the host waits for
-// the results.  The scratch buffers grow only once the stream is idle.
-static int rtcp_begin(lkf_engine *e, size_t inBytes, size_t groups, size_t outBytes) {
-  int rc = flush_topology(e);
-  if (rc) return rc;
-  HIPCHK(hipSetDevice(e->dev), "hipSetDevice");
-  rc = sender_after_queued(e);
-  if (rc) return rc;
-  if (inBytes > e->dRtcpIn.cap() || groups > e->dRtcpGroups.cap() || outBytes > e->dRtcpOut.cap()) {
-    HIPCHK(hipStreamSynchronize(e->sendS), "sync sender stream");
-    HIPCHK(e->dRtcpIn.reserve(2 * inBytes, 1 << 16), "alloc rtcp in");
-    HIPCHK(e->dRtcpGroups.reserve(2 * groups, 4096), "alloc rtcp groups");
-    HIPCHK(e->dRtcpOut.reserve(2 * outBytes, 1 << 16), "alloc rtcp out");
-  }
-  return LKF_OK;
-}
-static int rtcp_end(lkf_engine *e, void *dst, size_t bytes, std::vector<uint8_t> &tmp) {
-  tmp.resize(bytes);
-  CHKRANGE(e->dRtcpOut, bytes, "async d2h");
-  HIPCHK(hipMemcpyAsync(tmp.data(), e->dRtcpOut, bytes, hipMemcpyDeviceToHost, e->sendS), "rtcp results copy");
-  HIPCHK(hipStreamSynchronize(e->sendS), "sync");
-  std::memcpy(dst, tmp.data(), bytes);
-  return LKF_OK;
+// The three calls run behind the sender stream's queued work (Order::BehindSender):
+// the input goes up, the kernel runs and the results come back on that stream.
+// Their scratch is one family: input bytes, group bounds, result bytes.
+static int rtcp_grow(Frame &f, size_t inBytes, size_t groups, size_t outBytes) {
+  lkf_engine *e = f.e;
+  return f.grow("alloc rtcp scratch", want(e->dRtcpIn, inBytes, 1 << 16, 2 * inBytes),
+                want(e->dRtcpGroups, groups, 4096, 2 * groups), want(e->dRtcpOut, outBytes, 1 << 16, 2 * outBytes));
 }
 
 int lkf_rtcp_feedback(lkf_engine *e, const lkf_rtcp_fb *in, uint32_t n, int64_t now_ns, lkf_rtcp_fb_result *out) {
@@ -2801,23 +2866,12 @@ int lkf_rtcp_feedback(lkf_engine *e, const lkf_rtcp_fb *in, uint32_t n, int64_t 
   if (!n) return LKF_OK;
   // groups: one per DownTrack's contiguous entries (a DownTrack must not reappear)
   std::vector<uint32_t> g;
-  std::vector<uint8_t> seen(e->dtp.size(), 0);
-  for (uint32_t i = 0; i < n; i++) {
-    const int32_t dt = in[i].dt;
-    if (dt < 0 || dt >= int32_t(e->dtp.size())) return LKF_EINVAL;
-    if (i == 0 || in[i - 1].dt != dt) {
-      if (seen[dt]) return LKF_EORDER;
-      seen[dt] = 1;
-      g.push_back(i);
-    }
-  }
-  g.push_back(n);
-  int rc = rtcp_begin(e, size_t(n) * sizeof(lkf_rtcp_fb), g.size(), size_t(n) * sizeof(lkf_rtcp_fb_result));
-  if (rc) return rc;
-  hipStream_t s = e->sendS;
-  HIPCHK(hipMemcpyAsync(e->dRtcpIn, in, size_t(n) * sizeof(lkf_rtcp_fb), hipMemcpyHostToDevice, s), "rtcp fb copy");
-  HIPCHK(hipMemcpyAsync(e->dRtcpGroups, g.data(), g.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s),
-         "rtcp groups copy");
+  STEP(check_handles(&in[0].dt, sizeof(*in), n, e->dtp.size(), {Repeat::Groups, &g, true}));
+  Frame f(e, Order::BehindSender);
+  STEP(f.open());
+  STEP(rtcp_grow(f, size_t(n) * sizeof(lkf_rtcp_fb), g.size(), size_t(n) * sizeof(lkf_rtcp_fb_result)));
+  STEP(f.up(e->dRtcpIn, in, size_t(n) * sizeof(lkf_rtcp_fb), "rtcp fb copy"));
+  STEP(f.up(e->dRtcpGroups, g.data(), g.size() * sizeof(uint32_t), "rtcp groups copy"));
   RrUpdateLaunch a;
   a.in = reinterpret_cast<const lkf_rtcp_fb *>(e->dRtcpIn.get());
   a.gBegin = e->dRtcpGroups;
@@ -2829,29 +2883,23 @@ int lkf_rtcp_feedback(lkf_engine *e, const lkf_rtcp_fb *in, uint32_t n, int64_t 
   a.rtcp = e->dRtcp;
   a.ndts = uint32_t(e->dtp.size());
   a.out = reinterpret_cast<lkf_rtcp_fb_result *>(e->dRtcpOut.get());
-  HIPCHK(launch_rr_update(s, a), "rr update");
-  std::vector<uint8_t> tmp;
-  return rtcp_end(e, out, size_t(n) * sizeof(lkf_rtcp_fb_result), tmp);
+  HIPCHK(launch_rr_update(f.s, a), "rr update");
+  STEP(f.down(out, e->dRtcpOut, size_t(n) * sizeof(lkf_rtcp_fb_result), "rtcp results copy"));
+  return f.wait();
 }
 
 int lkf_rtcp_sender_reports(lkf_engine *e, const lkf_rtcp_sr_req *req, uint32_t n, int64_t now_ns, lkf_rtcp_sr *out,
                             uint8_t *wire28) {
   if (!e || (n && (!req || !out))) return LKF_EINVAL;
   if (!n) return LKF_OK;
-  std::vector<uint8_t> seen(e->dtp.size(), 0);
-  for (uint32_t i = 0; i < n; i++) {
-    const int32_t dt = req[i].dt;
-    if (dt < 0 || dt >= int32_t(e->dtp.size())) return LKF_EINVAL;
-    if (seen[dt]) return LKF_EORDER;  // one thread per request: a DownTrack's state has one writer
-    seen[dt] = 1;
-  }
+  // one thread per request: a DownTrack's state has one writer
+  STEP(check_handles(&req[0].dt, sizeof(*req), n, e->dtp.size(), {Repeat::DistinctEorder}));
   // results: n records (40 B each, so the wire bytes behind them stay 4-B aligned), then 28 B per request
   const size_t recBytes = size_t(n) * sizeof(lkf_rtcp_sr), wireBytes = wire28 ? size_t(n) * 28 : 0;
-  int rc = rtcp_begin(e, size_t(n) * sizeof(lkf_rtcp_sr_req), 0, recBytes + wireBytes);
-  if (rc) return rc;
-  hipStream_t s = e->sendS;
-  HIPCHK(hipMemcpyAsync(e->dRtcpIn, req, size_t(n) * sizeof(lkf_rtcp_sr_req), hipMemcpyHostToDevice, s),
-         "rtcp sr requests copy");
+  Frame f(e, Order::BehindSender);
+  STEP(f.open());
+  STEP(rtcp_grow(f, size_t(n) * sizeof(lkf_rtcp_sr_req), 0, recBytes + wireBytes));
+  STEP(f.up(e->dRtcpIn, req, size_t(n) * sizeof(lkf_rtcp_sr_req), "rtcp sr requests copy"));
   SrBuildLaunch a;
   a.req = reinterpret_cast<const lkf_rtcp_sr_req *>(e->dRtcpIn.get());
   a.n = n;
@@ -2862,10 +2910,9 @@ int lkf_rtcp_sender_reports(lkf_engine *e, const lkf_rtcp_sr_req *req, uint32_t 
   a.ndts = uint32_t(e->dtp.size());
   a.out = reinterpret_cast<lkf_rtcp_sr *>(e->dRtcpOut.get());
   a.wire = wire28 ? e->dRtcpOut.get() + recBytes : nullptr;
-  HIPCHK(launch_sr_build(s, a), "sr build");
-  std::vector<uint8_t> tmp;
-  rc = rtcp_end(e, out, recBytes, tmp);
-  if (rc) return rc;
+  HIPCHK(launch_sr_build(f.s, a), "sr build");
+  STEP(f.down(out, e->dRtcpOut, recBytes, "rtcp results copy"));
+  STEP(f.wait());
   if (wire28) D2H(wire28, e->dRtcpOut.get() + recBytes, wireBytes, "rtcp wire copy");
   return LKF_OK;
 }
@@ -2873,16 +2920,11 @@ int lkf_rtcp_sender_reports(lkf_engine *e, const lkf_rtcp_sr_req *req, uint32_t 
 int lkf_sender_delta_info(lkf_engine *e, const int32_t *dts, uint32_t n, lkf_rtp_delta_info *out) {
   if (!e || (n && (!dts || !out))) return LKF_EINVAL;
   if (!n) return LKF_OK;
-  std::vector<uint8_t> seen(e->dtp.size(), 0);
-  for (uint32_t i = 0; i < n; i++) {
-    if (dts[i] < 0 || dts[i] >= int32_t(e->dtp.size())) return LKF_EINVAL;
-    if (seen[dts[i]]) return LKF_EORDER;
-    seen[dts[i]] = 1;
-  }
-  int rc = rtcp_begin(e, size_t(n) * sizeof(int32_t), 0, size_t(n) * sizeof(lkf_rtp_delta_info));
-  if (rc) return rc;
-  hipStream_t s = e->sendS;
-  HIPCHK(hipMemcpyAsync(e->dRtcpIn, dts, size_t(n) * sizeof(int32_t), hipMemcpyHostToDevice, s), "rtcp dts copy");
+  STEP(check_handles(dts, sizeof(*dts), n, e->dtp.size(), {Repeat::DistinctEorder}));
+  Frame f(e, Order::BehindSender);
+  STEP(f.open());
+  STEP(rtcp_grow(f, size_t(n) * sizeof(int32_t), 0, size_t(n) * sizeof(lkf_rtp_delta_info)));
+  STEP(f.up(e->dRtcpIn, dts, size_t(n) * sizeof(int32_t), "rtcp dts copy"));
   DeltaSenderLaunch a;
   a.dts = reinterpret_cast<const int32_t *>(e->dRtcpIn.get());
   a.n = n;
@@ -2890,17 +2932,14 @@ int lkf_sender_delta_info(lkf_engine *e, const int32_t *dts, uint32_t n, lkf_rtp
   a.rtcp = e->dRtcp;
   a.ndts = uint32_t(e->dtp.size());
   a.out = reinterpret_cast<lkf_rtp_delta_info *>(e->dRtcpOut.get());
-  HIPCHK(launch_delta_sender(s, a), "delta sender");
-  std::vector<uint8_t> tmp;
-  return rtcp_end(e, out, size_t(n) * sizeof(lkf_rtp_delta_info), tmp);
+  HIPCHK(launch_delta_sender(f.s, a), "delta sender");
+  STEP(f.down(out, e->dRtcpOut, size_t(n) * sizeof(lkf_rtp_delta_info), "rtcp results copy"));
+  return f.wait();
 }
 
 int lkf_get_state(lkf_engine *e, int32_t dt, lkf_fwd_state *o) {
   if (!e || !o || dt < 0 || dt >= int32_t(e->dtp.size())) return LKF_EINVAL;
-  int rc = flush_topology(e);
-  if (rc) return rc;
-  rc = drain_streams(e);
-  if (rc) return rc;
+  STEP(quiesce(e));
   DTHot h;
   D2H(&h, e->dHot + dt, sizeof(h), "state copy");
   std::memset(o, 0, sizeof(*o));
@@ -2930,10 +2969,7 @@ int lkf_get_state(lkf_engine *e, int32_t dt, lkf_fwd_state *o) {
 int lkf_seed_state(lkf_engine *e, int32_t dt, const lkf_fwd_state *i) {
   if (!e || !i || dt < 0 || dt >= int32_t(e->dtp.size())) return LKF_EINVAL;
   if (!i->started) return LKF_OK;  // SeedState forwarder.go:360-362
-  int rc = flush_topology(e);
-  if (rc) return rc;
-  rc = drain_streams(e);
-  if (rc) return rc;
+  STEP(quiesce(e));
   DTHot h;
   D2H(&h, e->dHot + dt, sizeof(h), "state copy");
   auto setf = [&](uint32_t f, bool v) { h.flags = v ? (h.flags | f) : (h.flags & ~f); };
@@ -2959,31 +2995,23 @@ int lkf_seed_state(lkf_engine *e, int32_t dt, const lkf_fwd_state *i) {
   h.preStartTime = i->pre_start_time_ns;
   h.extFirstTS = i->ext_first_ts;
   h.refTSOffset = i->ref_ts_offset;
-  HIPCHK(hipMemcpy(e->dHot + dt, &h, sizeof(h), hipMemcpyHostToDevice), "seed copy");
-  return upload_done(e);
+  return write_row(e, e->dHot + dt, h, "seed copy");
 }
 
 int lkf_seq_lookup(lkf_engine *e, int32_t dt, const uint16_t *sns, uint32_t n, int64_t now_ns, lkf_seq_meta *out,
                    uint32_t *n_out) {
   if (!e || dt < 0 || dt >= int32_t(e->dtp.size()) || (n && (!sns || !out))) return LKF_EINVAL;
-  int rc = flush_topology(e);
-  if (rc) return rc;
-  rc = drain_streams(e);
-  if (rc) return rc;
-  if (n > e->dSns.cap() || n > e->dSeqOut.cap()) {
-    release_all(e->dSns, e->dSeqOut);
-    HIPCHK(e->dSns.reserve(n, 256), "alloc");
-    HIPCHK(e->dSeqOut.reserve(n, 256), "alloc");
-  }
+  Frame f(e, Order::Quiesced);
+  STEP(f.open());
+  STEP(f.grow("alloc seq lookup scratch", want(e->dSns, n, 256), want(e->dSeqOut, n, 256)));
   if (!e->dSeqN) HIPCHK(e->dSeqN.alloc(1), "alloc");
-  if (n) HIPCHK(hipMemcpy(e->dSns, sns, n * sizeof(uint16_t), hipMemcpyHostToDevice), "sns copy");
-  rc = upload_done(e);
-  if (rc) return rc;
-  HIPCHK(launch_seq_lookup(e->own, e->dHot, e->dSeq, e->cfg.seq_size, e->dSrm, e->srmStride, e->srmCap, uint32_t(dt),
+  if (n) STEP(f.up(e->dSns, sns, n * sizeof(uint16_t), "sns copy"));
+  STEP(f.uploaded());
+  HIPCHK(launch_seq_lookup(f.s, e->dHot, e->dSeq, e->cfg.seq_size, e->dSrm, e->srmStride, e->srmCap, uint32_t(dt),
                            e->dSns, n, now_ns / 1000000,
                            e->dSeqOut, e->dSeqN),
          "seq lookup");
-  HIPCHK(hipStreamSynchronize(e->own), "sync");
+  STEP(f.wait());
   uint32_t cnt = 0;
   D2H(&cnt, e->dSeqN, sizeof(cnt), "n copy");
   if (cnt) D2H(out, e->dSeqOut, cnt * sizeof(lkf_seq_meta), "out copy");
@@ -2993,34 +3021,26 @@ int lkf_seq_lookup(lkf_engine *e, int32_t dt, const uint16_t *sns, uint32_t n, i
 
 // The seven NACK -> RTX buffers grow together, dRtxOff last: its capacity is
 // what all of them hold (0 after a failed grow, which the next call retries).
-static uint64_t rtx_cap(const lkf_engine *e) { return e->dRtxOff.cap(); }
-static int rtx_reserve(lkf_engine *e, uint32_t n) {
-  if (n <= rtx_cap(e)) return LKF_OK;
-  release_all(e->dNacks, e->dNackG, e->dNackValid, e->dRtx, e->dRtxSrc, e->dRtxLen, e->dRtxOff);
-  HIPCHK(e->dNacks.reserve(n, 1024), "alloc nacks");
-  HIPCHK(e->dNackG.reserve(uint64_t(n) + 1, 1025), "alloc nack groups");
-  HIPCHK(e->dNackValid.reserve(n, 1024), "alloc nack valid");
-  HIPCHK(e->dRtx.reserve(n, 1024), "alloc rtx");
-  HIPCHK(e->dRtxSrc.reserve(n, 1024), "alloc rtx src");
-  HIPCHK(e->dRtxLen.reserve(n, 1024), "alloc rtx len");
-  HIPCHK(e->dRtxOff.reserve(n, 1024), "alloc rtx off");
-  return LKF_OK;
+static int rtx_grow(Frame &f, uint32_t n) {
+  lkf_engine *e = f.e;
+  return f.grow("alloc rtx scratch", want(e->dNacks, n, 1024), want(e->dNackG, uint64_t(n) + 1, 1025),
+                want(e->dNackValid, n, 1024), want(e->dRtx, n, 1024), want(e->dRtxSrc, n, 1024),
+                want(e->dRtxLen, n, 1024), want(e->dRtxOff, n, 1024));
 }
 
-// The lookup itself on stream s: m NACKs at `list` in ngroups non-empty
+// The lookup itself on the frame's stream: m NACKs at `list` in ngroups non-empty
 // DownTrack groups (bounds in dNackG), the records compacted on the host.
-static int rtx_lookup_run(lkf_engine *e, hipStream_t s, const lkf_nack *list, uint32_t ngroups, uint32_t m,
-                          int64_t now_ns, lkf_rtx *out, uint32_t cap, uint32_t *n_out) {
-  HIPCHK(launch_rtx_lookup(s, e->dHot, e->dSeq, e->cfg.seq_size, e->dSrm, e->srmStride, e->srmCap, list, e->dNackG,
+static int rtx_lookup_run(Frame &f, const lkf_nack *list, uint32_t ngroups, uint32_t m, int64_t now_ns, lkf_rtx *out,
+                          uint32_t cap, uint32_t *n_out) {
+  lkf_engine *e = f.e;
+  HIPCHK(launch_rtx_lookup(f.s, e->dHot, e->dSeq, e->cfg.seq_size, e->dSrm, e->srmStride, e->srmCap, list, e->dNackG,
                            ngroups, now_ns / 1000000, e->dRtx, e->dNackValid),
          "rtx lookup");
   std::vector<lkf_rtx> r(m);
   std::vector<uint32_t> v(m);
-  CHKRANGE(e->dRtx, m * sizeof(lkf_rtx), "async d2h");
-  HIPCHK(hipMemcpyAsync(r.data(), e->dRtx, m * sizeof(lkf_rtx), hipMemcpyDeviceToHost, s), "rtx copy");
-  CHKRANGE(e->dNackValid, m * sizeof(uint32_t), "async d2h");
-  HIPCHK(hipMemcpyAsync(v.data(), e->dNackValid, m * sizeof(uint32_t), hipMemcpyDeviceToHost, s), "valid copy");
-  HIPCHK(hipStreamSynchronize(s), "sync");
+  STEP(f.down(r.data(), e->dRtx, m * sizeof(lkf_rtx), "rtx copy"));
+  STEP(f.down(v.data(), e->dNackValid, m * sizeof(uint32_t), "valid copy"));
+  STEP(f.wait());
   uint32_t k = 0;
   for (uint32_t i = 0; i < m; i++) k += v[i];
   *n_out = k;
@@ -3037,16 +3057,9 @@ int lkf_rtx_lookup(lkf_engine *e, const lkf_nack *nacks, uint32_t n, int64_t now
   *n_out = 0;
   // groups: one per DownTrack's contiguous NACK list (a DownTrack must not reappear)
   std::vector<uint32_t> gStart;
-  std::vector<uint8_t> seen(e->dtp.size(), 0);
-  for (uint32_t i = 0; i < n; i++) {
-    const int32_t dt = nacks[i].dt;
-    if (dt < 0 || dt >= int32_t(e->dtp.size())) return LKF_EINVAL;
-    if (i == 0 || nacks[i - 1].dt != dt) {
-      if (seen[dt]) return LKF_EORDER;
-      seen[dt] = 1;
-      if (e->active[dt]) gStart.push_back(i);  // a removed DownTrack answers no NACK
-    }
-  }
+  if (n)  // (a removed DownTrack answers no NACK: its group is left out)
+    STEP(check_handles(&nacks[0].dt, sizeof(*nacks), n, e->dtp.size(),
+                       {Repeat::Groups, &gStart, false, e->active.data(), Inactive::Skip}));
   e->rtxNow = now_ns;  // retransmitPackets' time.Now() for the RTX sendingPacket (lkf_rtx_emit)
   if (gStart.empty()) return LKF_OK;
   // group ends: the next group's start or the end of its DownTrack's run
@@ -3061,31 +3074,24 @@ int lkf_rtx_lookup(lkf_engine *e, const lkf_nack *nacks, uint32_t n, int64_t now
   }
   gb[gStart.size()] = uint32_t(packed.size());
   const uint32_t m = uint32_t(packed.size());
-  int rc = flush_topology(e);
-  if (rc) return rc;
   // The lookup reads and updates the sequencer records and the DownTracks'
   // hot state, which between runs only the decide stream touches: ordered on
   // that stream behind the queued decides (their emits keep running), as the
-  // allocation calls.
-  hipStream_t s = e->decS;
-  HIPCHK(hipSetDevice(e->dev), "hipSetDevice");
-  if (m > rtx_cap(e)) HIPCHK(hipStreamSynchronize(s), "sync decide stream");  // (rtx_reserve reallocates)
-  rc = rtx_reserve(e, m);
-  if (rc) return rc;
-  HIPCHK(hipEventRecord(e->inEv, e->own), "event");
-  HIPCHK(hipStreamWaitEvent(s, e->inEv, 0), "wait own stream");
-  HIPCHK(hipMemcpyAsync(e->dNacks, packed.data(), m * sizeof(lkf_nack), hipMemcpyHostToDevice, s), "nacks copy");
-  HIPCHK(hipMemcpyAsync(e->dNackG, gb.data(), gb.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s),
-         "groups copy");
-  return rtx_lookup_run(e, s, e->dNacks, uint32_t(gStart.size()), m, now_ns, out, cap, n_out);
+  // allocation calls.  (The decide stream is waited for only if the scratch regrows.)
+  Frame f(e, Order::BehindDecide);
+  STEP(f.open());
+  STEP(rtx_grow(f, m));
+  STEP(f.up(e->dNacks, packed.data(), m * sizeof(lkf_nack), "nacks copy"));
+  STEP(f.up(e->dNackG, gb.data(), gb.size() * sizeof(uint32_t), "groups copy"));
+  return rtx_lookup_run(f, e->dNacks, uint32_t(gStart.size()), m, now_ns, out, cap, n_out);
 }
 
 // ---- RTCP ingress (rtcp_kernels.hip k_rtcp_in_*; the parse is rtcp_in_device.h) ----
 static_assert(sizeof(lkf_rtcp_raw) == 12 && sizeof(lkf_rtcp_in_result) == 48 && sizeof(lkf_rtcp_ref) == 16,
               "RTCP ingress records");
 
-// The call frame is the three RTCP calls' (rtcp_begin): the sender stream
-// ordered after every queued stage, the buffers grown only while it is idle.
+// The call frame is the three RTCP calls' (Order::BehindSender): the sender
+// stream ordered after every queued stage, the buffers grown only while it is idle.
 // Count pass -> scans -> the totals back on the host (the lists are sized by
 // them, never by a guess about the bytes) -> write pass -> k_rr_update on the
 // device-resident fb list -> the fold of its results into the entries.
@@ -3100,58 +3106,33 @@ int lkf_rtcp_ingest(lkf_engine *e, const lkf_rtcp_raw *in, uint32_t n, const uin
   if (n_nacks) *n_nacks = 0;
   // groups: one per DownTrack's contiguous entries (a DownTrack must not reappear)
   std::vector<uint32_t> g;
-  std::vector<uint8_t> seen(e->dtp.size(), 0);
-  for (uint32_t i = 0; i < n; i++) {
-    const int32_t dt = in[i].dt;
-    if (dt < 0 || dt >= int32_t(e->dtp.size())) return LKF_EINVAL;
-    if (in[i].len > LKF_RTCP_MAX_LEN || uint64_t(in[i].off) + in[i].len > arena_len) return LKF_EINVAL;
-    if (i == 0 || in[i - 1].dt != dt) {
-      if (seen[dt]) return LKF_EORDER;
-      seen[dt] = 1;
-      g.push_back(i);
-    }
-  }
-  const uint32_t ngroups = uint32_t(g.size());
-  g.push_back(n);
-  int rc = flush_topology(e);
-  if (rc) return rc;
-  HIPCHK(hipSetDevice(e->dev), "hipSetDevice");
-  rc = sender_after_queued(e);
-  if (rc) return rc;
-  hipStream_t s = e->sendS;
+  if (n)
+    STEP(check_handles(&in[0].dt, sizeof(*in), n, e->dtp.size(), {Repeat::Groups, &g, true}, [&](uint32_t i) {
+      return in[i].len <= LKF_RTCP_MAX_LEN && uint64_t(in[i].off) + in[i].len <= arena_len;
+    }));
+  const uint32_t ngroups = n ? uint32_t(g.size() - 1) : 0;
+  Frame f(e, Order::BehindSender);
+  STEP(f.open());
+  hipStream_t s = f.s;
   e->riNacks = 0;  // the last call's NACK list ends here
   e->riGroups.clear();
   if (!n) return LKF_OK;
-  // The per-entry buffers grow together, dRiRefOff last: its capacity is what
-  // all of them hold (0 after a failed grow, which the next call retries).
-  if (n > e->dRiRefOff.cap()) {
-    HIPCHK(hipStreamSynchronize(s), "sync sender stream");
-    const uint64_t m = 2 * uint64_t(n);
-    release_all(e->dRiIn, e->dRiGEntry, e->dRiFbG, e->dRiFbCnt, e->dRiRefCnt, e->dRiNackCnt, e->dRiFbOff,
-                e->dRiNackOff, e->dRiRes, e->dRiTot, e->dRiScan, e->dRiRefOff);
-    HIPCHK(e->dRiIn.reserve(m, 4096), "alloc rtcp raw");
-    HIPCHK(e->dRiGEntry.reserve(m + 1, 4097), "alloc rtcp group starts");
-    HIPCHK(e->dRiFbG.reserve(m + 1, 4097), "alloc rtcp fb groups");
-    HIPCHK(e->dRiFbCnt.reserve(m, 4096), "alloc rtcp counts");
-    HIPCHK(e->dRiRefCnt.reserve(m, 4096), "alloc rtcp counts");
-    HIPCHK(e->dRiNackCnt.reserve(m, 4096), "alloc rtcp counts");
-    HIPCHK(e->dRiFbOff.reserve(m, 4096), "alloc rtcp offsets");
-    HIPCHK(e->dRiNackOff.reserve(m, 4096), "alloc rtcp offsets");
-    HIPCHK(e->dRiRes.reserve(m, 4096), "alloc rtcp results");
-    HIPCHK(e->dRiTot.reserve(4, 4), "alloc rtcp totals");
-    const size_t words = scan_state_words(uint32_t(std::min<uint64_t>(std::max<uint64_t>(m, 4096), 0xffffffffu)));
-    HIPCHK(e->dRiScan.alloc(words), "alloc rtcp scan state");
-    HIPCHK(hipMemsetAsync(e->dRiScan, 0, words * sizeof(uint64_t), s), "rtcp scan state reset");
-    HIPCHK(e->dRiRefOff.reserve(m, 4096), "alloc rtcp offsets");
-  }
-  if (arena_len > e->dRiArena.cap()) {  // (on its own: empty after a failed grow, retried then)
-    HIPCHK(hipStreamSynchronize(s), "sync sender stream");
-    HIPCHK(e->dRiArena.reserve(2 * arena_len, 1 << 16), "alloc rtcp arena");
-  }
-  HIPCHK(hipMemcpyAsync(e->dRiIn, in, size_t(n) * sizeof(lkf_rtcp_raw), hipMemcpyHostToDevice, s), "rtcp raw copy");
-  if (arena_len) HIPCHK(hipMemcpyAsync(e->dRiArena, arena, arena_len, hipMemcpyHostToDevice, s), "rtcp arena copy");
-  HIPCHK(hipMemcpyAsync(e->dRiGEntry, g.data(), g.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s),
-         "rtcp groups copy");
+  // The per-entry buffers are one family, sized for twice the entries; the
+  // scan state is zeroed once, on the call's stream, when it is reallocated.
+  const uint64_t m = 2 * uint64_t(n);
+  auto words = [](uint64_t k) {
+    return uint64_t(scan_state_words(uint32_t(std::min<uint64_t>(std::max<uint64_t>(k, 4096), 0xffffffffu))));
+  };
+  STEP(f.grow("alloc rtcp ingress scratch", want(e->dRiIn, n, 4096, m), want(e->dRiGEntry, uint64_t(n) + 1, 4097, m + 1),
+              want(e->dRiFbG, uint64_t(n) + 1, 4097, m + 1), want(e->dRiFbCnt, n, 4096, m),
+              want(e->dRiRefCnt, n, 4096, m), want(e->dRiNackCnt, n, 4096, m), want(e->dRiFbOff, n, 4096, m),
+              want(e->dRiNackOff, n, 4096, m), want(e->dRiRes, n, 4096, m), want(e->dRiTot, 4, 4),
+              want(e->dRiScan, words(n), 0, words(m)), want(e->dRiRefOff, n, 4096, m)));
+  if (f.grew) HIPCHK(hipMemsetAsync(e->dRiScan, 0, e->dRiScan.cap() * sizeof(uint64_t), s), "rtcp scan state reset");
+  STEP(f.grow("alloc rtcp arena", want(e->dRiArena, arena_len, 1 << 16, 2 * arena_len)));  // (a family of its own)
+  STEP(f.up(e->dRiIn, in, size_t(n) * sizeof(lkf_rtcp_raw), "rtcp raw copy"));
+  if (arena_len) STEP(f.up(e->dRiArena, arena, arena_len, "rtcp arena copy"));
+  STEP(f.up(e->dRiGEntry, g.data(), g.size() * sizeof(uint32_t), "rtcp groups copy"));
   RtcpInLaunch a{};
   a.in = e->dRiIn;
   a.n = n;
@@ -3180,9 +3161,8 @@ int lkf_rtcp_ingest(lkf_engine *e, const lkf_rtcp_raw *in, uint32_t n, const uin
                      nullptr, e->dRiTot + 2, nullptr, nullptr),
          "rtcp ref scan");
   uint64_t tot[3] = {};
-  CHKRANGE(e->dRiTot, sizeof(tot), "async d2h");
-  HIPCHK(hipMemcpyAsync(tot, e->dRiTot, sizeof(tot), hipMemcpyDeviceToHost, s), "rtcp totals copy");
-  HIPCHK(hipStreamSynchronize(s), "sync sender stream");
+  STEP(f.down(tot, e->dRiTot, sizeof(tot), "rtcp totals copy"));
+  STEP(f.wait());
   for (uint64_t t : tot)
     if (t > 0xffffffffull) {  // (or a scan that gave up: ~0)
       e->err = "RTCP ingest: a list of one call exceeds 2^32 - 1 records";
@@ -3214,7 +3194,7 @@ int lkf_rtcp_ingest(lkf_engine *e, const lkf_rtcp_raw *in, uint32_t n, const uin
   u.out = e->dRiFbOut;
   HIPCHK(launch_rr_update(s, u), "rr update");
   HIPCHK(launch_rtcp_in_fold(s, a), "rtcp fold");
-  HIPCHK(hipStreamSynchronize(s), "sync sender stream");
+  STEP(f.wait());
   D2H(out, e->dRiRes, size_t(n) * sizeof(lkf_rtcp_in_result), "rtcp results copy");
   *n_fb = uint32_t(tot[0]);
   *n_refs = uint32_t(tot[2]);
@@ -3265,46 +3245,34 @@ int lkf_rtx_lookup_ingested(lkf_engine *e, int64_t now_ns, lkf_rtx *out, uint32_
   if (keep.empty()) return LKF_OK;
   gb.push_back(m);
   const bool inPlace = keep.size() == e->riGroups.size();
-  int rc = flush_topology(e);
-  if (rc) return rc;
-  hipStream_t s = e->decS;  // as lkf_rtx_lookup: behind the queued decides
-  HIPCHK(hipSetDevice(e->dev), "hipSetDevice");
-  if (m > rtx_cap(e)) HIPCHK(hipStreamSynchronize(s), "sync decide stream");  // (rtx_reserve reallocates)
-  rc = rtx_reserve(e, m);
-  if (rc) return rc;
-  HIPCHK(hipEventRecord(e->inEv, e->own), "event");
-  HIPCHK(hipStreamWaitEvent(s, e->inEv, 0), "wait own stream");
+  Frame f(e, Order::BehindDecide);  // as lkf_rtx_lookup: behind the queued decides
+  STEP(f.open());
   HIPCHK(hipEventRecord(e->inEv, e->sendS), "event");  // the ingest's write pass
-  HIPCHK(hipStreamWaitEvent(s, e->inEv, 0), "wait sender stream");
+  HIPCHK(hipStreamWaitEvent(f.s, e->inEv, 0), "wait sender stream");
+  STEP(rtx_grow(f, m));
   if (!inPlace)
     for (size_t k = 0; k < keep.size(); k++)
       HIPCHK(hipMemcpyAsync(e->dNacks + gb[k], e->dRiNacks + keep[k]->begin,
-                            size_t(keep[k]->end - keep[k]->begin) * sizeof(lkf_nack), hipMemcpyDeviceToDevice, s),
+                            size_t(keep[k]->end - keep[k]->begin) * sizeof(lkf_nack), hipMemcpyDeviceToDevice, f.s),
              "nacks pack");
-  HIPCHK(hipMemcpyAsync(e->dNackG, gb.data(), gb.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s), "groups copy");
-  return rtx_lookup_run(e, s, inPlace ? e->dRiNacks.get() : e->dNacks.get(), uint32_t(keep.size()), m, now_ns, out, cap,
+  STEP(f.up(e->dNackG, gb.data(), gb.size() * sizeof(uint32_t), "groups copy"));
+  return rtx_lookup_run(f, inPlace ? e->dRiNacks.get() : e->dNacks.get(), uint32_t(keep.size()), m, now_ns, out, cap,
                         n_out);
 }
 
-static int rtx_emit_common(lkf_engine *e, const lkf_rtx *rtx, uint32_t n, const uint8_t *srcArena,
+static int rtx_emit_common(Frame &f, const lkf_rtx *rtx, uint32_t n, const uint8_t *srcArena,
                            const std::vector<uint16_t> &srcHdr, lkf_out *out, uint8_t *out_arena, uint64_t out_cap,
                            uint32_t *n_out, uint64_t *out_len);
-// The retransmissions run on the sender stream, after every queued stage that
-// touches what they read or update: the decides and sequencer DD bytes
-// (decide stream), the sender statistics (sender stream for long batches,
-// emit stream for short ones — the RTX sendingPacket updates the same
-// RTPStatsSender) and the bucket copies (sender stream).  The host then waits
-// for that point: the scratch buffers below are rewritten from the host.
-static int rtx_order(lkf_engine *e, uint32_t n) {
-  HIPCHK(hipSetDevice(e->dev), "hipSetDevice");
-  if (e->twccDirty) {  // a transport-cc DownTrack added / bound since the last run: its counters first
-    const int rt = rebuild_twcc(e);
-    if (rt) return rt;
-  }
-  const int rc = sender_after_queued(e);
-  if (rc) return rc;
-  HIPCHK(hipStreamSynchronize(e->sendS), "sync sender stream");
-  return rtx_reserve(e, n);
+// The retransmissions run on the sender stream (Order::BehindSender), after
+// every queued stage that touches what they read or update: the decides and
+// sequencer DD bytes (decide stream), the sender statistics (sender stream for
+// long batches, emit stream for short ones — the RTX sendingPacket updates
+// the same RTPStatsSender) and the bucket copies (sender stream).  The host
+// then waits for that point: the scratch buffers are rewritten from the host.
+static int rtx_open(Frame &f, uint32_t n) {
+  STEP(f.open(true, true));
+  STEP(f.wait());
+  return rtx_grow(f, n);
 }
 int lkf_rtx_emit(lkf_engine *e, const lkf_rtx *rtx, uint32_t n, const lkf_raw_pkt *src, const uint8_t *src_arena,
                  uint64_t src_len, lkf_out *out, uint8_t *out_arena, uint64_t out_cap, uint32_t *n_out,
@@ -3313,22 +3281,18 @@ int lkf_rtx_emit(lkf_engine *e, const lkf_rtx *rtx, uint32_t n, const lkf_raw_pk
   *n_out = 0;
   *out_len = 0;
   if (!n) return LKF_OK;
-  for (uint32_t i = 0; i < n; i++) {
-    if (rtx[i].dt < 0 || rtx[i].dt >= int32_t(e->dtp.size())) return LKF_EINVAL;
-    if (src[i].len && (!src_arena || uint64_t(src[i].off) + src[i].len > src_len)) return LKF_EINVAL;
-  }
-  int rc = flush_topology(e);
-  if (rc) return rc;
-  rc = rtx_order(e, n);
-  if (rc) return rc;
-  HIPCHK(e->dRtxIn.reserve(src_len + 64, 1 << 20), "alloc rtx in");
+  STEP(check_handles(&rtx[0].dt, sizeof(*rtx), n, e->dtp.size(), {}, [&](uint32_t i) {
+    return !src[i].len || (src_arena && uint64_t(src[i].off) + src[i].len <= src_len);
+  }));
+  Frame f(e, Order::BehindSender);
+  STEP(rtx_open(f, n));
+  HIPCHK(e->dRtxIn.reserve(src_len + 64, 1 << 20), "alloc rtx in");  // (the stream is idle)
   // uploads ordered on the sender stream ahead of the kernels that read them
   // (a pageable hipMemcpy may return before its DMA lands, and the engine's
   // streams do not order against the null stream)
-  HIPCHK(hipMemcpyAsync(e->dRtx, rtx, n * sizeof(lkf_rtx), hipMemcpyHostToDevice, e->sendS), "rtx copy");
-  HIPCHK(hipMemcpyAsync(e->dRtxSrc, src, n * sizeof(lkf_raw_pkt), hipMemcpyHostToDevice, e->sendS), "src copy");
-  if (src_len)
-    HIPCHK(hipMemcpyAsync(e->dRtxIn, src_arena, src_len, hipMemcpyHostToDevice, e->sendS), "src arena copy");
+  STEP(f.up(e->dRtx, rtx, n * sizeof(lkf_rtx), "rtx copy"));
+  STEP(f.up(e->dRtxSrc, src, n * sizeof(lkf_raw_pkt), "src copy"));
+  if (src_len) STEP(f.up(e->dRtxIn, src_arena, src_len, "src arena copy"));
   std::vector<uint16_t> hdr(n, 0);
   for (uint32_t i = 0; i < n; i++) {
     if (!src[i].len) continue;
@@ -3337,16 +3301,16 @@ int lkf_rtx_emit(lkf_engine *e, const lkf_rtx *rtx, uint32_t n, const lkf_raw_pk
     if ((b[0] & 0x10) && h + 4 <= src[i].len) h += 4 + 4 * ((uint32_t(b[h + 2]) << 8) | b[h + 3]);
     hdr[i] = uint16_t(h);
   }
-  return rtx_emit_common(e, rtx, n, e->dRtxIn, hdr, out, out_arena, out_cap, n_out, out_len);
+  return rtx_emit_common(f, rtx, n, e->dRtxIn, hdr, out, out_arena, out_cap, n_out, out_len);
 }
 
 // The retransmissions from device-side sources (dRtx / dRtxSrc filled; srcArena:
 // the bytes they index): sizes, offsets, wire bytes, then sendingPacket per
 // retransmission (srcHdr[i]: the source header's size).
-static int rtx_emit_common(lkf_engine *e, const lkf_rtx *rtx, uint32_t n, const uint8_t *srcArena,
+static int rtx_emit_common(Frame &f, const lkf_rtx *rtx, uint32_t n, const uint8_t *srcArena,
                            const std::vector<uint16_t> &srcHdr, lkf_out *out, uint8_t *out_arena, uint64_t out_cap,
                            uint32_t *n_out, uint64_t *out_len) {
-  int rc = LKF_OK;
+  lkf_engine *e = f.e;
   const uint8_t *rtxDD = nullptr;
   if (e->nSeqDD) {  // epm.ddBytes of each record (its sequencer slot)
     HIPCHK(e->dRtxDD.reserve(size_t(n) * kSeqDDBytes, 1024 * kSeqDDBytes), "alloc rtx dd");
@@ -3359,9 +3323,8 @@ static int rtx_emit_common(lkf_engine *e, const lkf_rtx *rtx, uint32_t n, const 
                          nullptr, nullptr, rtxDD),
          "rtx size");
   std::vector<uint32_t> len(n);
-  CHKRANGE(e->dRtxLen, n * sizeof(uint32_t), "async d2h");
-  HIPCHK(hipMemcpyAsync(len.data(), e->dRtxLen, n * sizeof(uint32_t), hipMemcpyDeviceToHost, e->sendS), "len copy");
-  HIPCHK(hipStreamSynchronize(e->sendS), "sync");
+  STEP(f.down(len.data(), e->dRtxLen, n * sizeof(uint32_t), "len copy"));
+  STEP(f.wait());
   std::vector<uint64_t> off(n, 0);
   uint64_t tot = 0;
   uint32_t k = 0;
@@ -3375,8 +3338,8 @@ static int rtx_emit_common(lkf_engine *e, const lkf_rtx *rtx, uint32_t n, const 
   *n_out = k;
   *out_len = tot;
   if (tot > out_cap || (k && (!out || !out_arena))) return LKF_ENOSPC;
-  HIPCHK(e->dRtxOut.reserve(tot + 64, 1 << 20), "alloc rtx out");
-  HIPCHK(hipMemcpyAsync(e->dRtxOff, off.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice, e->sendS), "off copy");
+  HIPCHK(e->dRtxOut.reserve(tot + 64, 1 << 20), "alloc rtx out");  // (the stream is idle)
+  STEP(f.up(e->dRtxOff, off.data(), n * sizeof(uint64_t), "off copy"));
   HIPCHK(launch_rtx_emit(e->sendS, true, n, e->dRtx, e->dRtxSrc, srcArena, e->dDTs, e->dTracks, e->dRtxLen,
                          e->dRtxOff, e->dRtxOut, rtxDD),
          "rtx write");
@@ -3384,11 +3347,8 @@ static int rtx_emit_common(lkf_engine *e, const lkf_rtx *rtx, uint32_t n, const 
     HIPCHK(launch_twcc_stamp(e->sendS, e->dDTs, e->dTwccCtrD, e->dTwccCtrT, n, nullptr, nullptr, nullptr, e->dRtx,
                              e->dRtxOff, e->dRtxLen, e->dRtxOut),
            "twcc stamp");
-  if (tot) {
-    CHKRANGE(e->dRtxOut, tot, "async d2h");
-    HIPCHK(hipMemcpyAsync(out_arena, e->dRtxOut, tot, hipMemcpyDeviceToHost, e->sendS), "rtx bytes copy");
-  }
-  HIPCHK(hipStreamSynchronize(e->sendS), "sync");
+  if (tot) STEP(f.down(out_arena, e->dRtxOut, tot, "rtx bytes copy"));
+  STEP(f.wait());
   {  // sendingPacket (downtrack.go:1671-1681): the bucket packet's header as
      // unmarshalled (CSRCs and extensions kept), the forwarded payload
     std::vector<SenderUpd> ul;
@@ -3409,8 +3369,7 @@ static int rtx_emit_common(lkf_engine *e, const lkf_rtx *rtx, uint32_t n, const 
       u.marker = rtx[i].meta.marker ? 1 : 0;
       ul.push_back(u);
     }
-    rc = sender_list(e, ul);
-    if (rc) return rc;
+    STEP(sender_list(e, ul));
   }
   k = 0;
   for (uint32_t i = 0; i < n; i++) {
@@ -3439,12 +3398,9 @@ int lkf_rtx_emit_bucket(lkf_engine *e, const lkf_rtx *rtx, uint32_t n, lkf_out *
   *n_out = 0;
   *out_len = 0;
   if (!n) return LKF_OK;
-  for (uint32_t i = 0; i < n; i++)
-    if (rtx[i].dt < 0 || rtx[i].dt >= int32_t(e->dtp.size())) return LKF_EINVAL;
-  int rc = flush_topology(e);
-  if (rc) return rc;
-  rc = rtx_order(e, n);
-  if (rc) return rc;
+  STEP(check_handles(&rtx[0].dt, sizeof(*rtx), n, e->dtp.size(), {}));
+  Frame f(e, Order::BehindSender);
+  STEP(rtx_open(f, n));
   std::vector<int32_t> sid(n, -1);
   std::vector<uint16_t> sn(n);
   {
@@ -3465,29 +3421,21 @@ int lkf_rtx_emit_bucket(lkf_engine *e, const lkf_rtx *rtx, uint32_t n, lkf_out *
     }
   }
   if (!e->bktSlots) std::fill(sid.begin(), sid.end(), -1);
-  if (n > e->dBktStream.cap() || n > e->dBktSn.cap()) {
-    release_all(e->dBktStream, e->dBktSn);
-    HIPCHK(e->dBktStream.reserve(n, 1024), "alloc bucket reads");
-    HIPCHK(e->dBktSn.reserve(n, 1024), "alloc bucket read sns");
-  }
+  STEP(f.grow("alloc bucket reads", want(e->dBktStream, n, 1024), want(e->dBktSn, n, 1024)));
   // (uploads on the sender stream, ahead of k_bkt_read / k_rtx: see lkf_rtx_emit)
-  HIPCHK(hipMemcpyAsync(e->dRtx, rtx, n * sizeof(lkf_rtx), hipMemcpyHostToDevice, e->sendS), "rtx copy");
-  HIPCHK(hipMemcpyAsync(e->dBktStream, sid.data(), n * sizeof(int32_t), hipMemcpyHostToDevice, e->sendS),
-         "bucket read copy");
-  HIPCHK(hipMemcpyAsync(e->dBktSn, sn.data(), n * sizeof(uint16_t), hipMemcpyHostToDevice, e->sendS),
-         "bucket sn copy");
-  HIPCHK(e->dRtxIn.reserve(uint64_t(n) * kBktSlot + 64, 1 << 20), "alloc rtx in");
+  STEP(f.up(e->dRtx, rtx, n * sizeof(lkf_rtx), "rtx copy"));
+  STEP(f.up(e->dBktStream, sid.data(), n * sizeof(int32_t), "bucket read copy"));
+  STEP(f.up(e->dBktSn, sn.data(), n * sizeof(uint16_t), "bucket sn copy"));
+  HIPCHK(e->dRtxIn.reserve(uint64_t(n) * kBktSlot + 64, 1 << 20), "alloc rtx in");  // (the queued uploads do not touch it)
   HIPCHK(launch_bucket_read(e->sendS, n, e->dBktStream, e->dBktSn, e->dBkt, e->dBktTag, e->dBktRing, e->dRtxIn,
                             e->dRtxSrc),
          "bucket read");
   std::vector<lkf_raw_pkt> src(n);
-  CHKRANGE(e->dRtxSrc, n * sizeof(lkf_raw_pkt), "async d2h");
-  HIPCHK(hipMemcpyAsync(src.data(), e->dRtxSrc, n * sizeof(lkf_raw_pkt), hipMemcpyDeviceToHost, e->sendS),
-         "src back");
-  HIPCHK(hipStreamSynchronize(e->sendS), "sync");
+  STEP(f.down(src.data(), e->dRtxSrc, n * sizeof(lkf_raw_pkt), "src back"));
+  STEP(f.wait());
   std::vector<uint16_t> hdr(n, 0);
   for (uint32_t i = 0; i < n; i++) hdr[i] = uint16_t(src[i].len ? src[i].reserved : 0);
-  return rtx_emit_common(e, rtx, n, e->dRtxIn, hdr, out, out_arena, out_cap, n_out, out_len);
+  return rtx_emit_common(f, rtx, n, e->dRtxIn, hdr, out, out_arena, out_cap, n_out, out_len);
 }
 
 // ---- padding / blank frames (downtrack.go:764-859, :1307-1401) -------------
@@ -3496,30 +3444,21 @@ int lkf_rtx_emit_bucket(lkf_engine *e, const lkf_rtx *rtx, uint32_t n, lkf_out *
 // 12 + 8 + 80), the kernel fills what it sends, the host packs it.
 // sendingPacket -> RTPStatsSender.Update for host-listed packets (padding,
 // blank frames, RTX): grouped by DownTrack in call order, one thread per
-// DownTrack (k_sender_updates).  Runs on e->own after the producing kernel.
+// DownTrack (k_sender_updates).  Runs on the sender stream, after the queued
+// runs' sender statistics (sender or emit stream), which update the same
+// DownTracks' RTPStatsSender, and after the producing kernel (the caller has
+// waited for it).
 static int sender_list(lkf_engine *e, std::vector<SenderUpd> &list) {
   if (list.empty()) return LKF_OK;
   std::stable_sort(list.begin(), list.end(), [](const SenderUpd &a, const SenderUpd &b) { return a.dt < b.dt; });
   std::vector<uint32_t> g;
-  for (uint32_t i = 0; i < list.size(); i++)
-    if (i == 0 || list[i].dt != list[i - 1].dt) g.push_back(i);
-  g.push_back(uint32_t(list.size()));
-  if (list.size() > e->dSSList.cap() || g.size() > e->dSSGroups.cap()) {
-    release_all(e->dSSList, e->dSSGroups);
-    HIPCHK(e->dSSList.reserve(2 * list.size(), 4096), "alloc sender list");
-    HIPCHK(e->dSSGroups.reserve(2 * list.size() + 1, 4097), "alloc sender groups");
-  }
-  // on the sender stream, after the queued runs' sender statistics (sender or
-  // emit stream), which update the same DownTracks' RTPStatsSender
-  hipStream_t st = e->sendS;
-  {
-    const int rc = sender_after_queued(e);
-    if (rc) return rc;
-  }
-  HIPCHK(hipMemcpyAsync(e->dSSList, list.data(), list.size() * sizeof(SenderUpd), hipMemcpyHostToDevice, st),
-         "sender list copy");
-  HIPCHK(hipMemcpyAsync(e->dSSGroups, g.data(), g.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st),
-         "sender groups copy");
+  STEP(check_handles(&list[0].dt, sizeof(SenderUpd), uint32_t(list.size()), e->dtp.size(), {Repeat::Groups, &g, true}));
+  Frame f(e, Order::BehindSender);
+  STEP(f.open(false));
+  STEP(f.grow("alloc sender list", want(e->dSSList, list.size(), 4096, 2 * list.size()),
+              want(e->dSSGroups, g.size(), 4097, 2 * list.size() + 1)));
+  STEP(f.up(e->dSSList, list.data(), list.size() * sizeof(SenderUpd), "sender list copy"));
+  STEP(f.up(e->dSSGroups, g.data(), g.size() * sizeof(uint32_t), "sender groups copy"));
   SenderListLaunch a;
   a.list = e->dSSList;
   a.gBegin = e->dSSGroups;
@@ -3527,9 +3466,8 @@ static int sender_list(lkf_engine *e, std::vector<SenderUpd> &list) {
   a.ss = e->dSS;
   a.ring = e->dSSRing;
   a.gap = e->dSSGap;
-  HIPCHK(launch_sender_updates(st, a), "sender updates");
-  HIPCHK(hipStreamSynchronize(st), "sync");
-  return LKF_OK;
+  HIPCHK(launch_sender_updates(f.s, a), "sender updates");
+  return f.wait();
 }
 
 // a padding / blank packet's header with the pacer's extension block
@@ -3546,39 +3484,27 @@ static int pad_common(lkf_engine *e, int blank, const lkf_pad_req *reqs, uint32_
   *n_out = 0;
   *arena_len = 0;
   if (!n) return LKF_OK;
-  std::vector<uint8_t> seen(e->dtp.size(), 0);
+  STEP(check_handles(&reqs[0].dt, sizeof(*reqs), n, e->dtp.size(), {Repeat::DistinctEinval}));
   std::vector<uint64_t> off(2 * size_t(n));
   uint64_t recs = 0, bytes = 0;
   for (uint32_t i = 0; i < n; i++) {
     const int32_t dt = reqs[i].dt;
-    if (dt < 0 || dt >= int32_t(e->dtp.size()) || seen[dt]) return LKF_EINVAL;
-    seen[dt] = 1;
     const uint64_t np = !e->active[dt] ? 0 : blank ? 2 : (uint64_t(reqs[i].bytes_to_send) + 274) / 275;
     off[i] = recs;
     off[n + i] = bytes;
     recs += np;
     bytes += np * (blank ? 112 : 288);
   }
-  int rc = flush_topology(e);
-  if (rc) return rc;
-  if (e->twccDirty) {  // a transport-cc DownTrack added / bound since the last run: its counters first
-    rc = rebuild_twcc(e);
-    if (rc) return rc;
-  }
   // k_pad reads and writes the DownTracks' Forwarder / sequencer state, which
   // between runs only the decide stream touches: it runs there, behind the
   // queued decides (their emits keep running); its sendingPacket updates go to
   // the sender stream (sender_list)
-  const hipStream_t ds = e->decS;
-  HIPCHK(hipSetDevice(e->dev), "hipSetDevice");
-  if (n > e->dPadReq.cap() || 2 * uint64_t(n) > e->dPadOff.cap() || 2 * uint64_t(n) > e->dPadCnt.cap()) {
-    release_all(e->dPadReq, e->dPadOff, e->dPadCnt);
-    HIPCHK(e->dPadReq.reserve(n, 1024), "alloc pad reqs");
-    HIPCHK(e->dPadOff.reserve(2 * uint64_t(n), 2048), "alloc pad offsets");
-    HIPCHK(e->dPadCnt.reserve(2 * uint64_t(n), 2048), "alloc pad counts");
-  }
-  HIPCHK(e->dPadOut.reserve(recs, 4096), "alloc pad out");
-  HIPCHK(e->dPadArena.reserve(bytes, 1 << 20), "alloc pad arena");
+  Frame f(e, Order::BehindDecide);
+  STEP(f.open(true, true));
+  const hipStream_t ds = f.s;
+  STEP(f.grow("alloc pad requests", want(e->dPadReq, n, 1024), want(e->dPadOff, 2 * uint64_t(n), 2048),
+              want(e->dPadCnt, 2 * uint64_t(n), 2048)));
+  STEP(f.grow("alloc pad out", want(e->dPadOut, recs, 4096), want(e->dPadArena, bytes, 1 << 20)));
   // a removed DownTrack sends nothing: its request is dropped before the kernel
   std::vector<lkf_pad_req> q(reqs, reqs + n);
   std::vector<uint32_t> live;
@@ -3594,12 +3520,9 @@ static int pad_common(lkf_engine *e, int blank, const lkf_pad_req *reqs, uint32_
   const uint32_t m = uint32_t(live.size());
   std::vector<uint32_t> cnt(2 * size_t(m), 0);
   if (m) {
-    HIPCHK(hipEventRecord(e->inEv, e->own), "event");
-    HIPCHK(hipStreamWaitEvent(ds, e->inEv, 0), "wait own stream");
     // the request uploads on the decide stream, ordered ahead of k_pad (see lkf_rtx_emit)
-    HIPCHK(hipMemcpyAsync(e->dPadReq, lq.data(), m * sizeof(lkf_pad_req), hipMemcpyHostToDevice, ds), "pad req copy");
-    HIPCHK(hipMemcpyAsync(e->dPadOff, loff.data(), 2 * size_t(m) * sizeof(uint64_t), hipMemcpyHostToDevice, ds),
-           "pad off copy");
+    STEP(f.up(e->dPadReq, lq.data(), m * sizeof(lkf_pad_req), "pad req copy"));
+    STEP(f.up(e->dPadOff, loff.data(), 2 * size_t(m) * sizeof(uint64_t), "pad off copy"));
     PadArgs a{};
     a.blank = blank;
     a.n = m;
@@ -3626,7 +3549,7 @@ static int pad_common(lkf_engine *e, int blank, const lkf_pad_req *reqs, uint32_
       HIPCHK(launch_twcc_stamp(ds, e->dDTs, e->dTwccCtrD, e->dTwccCtrT, m, e->dPadOut, e->dPadOff, e->dPadCnt, nullptr,
                                nullptr, nullptr, e->dPadArena),
              "twcc stamp");
-    HIPCHK(hipStreamSynchronize(ds), "sync");
+    STEP(f.wait());
     D2H(cnt.data(), e->dPadCnt, 2 * size_t(m) * sizeof(uint32_t), "pad cnt copy");
   }
   if (bytes_sent)
@@ -3663,8 +3586,7 @@ static int pad_common(lkf_engine *e, int blank, const lkf_pad_req *reqs, uint32_
         u.marker = (o.flags & LKF_OUT_MARKER) ? 1 : 0;
         ul.push_back(u);
       }
-    rc = sender_list(e, ul);
-    if (rc) return rc;
+    STEP(sender_list(e, ul));
   }
   for (uint32_t j = 0; j < m; j++)
     for (uint32_t c = 0; c < cnt[j]; c++) tot += (uint64_t(recv[loff[j] + c].out_len) + 15) & ~uint64_t(15);
@@ -3690,10 +3612,7 @@ int32_t lkf_add_stream_tracker_dd(lkf_engine *e, int32_t track) {
   if (!e || track < 0 || track >= int32_t(e->tracks.size()) || !track_has_dd(e->tracks[track])) return LKF_EINVAL;
   if (e->trackDDTrk.size() < e->tracks.size()) e->trackDDTrk.resize(e->tracks.size(), -1);
   if (e->trackDDTrk[track] >= 0) return LKF_EINVAL;
-  int rc = flush_topology(e);
-  if (rc) return rc;
-  rc = drain_streams(e);
-  if (rc) return rc;
+  STEP(quiesce(e));
   if (!e->dTrackDDTrk) {
     HIPCHK(e->dTrackDDTrk.alloc(e->cfg.max_tracks), "alloc track dd trackers");
     HIPCHK(hipMemset(e->dTrackDDTrk, 0xff, size_t(e->cfg.max_tracks) * sizeof(uint32_t)), "track dd trackers reset");
@@ -3721,8 +3640,7 @@ int32_t lkf_add_stream_tracker_dd(lkf_engine *e, int32_t track) {
 int lkf_dd_tracker_ctl(lkf_engine *e, int32_t tracker, int32_t op, int32_t arg) {
   if (!e || tracker < 0 || uint32_t(tracker) >= e->nDDTrk) return LKF_EINVAL;
   if (op != LKF_TRACKER_PAUSE && op != LKF_TRACKER_STOP) return LKF_EINVAL;
-  int rc = drain_streams(e);
-  if (rc) return rc;
+  STEP(quiesce(e, false));
   DDTrkState t;
   D2H(&t, e->dDDTrk + tracker, sizeof(t), "dd tracker read");
   if (op == LKF_TRACKER_STOP) {
@@ -3739,28 +3657,21 @@ int lkf_dd_tracker_ctl(lkf_engine *e, int32_t tracker, int32_t op, int32_t arg) 
       }
     }
   }
-  HIPCHK(hipMemcpy(e->dDDTrk + tracker, &t, sizeof(t), hipMemcpyHostToDevice), "dd tracker write");
-  return upload_done(e);
+  return write_row(e, e->dDDTrk + tracker, t, "dd tracker write");
 }
 
 int lkf_dd_trackers_tick(lkf_engine *e, const int32_t *trackers, uint32_t n, int64_t bitrate_elapsed_ns,
                          lkf_dd_tracker_status *out) {
   if (!e || (n && (!trackers || !out))) return LKF_EINVAL;
-  std::vector<uint8_t> seen(e->nDDTrk, 0);
-  for (uint32_t i = 0; i < n; i++) {
-    if (trackers[i] < 0 || uint32_t(trackers[i]) >= e->nDDTrk || seen[trackers[i]]) return LKF_EINVAL;
-    seen[trackers[i]] = 1;
-  }
   if (!n) return LKF_OK;
-  int rc = drain_streams(e);
-  if (rc) return rc;
-  HIPCHK(e->dDDTrkIds.reserve(n, 1024), "alloc dd tracker ids");
-  HIPCHK(e->dDDTrkOut.reserve(n, 1024), "alloc dd tracker out");
-  HIPCHK(hipMemcpy(e->dDDTrkIds, trackers, n * sizeof(int32_t), hipMemcpyHostToDevice), "dd tracker ids copy");
-  rc = upload_done(e);
-  if (rc) return rc;
-  HIPCHK(launch_dd_tracker_tick(e->own, e->dDDTrk, e->dDDTrkIds, n, bitrate_elapsed_ns, e->dDDTrkOut), "dd tracker tick");
-  HIPCHK(hipStreamSynchronize(e->own), "sync");
+  STEP(check_handles(trackers, sizeof(*trackers), n, e->nDDTrk, {Repeat::DistinctEinval}));
+  Frame f(e, Order::Quiesced);
+  STEP(f.open(false));
+  STEP(f.grow("alloc dd tracker scratch", want(e->dDDTrkIds, n, 1024), want(e->dDDTrkOut, n, 1024)));
+  STEP(f.up(e->dDDTrkIds, trackers, n * sizeof(int32_t), "dd tracker ids copy"));
+  STEP(f.uploaded());
+  HIPCHK(launch_dd_tracker_tick(f.s, e->dDDTrk, e->dDDTrkIds, n, bitrate_elapsed_ns, e->dDDTrkOut), "dd tracker tick");
+  STEP(f.wait());
   D2H(out, e->dDDTrkOut, n * sizeof(lkf_dd_tracker_status), "dd tracker out copy");
   return LKF_OK;
 }
@@ -3769,8 +3680,7 @@ int lkf_dd_trackers_tick(lkf_engine *e, const int32_t *trackers, uint32_t n, int
 int32_t lkf_add_stream_tracker(lkf_engine *e, int32_t track, int32_t layer, uint32_t samples_required,
                                uint32_t cycles_required) {
   if (!e || track < 0 || track >= int32_t(e->tracks.size()) || layer < 0) return LKF_EINVAL;
-  int rc = drain_streams(e);
-  if (rc) return rc;
+  STEP(quiesce(e, false));
   if (e->nTrk + 1 > e->dTrk.cap()) {  // grow, keeping the trackers
     DevBuf<TrackerState> n;
     HIPCHK(n.alloc(std::max<uint32_t>(2 * uint32_t(e->dTrk.cap()), 1024)), "alloc trackers");
@@ -3783,9 +3693,7 @@ int32_t lkf_add_stream_tracker(lkf_engine *e, int32_t track, int32_t layer, uint
   t.layer = layer;
   t.samples = samples_required;
   t.cycles = cycles_required;
-  HIPCHK(hipMemcpy(e->dTrk + e->nTrk, &t, sizeof(t), hipMemcpyHostToDevice), "tracker init");
-  rc = upload_done(e);
-  if (rc) return rc;
+  STEP(write_row(e, e->dTrk + e->nTrk, t, "tracker init"));
   return int32_t(e->nTrk++);
 }
 
@@ -3802,16 +3710,14 @@ int32_t lkf_add_stream_tracker_frame(lkf_engine *e, int32_t track, int32_t layer
   t.clockRate = clock_rate;
   t.minFPS = min_fps;
   tracker_frame_reset_fps(t);
-  HIPCHK(hipMemcpy(e->dTrk + id, &t, sizeof(t), hipMemcpyHostToDevice), "tracker write");
-  const int rc = upload_done(e);
+  const int rc = write_row(e, e->dTrk + id, t, "tracker write");
   return rc ? rc : id;
 }
 
 // Reset / SetPaused / Stop (streamtracker.go:127-185) on the host copy of the state
 int lkf_stream_tracker_ctl(lkf_engine *e, int32_t tracker, int32_t op, int32_t arg) {
   if (!e || tracker < 0 || uint32_t(tracker) >= e->nTrk) return LKF_EINVAL;
-  int rc = drain_streams(e);
-  if (rc) return rc;
+  STEP(quiesce(e, false));
   TrackerState t;
   D2H(&t, e->dTrk + tracker, sizeof(t), "tracker read");
   auto resetLocked = [&]() {
@@ -3856,8 +3762,7 @@ int lkf_stream_tracker_ctl(lkf_engine *e, int32_t tracker, int32_t op, int32_t a
     default:
       return LKF_EINVAL;
   }
-  HIPCHK(hipMemcpy(e->dTrk + tracker, &t, sizeof(t), hipMemcpyHostToDevice), "tracker write");
-  return upload_done(e);
+  return write_row(e, e->dTrk + tracker, t, "tracker write");
 }
 
 int lkf_stream_trackers_tick(lkf_engine *e, const int32_t *trackers, uint32_t n, int check, int64_t bitrate_elapsed_ns,
@@ -3868,20 +3773,14 @@ int lkf_stream_trackers_tick_at(lkf_engine *e, const int32_t *trackers, uint32_t
                                 int64_t bitrate_elapsed_ns, int64_t now_ns, lkf_tracker_status *out) {
   if (!e || (n && (!trackers || !out))) return LKF_EINVAL;
   if (!n) return LKF_OK;
-  std::vector<uint8_t> seen(e->nTrk, 0);
-  for (uint32_t i = 0; i < n; i++) {
-    if (trackers[i] < 0 || uint32_t(trackers[i]) >= e->nTrk || seen[trackers[i]]) return LKF_EINVAL;
-    seen[trackers[i]] = 1;
-  }
-  int rc = drain_streams(e);
-  if (rc) return rc;
-  HIPCHK(e->dTrkIds.reserve(n, 1024), "alloc tracker ids");
-  HIPCHK(e->dTrkOut.reserve(n, 1024), "alloc tracker out");
-  HIPCHK(hipMemcpy(e->dTrkIds, trackers, n * sizeof(int32_t), hipMemcpyHostToDevice), "tracker ids copy");
-  rc = upload_done(e);
-  if (rc) return rc;
-  HIPCHK(launch_tracker_tick(e->own, e->dTrk, e->dTrkIds, n, check, bitrate_elapsed_ns, now_ns, e->dTrkOut), "tracker tick");
-  HIPCHK(hipStreamSynchronize(e->own), "sync");
+  STEP(check_handles(trackers, sizeof(*trackers), n, e->nTrk, {Repeat::DistinctEinval}));
+  Frame f(e, Order::Quiesced);
+  STEP(f.open(false));
+  STEP(f.grow("alloc tracker scratch", want(e->dTrkIds, n, 1024), want(e->dTrkOut, n, 1024)));
+  STEP(f.up(e->dTrkIds, trackers, n * sizeof(int32_t), "tracker ids copy"));
+  STEP(f.uploaded());
+  HIPCHK(launch_tracker_tick(f.s, e->dTrk, e->dTrkIds, n, check, bitrate_elapsed_ns, now_ns, e->dTrkOut), "tracker tick");
+  STEP(f.wait());
   D2H(out, e->dTrkOut, n * sizeof(lkf_tracker_status), "tracker out copy");
   return LKF_OK;
 }
@@ -3924,10 +3823,8 @@ static int red_common(lkf_engine *e, bool decode, const lkf_pkt *pkts, uint32_t 
       bytes += decode ? 3 * ((hdr + pl + 15) & ~15ull) : ((hdr + std::max<uint64_t>(1500, pl + 1) + 15) & ~15ull);
     }
   }
-  int rc = flush_topology(e);
-  if (rc) return rc;
-  rc = drain_streams(e);
-  if (rc) return rc;
+  Frame f(e, Order::Quiesced);
+  STEP(f.open());
   if (!gb.empty()) {
     auto &r = e->red;
     if (decode && !e->dRedDec) {
@@ -3938,26 +3835,20 @@ static int red_common(lkf_engine *e, bool decode, const lkf_pkt *pkts, uint32_t 
       HIPCHK(e->dRedEnc.alloc(e->cfg.max_tracks), "alloc red enc");
       HIPCHK(hipMemset(e->dRedEnc, 0, size_t(e->cfg.max_tracks) * sizeof(RedEncState)), "red enc reset");
     }
-    HIPCHK(r.in.reserve(n, 1024), "alloc red in");
-    HIPCHK(r.inArena.reserve(arena_len + 64, 1024), "alloc red in arena");
-    HIPCHK(r.out.reserve(recs, 1024), "alloc red out");
-    HIPCHK(r.outArena.reserve(bytes, 1024), "alloc red out arena");
-    HIPCHK(r.g.reserve(2 * gb.size(), 1024), "alloc red groups");
-    HIPCHK(r.cnt.reserve(n, 1024), "alloc red counts");
-    HIPCHK(r.map.reserve(nt, 1024), "alloc red map");
-    HIPCHK(r.off.reserve(2 * uint64_t(n) + 1, 1024), "alloc red offsets");
+    STEP(f.grow("alloc red scratch", want(r.in, n, 1024), want(r.inArena, arena_len + 64, 1024),
+                want(r.out, recs, 1024), want(r.outArena, bytes, 1024), want(r.g, 2 * gb.size(), 1024),
+                want(r.cnt, n, 1024), want(r.map, nt, 1024), want(r.off, 2 * uint64_t(n) + 1, 1024)));
     std::vector<int32_t> mp(nt, -1);
     for (uint32_t t = 0; t < map_len; t++) mp[t] = map[t];
     std::vector<uint32_t> g(gb);
     g.insert(g.end(), ge.begin(), ge.end());
-    HIPCHK(hipMemcpy(r.in, pkts, n * sizeof(lkf_pkt), hipMemcpyHostToDevice), "red in copy");
-    HIPCHK(hipMemcpy(r.inArena, arena, arena_len, hipMemcpyHostToDevice), "red arena copy");
-    HIPCHK(hipMemcpy(r.g, g.data(), g.size() * sizeof(uint32_t), hipMemcpyHostToDevice), "red groups copy");
-    HIPCHK(hipMemcpy(r.map, mp.data(), nt * sizeof(int32_t), hipMemcpyHostToDevice), "red map copy");
-    HIPCHK(hipMemcpy(r.off, off.data(), 2 * size_t(n) * sizeof(uint64_t), hipMemcpyHostToDevice), "red off copy");
+    STEP(f.up(r.in, pkts, n * sizeof(lkf_pkt), "red in copy"));
+    STEP(f.up(r.inArena, arena, arena_len, "red arena copy"));
+    STEP(f.up(r.g, g.data(), g.size() * sizeof(uint32_t), "red groups copy"));
+    STEP(f.up(r.map, mp.data(), nt * sizeof(int32_t), "red map copy"));
+    STEP(f.up(r.off, off.data(), 2 * size_t(n) * sizeof(uint64_t), "red off copy"));
     HIPCHK(hipMemset(r.cnt, 0, n * sizeof(uint32_t)), "red counts reset");
-    rc = upload_done(e);
-    if (rc) return rc;
+    STEP(f.uploaded());
     RedLaunch a;
     a.in = r.in;
     a.inArena = r.inArena;
@@ -3972,8 +3863,8 @@ static int red_common(lkf_engine *e, bool decode, const lkf_pkt *pkts, uint32_t 
     a.out = r.out;
     a.outArena = r.outArena;
     a.cnt = r.cnt;
-    HIPCHK(launch_red(e->own, decode, a), "red");
-    HIPCHK(hipStreamSynchronize(e->own), "sync");
+    HIPCHK(launch_red(f.s, decode, a), "red");
+    STEP(f.wait());
   }
   std::vector<uint32_t> cnt(n, 0);
   std::vector<lkf_pkt> rec(recs ? recs : 1);
@@ -4027,52 +3918,37 @@ int lkf_red_decode(lkf_engine *e, const lkf_pkt *pkts, uint32_t n, const uint8_t
 // capacity is what all of them hold; 0 after a failed grow); likewise the
 // provisional pass's request and result buffers, dProvOut (bytes) last.
 static uint64_t alloc_cap(const lkf_engine *e) { return e->dAllocCapacity.cap(); }
-static uint64_t prov_cap(const lkf_engine *e) { return e->dProvOut.cap() / sizeof(lkf_allocation); }
+static int alloc_grow(Frame &f, uint32_t n) {
+  lkf_engine *e = f.e;
+  return f.grow("alloc allocation scratch", want(e->dAllocReq, n, 1024), want(e->dAllocOut, n, 1024),
+                want(e->dAllocCapacity, n, 1024));
+}
 static int alloc_common(lkf_engine *e, int mode, const lkf_alloc_req *reqs, const int64_t *capacity, uint32_t n,
                         void *out, size_t outSize) {
   if (!e || (n && (!reqs || !out || (mode == ALLOC_NEXT_HIGHER && !capacity)))) return LKF_EINVAL;
   if (!n) return LKF_OK;
-  std::vector<uint8_t> seen(e->dtp.size(), 0);
-  for (uint32_t i = 0; i < n; i++) {
-    const int32_t dt = reqs[i].dt;
-    if (dt < 0 || dt >= int32_t(e->dtp.size()) || seen[dt]) return LKF_EINVAL;
-    if (!e->active[dt]) {  // a removed DownTrack has no allocation (its state stays as it was)
-      e->err = "allocation request for a removed DownTrack";
-      return LKF_EINVAL;
-    }
-    seen[dt] = 1;
+  HandleFault why;  // a removed DownTrack has no allocation (its state stays as it was)
+  const HandlePolicy p{Repeat::DistinctEinval, nullptr, false, e->active.data(), Inactive::Refuse, &why};
+  if (const int rc = check_handles(&reqs[0].dt, sizeof(*reqs), n, e->dtp.size(), p)) {
+    if (why == HandleFault::Inactive) e->err = "allocation request for a removed DownTrack";
+    return rc;
   }
-  int rc = flush_topology(e);
-  if (rc) return rc;
   // The allocation reads and writes the DownTracks' hot state and last
   // allocation, which between runs only the decide stream touches: it is
-  // ordered on that stream after the queued runs' decides, and the host waits
-  // for it alone, not for their emits, sender statistics or protect stages
-  // (those keep overlapping the call).
-  hipStream_t s = e->decS;
-  HIPCHK(hipSetDevice(e->dev), "hipSetDevice");
-  if (n > alloc_cap(e)) {
-    HIPCHK(hipStreamSynchronize(s), "sync before alloc buffers realloc");
-    release_all(e->dAllocReq, e->dAllocOut, e->dAllocCapacity);
-    HIPCHK(e->dAllocReq.reserve(n, 1024), "alloc alloc reqs");
-    HIPCHK(e->dAllocOut.reserve(n, 1024), "alloc alloc out");
-    HIPCHK(e->dAllocCapacity.reserve(n, 1024), "alloc alloc capacity");
-  }
+  // ordered on that stream after the queued runs' decides (Order::BehindDecide),
+  // and the host waits for it alone, not for their emits, sender statistics or
+  // protect stages (those keep overlapping the call).
+  Frame f(e, Order::BehindDecide);
+  STEP(f.open());
+  STEP(alloc_grow(f, n));
   static_assert(sizeof(lkf_video_transition) <= sizeof(lkf_allocation), "transition fits the out buffer");
-  // (the engine's own stream: anything an earlier control call left there)
-  HIPCHK(hipEventRecord(e->inEv, e->own), "event");
-  HIPCHK(hipStreamWaitEvent(s, e->inEv, 0), "wait own stream");
-  HIPCHK(hipMemcpyAsync(e->dAllocReq, reqs, n * sizeof(lkf_alloc_req), hipMemcpyHostToDevice, s), "alloc req copy");
-  if (mode == ALLOC_NEXT_HIGHER)
-    HIPCHK(hipMemcpyAsync(e->dAllocCapacity, capacity, n * sizeof(int64_t), hipMemcpyHostToDevice, s),
-           "capacity copy");
-  HIPCHK(launch_allocate(s, mode, e->dAllocReq, e->dAllocCapacity, n, e->dHot, e->dDTs, e->dTracks, e->dLastAlloc,
+  STEP(f.up(e->dAllocReq, reqs, n * sizeof(lkf_alloc_req), "alloc req copy"));
+  if (mode == ALLOC_NEXT_HIGHER) STEP(f.up(e->dAllocCapacity, capacity, n * sizeof(int64_t), "capacity copy"));
+  HIPCHK(launch_allocate(f.s, mode, e->dAllocReq, e->dAllocCapacity, n, e->dHot, e->dDTs, e->dTracks, e->dLastAlloc,
                          e->dAllocOut),
          "allocate");
-  CHKRANGE(e->dAllocOut, n * outSize, "async d2h");
-  HIPCHK(hipMemcpyAsync(out, e->dAllocOut, n * outSize, hipMemcpyDeviceToHost, s), "alloc out copy");
-  HIPCHK(hipStreamSynchronize(s), "sync");
-  return LKF_OK;
+  STEP(f.down(out, e->dAllocOut, n * outSize, "alloc out copy"));
+  return f.wait();
 }
 int lkf_allocate_optimal(lkf_engine *e, const lkf_alloc_req *reqs, uint32_t n, lkf_allocation *out) {
   return alloc_common(e, ALLOC_OPTIMAL, reqs, nullptr, n, out, sizeof(lkf_allocation));
@@ -4091,54 +3967,43 @@ int lkf_pause(lkf_engine *e, const lkf_alloc_req *reqs, uint32_t n, lkf_allocati
 // ---- the cooperative allocation pass (Provisional*, allocateAllTracks) ------
 // distinct, active, video DownTracks (the reference's selector is nil for audio)
 static int prov_check(lkf_engine *e, const int32_t *dts, uint32_t n, size_t stride) {
-  std::vector<uint8_t> seen(e->dtp.size(), 0);
-  for (uint32_t i = 0; i < n; i++) {
-    const int32_t dt = *reinterpret_cast<const int32_t *>(reinterpret_cast<const uint8_t *>(dts) + i * stride);
-    if (dt < 0 || dt >= int32_t(e->dtp.size()) || seen[dt] || !e->active[dt] ||
-        e->tracks[e->dtp[dt].track].kind != LKF_KIND_VIDEO) {
-      e->err = "provisional allocation: DownTracks must be distinct, active and video";
-      return LKF_EINVAL;
-    }
-    seen[dt] = 1;
-  }
-  return LKF_OK;
+  const HandlePolicy p{Repeat::DistinctEinval, nullptr, false, e->active.data()};
+  const int rc = check_handles(dts, stride, n, e->dtp.size(), p, [&](uint32_t i) {
+    int32_t dt;
+    std::memcpy(&dt, reinterpret_cast<const uint8_t *>(dts) + i * stride, sizeof(dt));
+    return e->tracks[e->dtp[dt].track].kind == LKF_KIND_VIDEO;
+  });
+  if (rc) e->err = "provisional allocation: DownTracks must be distinct, active and video";
+  return rc;
 }
-static int prov_reserve(lkf_engine *e, uint32_t n, uint32_t ngroups) {
+// The provisional pass's request and result buffers and the allocation calls'
+// three (at least as large, and never shrunk) are one family here.
+static int prov_grow(Frame &f, uint32_t n, uint32_t ngroups) {
+  lkf_engine *e = f.e;
   const lkf_cfg &c = e->cfg;
   if (!e->dProv) {
     HIPCHK(e->dProv.alloc(c.max_downtracks), "alloc provisional");
     HIPCHK(hipMemset(e->dProv, 0, size_t(c.max_downtracks) * sizeof(ProvState)), "provisional reset");
   }
-  if (n > prov_cap(e) || n > alloc_cap(e)) {  // (the allocation calls' buffers: at least as large)
-    const uint64_t pc = std::max<uint32_t>(n, 1024), ac = std::max<uint64_t>(alloc_cap(e), pc);
-    release_all(e->dProvReq, e->dProvOut, e->dAllocReq, e->dAllocOut, e->dAllocCapacity);
-    HIPCHK(e->dProvReq.alloc(pc), "alloc prov reqs");
-    HIPCHK(e->dProvOut.alloc(pc * sizeof(lkf_allocation)), "alloc prov out");
-    HIPCHK(e->dAllocReq.alloc(ac), "alloc alloc reqs");
-    HIPCHK(e->dAllocOut.alloc(ac), "alloc alloc out");
-    HIPCHK(e->dAllocCapacity.alloc(ac), "alloc alloc capacity");
-  }
-  HIPCHK(e->dProvGroups.reserve(ngroups, 256), "alloc prov groups");
-  return LKF_OK;
+  const uint64_t ac = std::max<uint64_t>(alloc_cap(e), n);
+  STEP(f.grow("alloc provisional scratch", want(e->dProvReq, n, 1024),
+              want(e->dProvOut, n * sizeof(lkf_allocation), 1024 * sizeof(lkf_allocation)),
+              want(e->dAllocReq, n, 1024, ac), want(e->dAllocOut, n, 1024, ac), want(e->dAllocCapacity, n, 1024, ac)));
+  return f.grow("alloc prov groups", want(e->dProvGroups, ngroups, 256));
 }
 static int prov_common(lkf_engine *e, int mode, const lkf_prov_req *reqs, const lkf_alloc_req *alloc, uint32_t n,
                        void *out, size_t outSize) {
   if (!e || (n && !reqs && !alloc) || (n && outSize && !out)) return LKF_EINVAL;
   if (!n) return LKF_OK;
-  int rc = alloc ? prov_check(e, &alloc[0].dt, n, sizeof(lkf_alloc_req)) : prov_check(e, &reqs[0].dt, n, sizeof(lkf_prov_req));
-  if (rc) return rc;
-  rc = flush_topology(e);
-  if (rc) return rc;
-  rc = drain_streams(e);
-  if (rc) return rc;
-  rc = prov_reserve(e, n, 0);
-  if (rc) return rc;
+  STEP(alloc ? prov_check(e, &alloc[0].dt, n, sizeof(lkf_alloc_req)) : prov_check(e, &reqs[0].dt, n, sizeof(lkf_prov_req)));
+  Frame f(e, Order::Quiesced);
+  STEP(f.open());
+  STEP(prov_grow(f, n, 0));
   if (alloc)
-    HIPCHK(hipMemcpy(e->dAllocReq, alloc, n * sizeof(lkf_alloc_req), hipMemcpyHostToDevice), "prov req copy");
+    STEP(f.up(e->dAllocReq, alloc, n * sizeof(lkf_alloc_req), "prov req copy"));
   else
-    HIPCHK(hipMemcpy(e->dProvReq, reqs, n * sizeof(lkf_prov_req), hipMemcpyHostToDevice), "prov req copy");
-  rc = upload_done(e);
-  if (rc) return rc;
+    STEP(f.up(e->dProvReq, reqs, n * sizeof(lkf_prov_req), "prov req copy"));
+  STEP(f.uploaded());
   ProvLaunch a;
   a.mode = mode;
   a.n = n;
@@ -4150,8 +4015,8 @@ static int prov_common(lkf_engine *e, int mode, const lkf_prov_req *reqs, const 
   a.last = e->dLastAlloc;
   a.prov = e->dProv;
   a.out = e->dProvOut;
-  HIPCHK(launch_prov(e->own, a), "provisional");
-  HIPCHK(hipStreamSynchronize(e->own), "sync");
+  HIPCHK(launch_prov(f.s, a), "provisional");
+  STEP(f.wait());
   if (outSize) D2H(out, e->dProvOut, n * outSize, "prov out copy");
   return LKF_OK;
 }
@@ -4192,23 +4057,18 @@ int lkf_allocate_all(lkf_engine *e, const lkf_alloc_group *groups, uint32_t ngro
       if (cover[groups[g].first + k]++) return LKF_EINVAL;
   }
   if (!ngroups || !n) return LKF_OK;
-  int rc = prov_check(e, &reqs[0].dt, n, sizeof(lkf_alloc_req));
-  if (rc) return rc;
-  rc = flush_topology(e);
-  if (rc) return rc;
-  rc = drain_streams(e);
-  if (rc) return rc;
-  rc = prov_reserve(e, n, ngroups);
-  if (rc) return rc;
-  HIPCHK(hipMemcpy(e->dAllocReq, reqs, n * sizeof(lkf_alloc_req), hipMemcpyHostToDevice), "alloc req copy");
-  HIPCHK(hipMemcpy(e->dProvGroups, groups, ngroups * sizeof(lkf_alloc_group), hipMemcpyHostToDevice), "groups copy");
+  STEP(prov_check(e, &reqs[0].dt, n, sizeof(lkf_alloc_req)));
+  Frame f(e, Order::Quiesced);
+  STEP(f.open());
+  STEP(prov_grow(f, n, ngroups));
+  STEP(f.up(e->dAllocReq, reqs, n * sizeof(lkf_alloc_req), "alloc req copy"));
+  STEP(f.up(e->dProvGroups, groups, ngroups * sizeof(lkf_alloc_group), "groups copy"));
   HIPCHK(hipMemset(e->dProvOut, 0, n * sizeof(lkf_allocation)), "alloc out reset");
-  rc = upload_done(e);
-  if (rc) return rc;
-  HIPCHK(launch_allocate_all(e->own, e->dProvGroups, ngroups, e->dAllocReq, e->dHot, e->dDTs, e->dTracks,
+  STEP(f.uploaded());
+  HIPCHK(launch_allocate_all(f.s, e->dProvGroups, ngroups, e->dAllocReq, e->dHot, e->dDTs, e->dTracks,
                              e->dLastAlloc, e->dProv, reinterpret_cast<lkf_allocation *>(e->dProvOut.get())),
          "allocate all");
-  HIPCHK(hipStreamSynchronize(e->own), "sync");
+  STEP(f.wait());
   D2H(out, e->dProvOut, n * sizeof(lkf_allocation), "alloc out copy");
   return LKF_OK;
 }
@@ -4591,8 +4451,7 @@ int lkf_stream_srtp_get(lkf_engine *e, int32_t stream, lkf_stream_srtp *out) {
   std::memset(out, 0, sizeof(*out));
   out->transport = -1;
   if (!e->dSrtpRx) return LKF_OK;  // no stream was ever bound
-  int rc = drain_streams(e);
-  if (rc) return rc;
+  STEP(quiesce(e, false));
   SrtpRx s;
   D2H(&s, e->dSrtpRx + stream, sizeof(s), "srtp rx state copy");
   out->s_l = s.sl;
@@ -4689,10 +4548,7 @@ int lkf_ingested_dd(lkf_engine *e, lkf_pkt_dd *out, uint32_t cap, uint32_t *n_ou
 
 int lkf_stream_stats_get(lkf_engine *e, int32_t sid, lkf_stream_stats *o) {
   if (!e || !o || sid < 0 || sid >= int32_t(e->streams.size())) return LKF_EINVAL;
-  int rc = flush_topology(e);
-  if (rc) return rc;
-  rc = drain_streams(e);
-  if (rc) return rc;
+  STEP(quiesce(e));
   StreamHot h;
   D2H(&h, e->dStreamHot + sid, sizeof(h), "stream state copy");
   std::memset(o, 0, sizeof(*o));
@@ -4758,12 +4614,12 @@ int lkf_stream_set_rtt(lkf_engine *e, int32_t sid, uint32_t rtt_ms) {
   if (rtt_ms == 0) return LKF_OK;  // Buffer.SetRTT ignores 0
   int rc = flush_topology(e);
   if (rc) return rc;
+  // (not quiesce(): a stream without a NackQueue returns between the flush and the drain)
   if (!e->streams[sid].nack || !e->dNack) return LKF_OK;  // no NackQueue (the rtpStats RTT is out of scope)
   rc = drain_streams(e);  // a queued ingest reads the RTT
   if (rc) return rc;
   e->streams[sid].rtt_ms = rtt_ms;
-  HIPCHK(hipMemcpy(&e->dNack[sid].rtt, &rtt_ms, sizeof(rtt_ms), hipMemcpyHostToDevice), "nack rtt");
-  return upload_done(e);
+  return write_row(e, &e->dNack[sid].rtt, rtt_ms, "nack rtt");
 }
 
 // Room -> participant -> microphone-stream tables for k_speakers.
@@ -4855,14 +4711,8 @@ int lkf_speakers_enqueue(lkf_engine *e, int64_t now_ns) {
 
 int lkf_speakers(lkf_engine *e, int64_t now_ns, lkf_speaker *out, uint32_t cap, uint32_t *n_out) {
   if (!e || !n_out) return LKF_EINVAL;
-  int rc = flush_topology(e);
-  if (rc) return rc;
-  rc = drain_streams(e);
-  if (rc) return rc;
-  if (e->spkDirty) {
-    rc = rebuild_speakers(e);
-    if (rc) return rc;
-  }
+  STEP(quiesce(e));
+  if (e->spkDirty) STEP(rebuild_speakers(e));
   *n_out = 0;
   if (e->nRooms == 0) return LKF_OK;
   SpeakersLaunch a;
@@ -5101,8 +4951,7 @@ int lkf_debug_check(lkf_engine *e, uint64_t out[4], int reset) {
 // checks them after graph re-captures forced under queued runs.
 int lkf_debug_dd_cursors(lkf_engine *e, uint64_t out[7]) {
   if (!e || !out || !e->ddAlloc) return LKF_EINVAL;
-  int rc = drain_streams(e);
-  if (rc) return rc;
+  STEP(quiesce(e, false));
   for (int c = 0; c < lkf_engine::kCtx; c++) {
     uint64_t u[2] = {0, 0};
     D2H(u, e->ctx[c].dDDUsed, sizeof(u), "dd cursor copy");
@@ -5119,8 +4968,7 @@ int lkf_debug_dd_cursors(lkf_engine *e, uint64_t out[7]) {
 // spatial | temporal << 8 (+128 each)).
 int lkf_debug_dd_state(lkf_engine *e, int32_t dt, uint64_t out[16]) {
   if (!e || !out || dt < 0 || size_t(dt) >= e->dtp.size() || !e->dDDState) return LKF_EINVAL;
-  int rc = drain_streams(e);
-  if (rc) return rc;
+  STEP(quiesce(e, false));
   DDState d;
   DTHot h;
   D2H(&d, e->dDDState + dt, sizeof(d), "dd state");
@@ -5151,10 +4999,7 @@ int lkf_downtrack_summaries(lkf_engine *e, lkf_dt_summary *out, uint32_t cap, ui
   if (cap < nd) return LKF_ENOSPC;
   if (!nd) return LKF_OK;
   if (!out) return LKF_EINVAL;
-  int rc = flush_topology(e);
-  if (rc) return rc;
-  rc = drain_streams(e);
-  if (rc) return rc;
+  STEP(quiesce(e));
   std::vector<DTCum> c(nd);
   D2H(c.data(), e->dDTCum, nd * sizeof(DTCum), "dt totals copy");
   for (uint32_t d = 0; d < nd; d++) {

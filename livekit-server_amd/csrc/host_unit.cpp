@@ -1,6 +1,7 @@
 // host_unit.cpp — CPU unit tests of the engine's pure host pieces: DevBuf
-// (dev_buf.h) over a malloc-backed fake of its two allocation functions, and
-// the control-op CSR (ctl_csr.h) against std::stable_sort.  Built with the
+// (dev_buf.h) over a malloc-backed fake of its two allocation functions, the
+// control-op CSR (ctl_csr.h) against std::stable_sort, and the control calls'
+// handle lists (handles.h) against a naive restatement.  Built with the
 // host compiler alone (make host_unit; address + undefined sanitizers).
 //   host_unit --list     the case names
 //   host_unit <name>     one case ("PASS <name>" / exit 1)
@@ -18,6 +19,7 @@
 
 #include "ctl_csr.h"
 #include "dev_buf.h"
+#include "handles.h"
 
 using namespace lkf;
 
@@ -129,6 +131,29 @@ static void devbuf_move() {
   CHECK(g_frees == f1 + 2 && !x.get() && !y.get());
 }
 
+// two calls with opposite shapes share a family (as feedback and sender reports do)
+static void devbuf_family_settles() {
+  DevBuf<uint8_t> in, out;
+  DevBuf<uint32_t> g;
+  auto call = [&](uint64_t nin, uint64_t ng, uint64_t nout) {
+    if (!family_short(want(in, nin, 64), want(g, ng, 8), want(out, nout, 64))) return 0;
+    CHECK(regrow_family(want(in, nin, 64, 2 * nin), want(g, ng, 8, 2 * ng), want(out, nout, 64, 2 * nout)) == 0);
+    return 1;
+  };
+  CHECK(call(10, 0, 10) == 1 && in.cap() == 64 && g.cap() == 8 && out.cap() == 64);  // the floors
+  CHECK(call(64, 8, 64) == 0);
+  CHECK(call(300, 3, 20) == 1 && in.cap() == 600 && out.cap() == 64);   // input-heavy
+  CHECK(call(20, 0, 100) == 1 && in.cap() == 600 && out.cap() == 200);  // output-heavy: the input side keeps its size
+  const int a0 = g_allocs;
+  for (int tick = 0; tick < 5; tick++) CHECK(call(300, 3, 20) == 0 && call(20, 0, 100) == 0);
+  CHECK(g_allocs == a0 && in.cap() == 600 && g.cap() == 8 && out.cap() == 200);
+  // a failed regrow: the buffers from the failure on are empty, the next call retries
+  g_fail_next = true;
+  CHECK(regrow_family(want(in, 700, 64), want(g, 1, 8), want(out, 1, 64)) != 0);
+  CHECK(in.get() == nullptr && in.cap() == 0 && g.cap() == 0 && out.cap() == 0);
+  CHECK(call(20, 0, 100) == 1 && in.cap() == 64 && out.cap() == 200);
+}
+
 // ---- control-op CSR ---------------------------------------------------------
 struct Ref {
   uint32_t lane, at;
@@ -216,15 +241,224 @@ static void csr_nl_200() { csr_random(200, 300); }      // one radix pass
 static void csr_nl_300() { csr_random(300, 400); }      // two
 static void csr_nl_70000() { csr_random(70000, 500); }  // three
 
+// ---- handle lists (handles.h) --------------------------------------------------
+using H = std::vector<int32_t>;
+using G = std::vector<uint32_t>;
+static const Repeat kPolicies[] = {Repeat::DistinctEinval, Repeat::DistinctEorder, Repeat::Groups};
+
+static int hcheck(const H &h, size_t limit, Repeat rep, G *groups = nullptr, const uint8_t *active = nullptr,
+                  Inactive ina = Inactive::Refuse, HandleFault *why = nullptr) {
+  HandlePolicy p;
+  p.repeat = rep;
+  p.groups = groups;
+  p.end = true;
+  p.active = active;
+  p.inactive = ina;
+  p.why = why;
+  return check_handles(h.data(), sizeof(int32_t), uint32_t(h.size()), limit, p);
+}
+
+static void handles_empty() {
+  for (Repeat rep : kPolicies) {
+    G g = {7, 7};
+    CHECK(hcheck({}, 4, rep, &g) == LKF_OK && g == G({0}));
+    CHECK(hcheck({}, 0, rep) == LKF_OK);
+  }
+  CHECK(hcheck({}, 4, Repeat::Any) == LKF_OK);
+}
+
+static void handles_range() {
+  for (Repeat rep : {Repeat::Any, Repeat::DistinctEinval, Repeat::DistinctEorder, Repeat::Groups}) {
+    HandleFault why = HandleFault::None;
+    CHECK(hcheck({0, -1}, 4, rep, nullptr, nullptr, Inactive::Refuse, &why) == LKF_EINVAL && why == HandleFault::Range);
+    CHECK(hcheck({4}, 4, rep) == LKF_EINVAL);
+    CHECK(hcheck({3, 0}, 4, rep) == LKF_OK);
+    CHECK(hcheck({0}, 0, rep) == LKF_EINVAL);
+    CHECK(hcheck({INT32_MIN}, 4, rep) == LKF_EINVAL && hcheck({INT32_MAX}, 4, rep) == LKF_EINVAL);
+  }
+}
+
+static void handles_adjacent_repeat() {
+  G g;
+  HandleFault why = HandleFault::None;
+  CHECK(hcheck({1, 2, 2, 3}, 4, Repeat::DistinctEinval, &g, nullptr, Inactive::Refuse, &why) == LKF_EINVAL &&
+        why == HandleFault::Repeat);
+  CHECK(hcheck({1, 2, 2, 3}, 4, Repeat::DistinctEorder, &g, nullptr, Inactive::Refuse, &why) == LKF_EORDER &&
+        why == HandleFault::Repeat);
+  CHECK(hcheck({1, 2, 2, 3}, 4, Repeat::Groups, &g, nullptr, Inactive::Refuse, &why) == LKF_OK &&
+        why == HandleFault::None && g == G({0, 1, 3, 4}));
+  CHECK(hcheck({1, 2, 2, 3}, 4, Repeat::Any, &g) == LKF_OK && g == G({0, 1, 3, 4}));
+  CHECK(hcheck({0, 1, 2, 3}, 4, Repeat::DistinctEinval, &g) == LKF_OK && g == G({0, 1, 2, 3, 4}));
+}
+
+static void handles_split_repeat() {
+  CHECK(hcheck({1, 2, 1}, 4, Repeat::DistinctEinval) == LKF_EINVAL);
+  CHECK(hcheck({1, 2, 1}, 4, Repeat::DistinctEorder) == LKF_EORDER);
+  CHECK(hcheck({1, 2, 1}, 4, Repeat::Groups) == LKF_EORDER);
+  CHECK(hcheck({1, 1, 2, 2, 1}, 4, Repeat::Groups) == LKF_EORDER);
+  CHECK(hcheck({1, 2, 1}, 4, Repeat::Any) == LKF_OK);
+}
+
+static void handles_first_offender_wins() {
+  for (Repeat rep : {Repeat::DistinctEorder, Repeat::Groups}) {
+    CHECK(hcheck({9, 1, 2, 1}, 4, rep) == LKF_EINVAL);  // [bad range, repeat]
+    CHECK(hcheck({1, 2, 1, 9}, 4, rep) == LKF_EORDER);  // [repeat, bad range]
+    CHECK(hcheck({1, 2, -1, 1}, 4, rep) == LKF_EINVAL);
+  }
+  // one entry: its range before the caller's test, the caller's test before "reappears"
+  const H h = {1, 2, 1, 9};
+  HandlePolicy p;
+  p.repeat = Repeat::Groups;
+  HandleFault why = HandleFault::None;
+  p.why = &why;
+  uint32_t asked = 0;
+  CHECK(check_handles(h.data(), 4, 4, 4, p, [&](uint32_t i) { return asked = i, i != 2; }) == LKF_EINVAL);
+  CHECK(why == HandleFault::Entry && asked == 2);
+  CHECK(check_handles(h.data(), 4, 4, 4, p, [&](uint32_t i) { return i != 3; }) == LKF_EORDER && why == HandleFault::Repeat);
+  const H r = {9, 0};
+  asked = 77;
+  CHECK(check_handles(r.data(), 4, 2, 4, p, [&](uint32_t i) { return asked = i, false; }) == LKF_EINVAL);
+  CHECK(why == HandleFault::Range && asked == 77);  // the test is not asked about an entry out of range
+}
+
+static void handles_stride() {
+  struct Rec {
+    uint8_t pad[3];  // (the handle is not 4-byte aligned)
+    uint8_t h[4];
+    uint8_t tail[6];
+  };
+  static_assert(sizeof(Rec) == 13, "an odd stride");
+  auto list = [](const H &h) {
+    std::vector<Rec> v(h.size());
+    for (size_t i = 0; i < h.size(); i++) {
+      std::memset(&v[i], 0xee, sizeof(Rec));
+      std::memcpy(v[i].h, &h[i], 4);
+    }
+    return v;
+  };
+  HandlePolicy p;
+  G g;
+  p.repeat = Repeat::Groups;
+  p.groups = &g;
+  p.end = true;
+  auto a = list({3, 3, 0, 2, 2, 2});
+  CHECK(check_handles(a[0].h, sizeof(Rec), 6, 4, p) == LKF_OK && g == G({0, 2, 3, 6}));
+  auto b = list({3, 0, 3});
+  CHECK(check_handles(b[0].h, sizeof(Rec), 3, 4, p) == LKF_EORDER);
+  auto c = list({3, 0, 4});
+  CHECK(check_handles(c[0].h, sizeof(Rec), 3, 4, p) == LKF_EINVAL);
+  CHECK(check_handles(c[0].h, sizeof(Rec), 2, 4, p) == LKF_OK && g == G({0, 1, 2}));  // n bounds the reads
+}
+
+static void handles_inactive_refused() {
+  const uint8_t active[4] = {1, 0, 1, 1};
+  HandleFault why = HandleFault::None;
+  for (Repeat rep : kPolicies) {
+    CHECK(hcheck({0, 1, 2}, 4, rep, nullptr, active, Inactive::Refuse, &why) == LKF_EINVAL && why == HandleFault::Inactive);
+    CHECK(hcheck({0, 2, 3}, 4, rep, nullptr, active, Inactive::Refuse, &why) == LKF_OK);
+    CHECK(hcheck({0, 5, 1}, 4, rep, nullptr, active, Inactive::Refuse, &why) == LKF_EINVAL && why == HandleFault::Range);
+  }
+  // a repeat earlier in the list is met first
+  CHECK(hcheck({0, 0, 1}, 4, Repeat::DistinctEorder, nullptr, active, Inactive::Refuse, &why) == LKF_EORDER);
+  CHECK(hcheck({1, 1}, 4, Repeat::DistinctEorder, nullptr, active, Inactive::Refuse, &why) == LKF_EINVAL &&
+        why == HandleFault::Inactive);
+}
+
+static void handles_inactive_skipped() {
+  const uint8_t active[4] = {1, 0, 1, 0};
+  G g;
+  CHECK(hcheck({0, 0, 1, 1, 2, 3}, 4, Repeat::Groups, &g, active, Inactive::Skip) == LKF_OK && g == G({0, 4, 6}));
+  CHECK(hcheck({1, 3}, 4, Repeat::Groups, &g, active, Inactive::Skip) == LKF_OK && g == G({2}));
+  CHECK(hcheck({0, 1, 2}, 4, Repeat::DistinctEinval, &g, active, Inactive::Skip) == LKF_OK && g == G({0, 2, 3}));
+  // a skipped handle still counts as seen
+  CHECK(hcheck({1, 0, 1}, 4, Repeat::Groups, &g, active, Inactive::Skip) == LKF_EORDER);
+  HandlePolicy p;  // without the end bound: the starts alone
+  p.repeat = Repeat::Groups;
+  p.groups = &g;
+  p.active = active;
+  p.inactive = Inactive::Skip;
+  const H h = {2, 2, 3, 0};
+  CHECK(check_handles(h.data(), 4, 4, 4, p) == LKF_OK && g == G({0, 3}));
+}
+
+// the rules restated entry by entry, every earlier entry rescanned
+static int handles_naive(const H &h, const std::vector<uint8_t> &entryBad, size_t limit, Repeat rep,
+                         const uint8_t *active, Inactive ina, G &groups) {
+  groups.clear();
+  for (size_t i = 0; i < h.size(); i++) {
+    if (h[i] < 0 || h[i] >= int64_t(limit)) return LKF_EINVAL;
+    if (entryBad[i]) return LKF_EINVAL;
+    const bool run = rep == Repeat::Groups || rep == Repeat::Any;
+    if (run && i > 0 && h[i - 1] == h[i]) continue;
+    if (rep != Repeat::Any)
+      for (size_t j = 0; j < i; j++)
+        if (h[j] == h[i]) return rep == Repeat::DistinctEinval ? LKF_EINVAL : LKF_EORDER;
+    if (active && !active[h[i]]) {
+      if (ina == Inactive::Refuse) return LKF_EINVAL;
+      continue;
+    }
+    groups.push_back(uint32_t(i));
+  }
+  groups.push_back(uint32_t(h.size()));
+  return LKF_OK;
+}
+
+static void handles_random() {
+  uint64_t s = 0x2545f4914f6cdd1dull;
+  auto rnd = [&]() {
+    s = s * 6364136223846793005ull + 1442695040888963407ull;
+    return uint32_t(s >> 33);
+  };
+  int ok = 0, einval = 0, eorder = 0;
+  for (int it = 0; it < 600; it++) {
+    const size_t limit = 4, n = rnd() % 9;
+    H h(n);
+    std::vector<uint8_t> bad(n, 0);
+    int32_t cur = int32_t(rnd() % limit);
+    for (size_t i = 0; i < n; i++) {
+      if (rnd() % 3) cur = int32_t(rnd() % limit);          // else: the run goes on
+      h[i] = rnd() % 40 == 0 ? int32_t(rnd() % 7) - 2 : cur;  // now and then out of range
+      bad[i] = rnd() % 50 == 0;
+    }
+    uint8_t active[4];
+    for (auto &a : active) a = rnd() % 5 != 0;
+    const Repeat rep = Repeat(rnd() % 4);
+    const Inactive ina = rnd() & 1 ? Inactive::Refuse : Inactive::Skip;
+    const uint8_t *act = rnd() & 1 ? active : nullptr;
+    G want, got;
+    const int rc = handles_naive(h, bad, limit, rep, act, ina, want);
+    HandlePolicy p;
+    p.repeat = rep;
+    p.groups = &got;
+    p.end = true;
+    p.active = act;
+    p.inactive = ina;
+    CHECK(check_handles(h.data(), 4, uint32_t(n), limit, p, [&](uint32_t i) { return !bad[i]; }) == rc);
+    if (rc == LKF_OK) CHECK(got == want);
+    (rc == LKF_OK ? ok : rc == LKF_EINVAL ? einval : eorder)++;
+  }
+  CHECK(ok > 50 && einval > 50 && eorder > 50);  // every outcome is exercised
+}
+
 static const struct {
   const char *name;
   void (*fn)();
 } kCases[] = {
+    {"handles_empty", handles_empty},
+    {"handles_range", handles_range},
+    {"handles_adjacent_repeat", handles_adjacent_repeat},
+    {"handles_split_repeat", handles_split_repeat},
+    {"handles_first_offender_wins", handles_first_offender_wins},
+    {"handles_stride", handles_stride},
+    {"handles_inactive_refused", handles_inactive_refused},
+    {"handles_inactive_skipped", handles_inactive_skipped},
+    {"handles_random", handles_random},
     {"devbuf_reserve_floor", devbuf_reserve_floor},
     {"devbuf_no_realloc", devbuf_no_realloc},
     {"devbuf_failed_grow", devbuf_failed_grow},
     {"devbuf_alloc_fixed", devbuf_alloc_fixed},
     {"devbuf_move", devbuf_move},
+    {"devbuf_family_settles", devbuf_family_settles},
     {"csr_empty", csr_empty},
     {"csr_one_lane_out_of_order", csr_one_lane_out_of_order},
     {"csr_equal_at_keeps_queue_order", csr_equal_at_keeps_queue_order},

@@ -23,6 +23,9 @@ the zero value (DownTrack takes its id before the first packet).
 import math
 import struct
 
+import numpy as np
+
+from tests import rtcp_wire_lib as W
 from tests.test_sender_cpu import M64, SN_INFO, PySender, s64
 
 M32 = (1 << 32) - 1
@@ -589,3 +592,64 @@ class Rig:
                 assert g == s, (dt, {k: (g[k], s[k]) for k in s if g[k] != s[k]})
             else:
                 assert g["initialized"] == 0, dt
+
+
+# ---- lkf_rtcp_ingest on a Rig: the call checked against the parse's restatement (tests/rtcp_wire_lib) ----
+RES_FIELDS = ("status", "fb_first", "fb_count", "reports", "nacks", "plis", "firs", "nack_first", "ref_first",
+              "ref_count")
+FB_FIELDS = ("flags", "last_sequence_number", "total_lost", "jitter", "last_sender_report", "delay", "nacks", "plis",
+             "firs", "fraction_lost")
+
+
+def ssrc(rig, dt):
+    return int(rig.tr.downtracks[dt].ssrc)
+
+
+def pack(pkg, entries, front=0):
+    """entries (dt, bytes) -> (RTCP_RAW_DTYPE array, arena bytes, offsets).  One bytes OBJECT listed by several
+    entries is laid down once: they name the same bytes.  `front` bytes of filler come first."""
+    arena = bytearray(b"\xee" * front)
+    raws = np.zeros(len(entries), dtype=pkg.abi.RTCP_RAW_DTYPE)
+    where = {}
+    for i, (dt, data) in enumerate(entries):
+        if id(data) not in where:
+            where[id(data)] = len(arena)
+            arena += data
+        raws[i] = (dt, where[id(data)], len(data))
+    return raws, bytes(arena), [int(x) for x in raws["off"]]
+
+
+def ingest(rig, entries, now, front=0, model=True):
+    """lkf_rtcp_ingest of `entries` on rig.eng, every output compared with the restatement and (model=True)
+    with the DownTracks' PyRtcp models, which advance.  -> (out, restated result dicts, NACK list)."""
+    pkg = rig.pkg
+    raws, arena, offs = pack(pkg, entries, front)
+    res, fbs, nacks, refs, _ = W.PyRtcpIn.call(entries, lambda d: ssrc(rig, d))
+    out, fb, fbo, grefs, nn = rig.eng.rtcp_ingest(raws, arena, now)
+    assert len(out) == len(entries)
+    for i, r in enumerate(res):
+        assert {k: int(out[i][k]) for k in RES_FIELDS} == r, (i, r)
+    assert len(fb) == len(fbs) == len(fbo)
+    for k, (dt, f) in enumerate(fbs):
+        assert int(fb[k]["dt"]) == dt and {x: int(fb[k][x]) for x in FB_FIELDS} == f, (k, f)
+    assert [(int(r["entry"]), int(r["kind"]), int(r["off"]), int(r["len"])) for r in grefs] == \
+        [(e, k, offs[e] + o, n) for e, k, o, n in refs]
+    got = rig.eng.rtcp_ingested_nacks()
+    assert nn == len(nacks) == len(got)
+    assert [(int(x["dt"]), int(x["sn"])) for x in got] == nacks
+    if model:
+        for i, r in enumerate(res):
+            rtt_report = 0
+            for k in range(r["fb_first"], r["fb_first"] + r["fb_count"]):
+                dt, f = fbs[k]
+                m = rig.models[dt]
+                want = (0, 0)
+                if f["flags"] & W.FB_HAS_RR:
+                    want = m.receiver_report(now, f["last_sequence_number"], f["total_lost"], f["jitter"],
+                                             f["last_sender_report"], f["delay"])
+                    if want[1] & FB_RTT_CHANGED:
+                        rtt_report = want[0]
+                m.counts(f["nacks"], f["plis"], f["firs"])
+                assert (int(fbo[k]["rtt_ms"]), int(fbo[k]["flags"])) == want, (i, k)
+            assert int(out[i]["rtt_ms"]) == rtt_report, i
+    return out, res, nacks

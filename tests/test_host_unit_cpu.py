@@ -4,8 +4,11 @@ livekit-server_amd/csrc/host_unit.cpp is a stand-alone program built with the
 host compiler and the address + undefined-behaviour sanitizers.  It tests
 DevBuf (dev_buf.h) over a malloc-backed fake of the two allocation functions
 (floors, no reallocation below the capacity, a failed grow leaving the buffer
-empty and retried, move-assignment freeing once, allocations == frees) and the
-control-op CSR (ctl_csr.h) against std::stable_sort by (lane, at_pkt).  Each
+empty and retried, move-assignment freeing once, allocations == frees, a
+scratch family shared by calls of opposite shapes settling on one size), the
+control-op CSR (ctl_csr.h) against std::stable_sort by (lane, at_pkt), and the
+control calls' handle-list check (handles.h: range, repeats under each policy,
+inactive handles, strides, the first offender deciding the code).  Each
 case runs as its own test; a sanitizer report fails the case it occurs in.
 """
 import os
@@ -28,8 +31,9 @@ NAMES = _names()
 
 
 def test_host_unit_inventory():
-    assert sum(n.startswith("devbuf_") for n in NAMES) >= 5
+    assert sum(n.startswith("devbuf_") for n in NAMES) >= 6
     assert sum(n.startswith("csr_") for n in NAMES) >= 7
+    assert sum(n.startswith("handles_") for n in NAMES) >= 9
     for nl in ("200", "300", "70000"):  # one, two and three radix passes
         assert "csr_nl_" + nl in NAMES
 

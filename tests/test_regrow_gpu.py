@@ -2,17 +2,28 @@
 
 Each case crosses the floor of a grown-on-demand device buffer family and then
 keeps using the regrown buffers: the sequencer lookup scratch (floor 256), the
-NACK -> RTX scratch (floor 1,024) and a batch context's control-op staging and
+NACK -> RTX scratch (floor 1,024), a batch context's control-op staging and
 event buffers (floor 4,096, which drains the engine and re-captures the
-context's stage graphs).  Every result is compared with the CPU oracle on
-identical input, on the 2-second configs[0] trace smoke() uses."""
+context's stage graphs), the RTCP calls' input / group / result buffers (floor
+65,536 bytes; one call past it, and the three calls in turn with their
+opposite shapes) and the RTCP ingress's per-entry buffers (floor 4,096 entries).
+Every result is compared with the CPU oracle on identical input (the RTCP
+calls: with tests/rtcp_lib.PyRtcp, replayed over the oracle's records), on the
+2-second configs[0] trace smoke() uses.
+
+The padding and allocation scratch families grow only past 1,024 distinct
+DownTracks; a topology that large does not belong in a seconds-long test, and
+they grow through the same code as the two RTCP families here."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
-from tests import rtx_lib
+from tests import rtcp_lib, rtx_lib
+from tests import rtcp_wire_lib as W
 from tests.oracle_lib import load as load_oracle
+from tests.rtcp_lib import ingest as checked_ingest
+from tests.rtcp_lib import rr_lsn
 
 pytestmark = pytest.mark.gpu
 EPOCH = 1700000000 * 10**9
@@ -165,3 +176,83 @@ def test_ctl_batch_regrow_and_recapture(pkg, workload, abi):
         eng.close()
         o.destroy(oh)
         tr.close()
+
+
+def _rtcp_rig(pkg, workload):
+    tr = _trace(workload)
+    rig = rtcp_lib.Rig(pkg, workload, tr, pkg.Engine.for_trace(tr))
+    rig.forward(tr.nbatches)
+    live = [d for d, m in enumerate(rig.models) if m.s.init]
+    assert len(live) > 4
+    return rig, live
+
+
+def test_rtcp_feedback_regrow(pkg, workload):
+    """lkf_rtcp_feedback with 100, 1,400 and 100 entries of 48 bytes: below the 65,536-byte floor of the call's
+    input buffer, past it (the input, group and result buffers regrow), and below again.  Each DownTrack's
+    entries are contiguous: a report first, then entries that only carry counts."""
+    rig, live = _rtcp_rig(pkg, workload)
+    try:
+        for step, total in enumerate((100, 1400, 100)):
+            per = -(-total // len(live))
+            ent = []
+            for d in live:
+                m = rig.models[d]
+                ent.append((d, True, rr_lsn(m.s.high_sn - 2 + step, m.s.start_sn), step, 10 * step + d % 7, 0, 0,
+                            1, 0, 0))
+                ent += [(d, False, 0, 0, 0, 0, 0, k % 3, k % 2, 1) for k in range(per - 1)]
+            ent = ent[:total]
+            assert len(ent) == total and total * 48 > (65536 if step == 1 else 0)
+            rig.feedback(ent, EPOCH + (3 + step) * 10**9)
+            rig.check_state()
+    finally:
+        rig.close()
+
+
+def test_rtcp_ingest_regrow(pkg, workload):
+    """lkf_rtcp_ingest with 64, 4,097 and 64 entries: below the 4,096-entry floor of the per-entry buffers,
+    past it (all twelve regrow and the scan state is zeroed again), and below again.  A DownTrack's entries
+    name the same few bytes, so the whole arena is a few hundred bytes."""
+    rig, live = _rtcp_rig(pkg, workload)
+    try:
+        for step, total in enumerate((64, 4097, 64)):
+            per = -(-total // len(live))
+            entries = []
+            for d in live:
+                m, ssrc = rig.models[d], int(rig.tr.downtracks[d].ssrc)
+                c = W.compound(W.rr(1, [W.report_block(ssrc, 0, step, rr_lsn(m.s.high_sn - 2 + step, m.s.start_sn),
+                                                       5 + step, 0, 0)]), W.sdes(1), W.pli(1, ssrc))
+                entries += [(d, c)] * per
+            entries = entries[:total]
+            assert len(entries) == total
+            out, _, _ = checked_ingest(rig, entries, EPOCH + (3 + step) * 10**9)
+            assert int(out["reports"].sum()) == total and int(out["plis"].sum()) == total
+            rig.check_state()
+    finally:
+        rig.close()
+
+
+def test_rtcp_calls_alternate_past_the_floor(pkg, workload):
+    """The three RTCP calls share one scratch family and need opposite shapes: feedback is input-heavy (48 bytes
+    in, 8 out per entry), sender reports and delta info are output-heavy (8 or 4 in, 68 or 120 out).  Over 1,080
+    DownTracks a tick of the three crosses the 65,536-byte floor on the input side (2 x 1,076 x 48), then on the
+    output side (1,076 x 68, then x 120); two ticks, every result and the whole state against the model."""
+    tr = workload.Trace(2, rooms=6, duration_s=1.0, batch_s=1.0, seed=1)
+    rig = rtcp_lib.Rig(pkg, workload, tr, pkg.Engine.for_trace(tr))
+    try:
+        rig.forward(tr.nbatches)
+        live = [d for d, m in enumerate(rig.models) if m.s.init]
+        assert len(live) * 2 * 48 > 65536 and len(live) * 68 > 65536 > len(live) * 2 * 8
+        for tick in range(2):
+            now = EPOCH + (2 + tick) * 10**9
+            rig.sender_reports([(d, 0) for d in live], now)
+            ent = []
+            for d in live:
+                m = rig.models[d]
+                ent += [(d, True, rr_lsn(m.s.high_sn - 1 + tick, m.s.start_sn), tick, d % 5, 0, 0, 1, 0, 0),
+                        (d, False, 0, 0, 0, 0, 0, 0, 1, tick)]
+            rig.feedback(ent, now + 10**8)
+            rig.delta(live)
+            rig.check_state()
+    finally:
+        rig.close()

@@ -15,15 +15,12 @@ import pytest
 
 from tests import pad_lib, rtcp_lib, rtx_lib
 from tests import rtcp_wire_lib as W
-from tests.rtcp_lib import FB_RTT_CHANGED, rr_lsn
+from tests.rtcp_lib import ingest, pack, rr_lsn
+from tests.rtcp_lib import ssrc as _ssrc
 
 pytestmark = pytest.mark.gpu
 EPOCH = 1700000000 * 10**9
 SEC = 10**9
-RES_FIELDS = ("status", "fb_first", "fb_count", "reports", "nacks", "plis", "firs", "nack_first", "ref_first",
-              "ref_count")
-FB_FIELDS = ("flags", "last_sequence_number", "total_lost", "jitter", "last_sender_report", "delay", "nacks", "plis",
-             "firs", "fraction_lost")
 
 
 def _rig(pkg, workload, config, extra_dts=0, nb=4):
@@ -32,63 +29,9 @@ def _rig(pkg, workload, config, extra_dts=0, nb=4):
     return rtcp_lib.Rig(pkg, workload, tr, pkg.Engine.for_trace(tr, extra_dts=extra_dts))
 
 
-def _ssrc(rig, dt):
-    return int(rig.tr.downtracks[dt].ssrc)
-
-
 def _block(rig, dt, esn, lost=0, jitter=0, lsr=0, dlsr=0):
     """A report block that acknowledges the DownTrack's sent extended SN `esn`."""
     return W.report_block(_ssrc(rig, dt), lost & 0xFF, lost, rr_lsn(esn, rig.models[dt].s.start_sn), jitter, lsr, dlsr)
-
-
-def pack(pkg, entries, front=0):
-    """entries (dt, bytes) -> (RTCP_RAW_DTYPE array, arena bytes, offsets).  One bytes OBJECT listed by several
-    entries is laid down once: they name the same bytes.  `front` bytes of filler come first."""
-    arena = bytearray(b"\xee" * front)
-    raws = np.zeros(len(entries), dtype=pkg.abi.RTCP_RAW_DTYPE)
-    where = {}
-    for i, (dt, data) in enumerate(entries):
-        if id(data) not in where:
-            where[id(data)] = len(arena)
-            arena += data
-        raws[i] = (dt, where[id(data)], len(data))
-    return raws, bytes(arena), [int(x) for x in raws["off"]]
-
-
-def ingest(rig, entries, now, front=0, model=True):
-    """lkf_rtcp_ingest of `entries` on rig.eng, every output compared with the restatement and (model=True)
-    with the DownTracks' PyRtcp models, which advance.  -> (out, restated result dicts, NACK list)."""
-    pkg = rig.pkg
-    raws, arena, offs = pack(pkg, entries, front)
-    res, fbs, nacks, refs, _ = W.PyRtcpIn.call(entries, lambda d: _ssrc(rig, d))
-    out, fb, fbo, grefs, nn = rig.eng.rtcp_ingest(raws, arena, now)
-    assert len(out) == len(entries)
-    for i, r in enumerate(res):
-        assert {k: int(out[i][k]) for k in RES_FIELDS} == r, (i, r)
-    assert len(fb) == len(fbs) == len(fbo)
-    for k, (dt, f) in enumerate(fbs):
-        assert int(fb[k]["dt"]) == dt and {x: int(fb[k][x]) for x in FB_FIELDS} == f, (k, f)
-    assert [(int(r["entry"]), int(r["kind"]), int(r["off"]), int(r["len"])) for r in grefs] == \
-        [(e, k, offs[e] + o, n) for e, k, o, n in refs]
-    got = rig.eng.rtcp_ingested_nacks()
-    assert nn == len(nacks) == len(got)
-    assert [(int(x["dt"]), int(x["sn"])) for x in got] == nacks
-    if model:
-        for i, r in enumerate(res):
-            rtt_report = 0
-            for k in range(r["fb_first"], r["fb_first"] + r["fb_count"]):
-                dt, f = fbs[k]
-                m = rig.models[dt]
-                want = (0, 0)
-                if f["flags"] & W.FB_HAS_RR:
-                    want = m.receiver_report(now, f["last_sequence_number"], f["total_lost"], f["jitter"],
-                                             f["last_sender_report"], f["delay"])
-                    if want[1] & FB_RTT_CHANGED:
-                        rtt_report = want[0]
-                m.counts(f["nacks"], f["plis"], f["firs"])
-                assert (int(fbo[k]["rtt_ms"]), int(fbo[k]["flags"])) == want, (i, k)
-            assert int(out[i]["rtt_ms"]) == rtt_report, i
-    return out, res, nacks
 
 
 def _compound_like_struct_entry(rig, ent):
