@@ -843,8 +843,9 @@ int lkf_rtx_emit_bucket(lkf_engine *e, const lkf_rtx *rtx, uint32_t n, lkf_out *
 /* ---- RTCP ingress: DownTrack.handleRTCP from the bytes ------------------ *
  * rtcp.Unmarshal(bytes) and the switch over packet types
  * (downtrack.go:1474-1563) for many DownTracks at once: the compound packets
- * as pion's RTPSender.Read hands them to each DownTrack (SRTCP already
- * removed) are parsed on the GPU, every reception report and counter is
+ * as pion's RTPSender.Read hands them to each DownTrack (plaintext: the
+ * caller's own, or what lkf_srtcp_unprotect left on the device, see
+ * lkf_rtcp_ingest_unprotected) are parsed on the GPU, every reception report and counter is
  * applied as lkf_rtcp_feedback would apply it, and the NACKed sequence numbers
  * stay on the device for lkf_rtx_lookup_ingested.
  *
@@ -1297,7 +1298,7 @@ int lkf_stream_set_rtt(lkf_engine *e, int32_t stream, uint32_t rtt_ms);
  * computes, from RFC 3711 §3.3 and RFC 7714 with pion's ordering (replay
  * check, then authenticate, then commit); parity unpinned, DESIGN.md §2.
  * Profiles and keys are those of lkf_add_transport (AES-128 only, no MKI,
- * key-derivation rate 0); SRTCP is out of scope.
+ * key-derivation rate 0); SRTCP has its own section below.
  *
  * Per received stream, in the order the call lists that stream's datagrams:
  *   started; s_l, the u64 index ROC << 16 | SEQ of the highest authenticated
@@ -1376,6 +1377,140 @@ int lkf_stream_srtp_get(lkf_engine *e, int32_t stream, lkf_stream_srtp *out);
 /* Over the last n unprotect calls (n <= 256): the sum of the unprotect stage
  * spans (index, crypto and commit kernels), ms. */
 int lkf_unprotect_timing_window(lkf_engine *e, uint32_t n, float *unprotect_ms);
+
+/* ---- SRTCP: unprotect in front of RTCP ingress, protect out ----------------- *
+ * What a subscriber's PeerConnection sends back is SRTCP, and what the server
+ * sends it (sender reports) is SRTCP as well: pion/srtp v2.0.18
+ * Context.DecryptRTCP behind SessionSRTCP, Context.EncryptRTCP behind
+ * WriteRTCP.  These calls do both on the GPU for the transports of
+ * lkf_add_transport (either direction's keys: a transport made with the remote
+ * side's write key opens, one made with the local write key seals).
+ *
+ * pion/srtp is not part of the reference tree, so the engine defines what it
+ * computes, from RFC 3711 §3.4 and §4.3, RFC 7714 §9 and §10 and pion's
+ * ordering; parity unpinned, DESIGN.md §2.  No MKI, key-derivation rate 0,
+ * AES-128 only.
+ *
+ * Keys.  A second session key set per transport from the same master key and
+ * salt with the PRF of the SRTP keys: labels 3 (encryption, 16 bytes), 4
+ * (authentication, 20 bytes, AES-CM only), 5 (salt, 14 bytes; 12 for GCM).
+ * For GCM the GHASH key is H = E(K, 0^128) of the SRTCP encryption key.
+ *
+ * Packet layout, len the datagram's length, T the tag length (10 / 16):
+ *   AES_CM_128_HMAC_SHA1_80   hdr[0:8] || enc(body) || E:1|index:31 (4 bytes,
+ *     big-endian) || tag[10].  tag = the first 10 bytes of HMAC-SHA1(auth key,
+ *     pkt[0 : len - 10]): the E||index word is inside the hash, no ROC is
+ *     appended.  Keystream: AES-CM with counter (salt << 16) XOR (SSRC << 64)
+ *     XOR (index << 16), from block 0 at byte 8; SSRC = bytes 4..7.  (pion's
+ *     generateCounter(index & 0xffff, index >> 16, ssrc, salt): the index sits
+ *     where ROC || SEQ sits for SRTP.)  Plaintext: hdr[0:8] || body, len - 14
+ *     bytes.
+ *   AEAD_AES_128_GCM          hdr[0:8] || ciphertext || tag[16] || E:1|index:31.
+ *     IV = (00 00 || SSRC || 00 00 || index_be32) XOR the 12-byte salt; AAD =
+ *     12 bytes, hdr[0:8] || the trailer word with E set; counter blocks and J0
+ *     as in lkf_protect.  Plaintext: len - 20 bytes.
+ *
+ * Receive state, per transport: LKF_SRTCP_SSRCS slots {in use, SSRC, latest (u32
+ * index), mask (u64: bit k says index latest - k was accepted)}.  pion keeps
+ * one such state per sender SSRC without a bound: the bound is a divergence.
+ * Replay window 64 (pion/webrtc's default for SRTCP too).
+ *
+ * For each datagram {transport, off, len}, in the order the call lists that
+ * transport's datagrams:
+ *   1. Parse.  LKF_SRTCP_RX_MALFORMED when the transport handle is unknown,
+ *      off is not a multiple of 16, off + len exceeds the arena, len < 8 + 4 +
+ *      T, or the version bits of byte 0 are not 2 (no byte of such a datagram
+ *      is read beyond byte 0).
+ *   2. LKF_SRTCP_RX_UNENCRYPTED when the E bit of the trailer word is 0.  A
+ *      divergence: pion's AES-CM path returns such a packet without
+ *      authenticating it; the engine hands nothing unauthenticated on, and
+ *      WebRTC peers always set E.
+ *   3. index = the trailer word & 0x7fffffff; ssrc = bytes 4..7.
+ *   4. Slot: the in-use slot with that SSRC.  Found and index <= latest:
+ *      latest - index >= 64 is LKF_SRTCP_RX_REPLAY_OLD, a set mask bit
+ *      LKF_SRTCP_RX_REPLAY_DUP.  Not found and all slots in use:
+ *      LKF_SRTCP_RX_NO_SLOT.  The comparison is plain unsigned: no 31-bit wrap
+ *      handling (index overflow is out of scope, as ROC overflow is for SRTP).
+ *   5. Authenticate.  A mismatch is LKF_SRTCP_RX_AUTH with no state change: a
+ *      forged packet with a new SSRC takes no slot, one far ahead does not
+ *      move latest.
+ *   6. Accept.  New SSRC: the lowest free slot, latest = index, mask = 1.
+ *      index > latest: mask <<= index - latest (0 when the shift is >= 64), bit
+ *      0 set, latest = index.  Otherwise bit latest - index set.
+ * Per-transport counters: accepted, auth_failures, replays, malformed,
+ * unencrypted, no_slot; a MALFORMED datagram with an unknown handle counts
+ * nowhere.  A rejected datagram's result has len = 0 and the bytes of its slot
+ * in the plaintext arena are unspecified; nothing is written past srtcp_len.
+ * The result's ssrc and index are 0 for MALFORMED and UNENCRYPTED datagrams.
+ *
+ * Send.  Per (transport, sender SSRC) a 31-bit index counter, incremented
+ * before use (the first packet carries index 1, pion's srtcpIndex++; 0 follows
+ * 0x7fffffff).  E is always set. */
+#define LKF_SRTCP_SSRCS 16
+#define LKF_SRTCP_RX_OK 0
+#define LKF_SRTCP_RX_MALFORMED 1
+#define LKF_SRTCP_RX_REPLAY_OLD 2
+#define LKF_SRTCP_RX_REPLAY_DUP 3
+#define LKF_SRTCP_RX_AUTH 4
+#define LKF_SRTCP_RX_UNENCRYPTED 5
+#define LKF_SRTCP_RX_NO_SLOT 6
+typedef struct lkf_srtcp_raw { /* one datagram (receive) or plaintext compound packet (send); 12 B */
+  int32_t transport;
+  uint32_t off, len;
+} lkf_srtcp_raw;
+typedef struct lkf_srtcp_rx_result { /* 16 B */
+  uint32_t ssrc, index;
+  uint32_t status; /* LKF_SRTCP_RX_* */
+  uint32_t len;    /* the plaintext's length at in[i].off of the plaintext arena; 0 when rejected */
+} lkf_srtcp_rx_result;
+/* Unprotects n datagrams of the arena srtcp (host memory; the engine pads its
+ * own staging, the caller's buffer needs no slack).  A control-rate call like
+ * the other RTCP calls: it queues behind the sender stream, waits and copies
+ * out.  out[i] answers in[i]; plain (srtcp_len bytes, may be NULL) receives the
+ * plaintext arena, which also stays on the device for
+ * lkf_rtcp_ingest_unprotected until the next lkf_srtcp_unprotect. */
+int lkf_srtcp_unprotect(lkf_engine *e, const lkf_srtcp_raw *in, uint32_t n, const uint8_t *srtcp, uint64_t srtcp_len,
+                        uint8_t *plain, lkf_srtcp_rx_result *out);
+typedef struct lkf_rtcp_entry { /* one handleRTCP call on DownTrack dt with datagram dgram's plaintext; 8 B */
+  int32_t dt;
+  uint32_t dgram; /* index into the last lkf_srtcp_unprotect's list */
+} lkf_rtcp_entry;
+/* lkf_rtcp_ingest on the plaintext the last lkf_srtcp_unprotect left on the
+ * device: entry i is the whole plaintext of datagram in[i].dgram (a rejected
+ * datagram is an entry of len 0, LKF_RTCP_IN_MALFORMED by the rule above);
+ * several entries may name one datagram.  Which DownTracks a decrypted
+ * compound addresses (pion's DestinationSSRC) is the host's to decide between
+ * the two calls.  The grouping rule, the outputs and the error codes are
+ * lkf_rtcp_ingest's; a dgram out of range is LKF_EINVAL before anything runs.
+ * lkf_rtcp_ref.off / len index the plaintext arena lkf_srtcp_unprotect
+ * returned. */
+int lkf_rtcp_ingest_unprotected(lkf_engine *e, const lkf_rtcp_entry *in, uint32_t n, int64_t now_ns,
+                                lkf_rtcp_in_result *out, lkf_rtcp_fb *fb, lkf_rtcp_fb_result *fb_out, uint32_t fb_cap,
+                                uint32_t *n_fb, lkf_rtcp_ref *refs, uint32_t ref_cap, uint32_t *n_refs,
+                                uint32_t *n_nacks);
+typedef struct lkf_transport_srtcp { /* one transport's SRTCP receive slots and counters; 368 B */
+  uint32_t in_use[LKF_SRTCP_SSRCS], ssrc[LKF_SRTCP_SSRCS], latest[LKF_SRTCP_SSRCS];
+  uint64_t mask[LKF_SRTCP_SSRCS];
+  uint64_t accepted, auth_failures, replays, malformed, unencrypted, no_slot;
+} lkf_transport_srtcp;
+int lkf_transport_srtcp_get(lkf_engine *e, int32_t transport, lkf_transport_srtcp *out); /* (waits for queued work) */
+/* A new DTLS session on the handle: receive slots, counters and send indices cleared. */
+int lkf_srtcp_reset(lkf_engine *e, int32_t transport);
+typedef struct lkf_srtcp_tx_result { /* 16 B */
+  uint32_t ssrc, index;
+  uint32_t off, len; /* the protected packet in out */
+} lkf_srtcp_tx_result;
+/* Protects n plaintext compound packets (in[i].off / len in plain; len >= 8,
+ * version 2).  Packet i goes to res[i].off = the sum over j < i of
+ * (in[j].len + 20 + 15) & ~15 and is len + 14 (AES-CM) or len + 20 (GCM) bytes
+ * long; *out_len (may be NULL) = the sum over all n.  An unknown transport,
+ * len < 8, a version other than 2 or off + len beyond plain_len is LKF_EINVAL,
+ * out_cap < *out_len LKF_ENOSPC, both before any index is consumed.
+ * Control-rate, as lkf_srtcp_unprotect. */
+int lkf_srtcp_protect(lkf_engine *e, const lkf_srtcp_raw *in, uint32_t n, const uint8_t *plain, uint64_t plain_len,
+                      uint8_t *out, uint64_t out_cap, lkf_srtcp_tx_result *res, uint64_t *out_len);
+/* The index the last packet of (transport, ssrc) carried; 0 when none has been sent. */
+int lkf_srtcp_tx_index(lkf_engine *e, int32_t transport, uint32_t ssrc, uint32_t *index);
 /* Removes a published track: WebRTCReceiver.closeTracks (receiver.go:700-716)
  * closes its DownTracks (as lkf_remove_downtrack each) and the Buffers of its
  * streams (Buffer.Close buffer.go:337-352: Write then returns io.EOF, so a

@@ -233,6 +233,7 @@ class Engine:
         self.h = self.lib.lkf_create(device, C.byref(cfg))
         if not self.h:
             raise EngineError("lkf_create failed on HIP device %d (no GPU or out of memory)" % device)
+        self._srtcp_lens = np.zeros(0, dtype=np.uint32)  # the last srtcp_unprotect's plaintext lengths
 
     @classmethod
     def for_trace(cls, trace, device=0, headroom=1.25, extra_dts=0, **kw):
@@ -381,6 +382,74 @@ class Engine:
                                           len(fb), C.byref(nfb), refs.ctypes.data, len(refs), C.byref(nref),
                                           C.byref(nn)), "rtcp_ingest")
         return out, fb[:nfb.value], fbo[:nfb.value], refs[:nref.value], nn.value
+
+    def srtcp_unprotect(self, raws, arena, want_plain=True):
+        """lkf_srtcp_unprotect: `raws` an abi.SRTCP_RAW_DTYPE array, `arena`
+        the datagrams' bytes (bytes or a uint8 array) ->
+        (abi.SRTCP_RX_RESULT_DTYPE per datagram, the plaintext arena as a
+        uint8 array of the input's length, or None)."""
+        rw = np.ascontiguousarray(raws, dtype=abi.SRTCP_RAW_DTYPE)
+        ar = np.frombuffer(arena, dtype=np.uint8) if isinstance(arena, (bytes, bytearray)) else \
+            np.ascontiguousarray(arena, dtype=np.uint8)
+        out = np.zeros(len(rw), dtype=abi.SRTCP_RX_RESULT_DTYPE)
+        plain = np.zeros(len(ar), dtype=np.uint8) if want_plain else None
+        self._chk(self.api["srtcp_unprotect"](self.h, rw.ctypes.data, len(rw), ar.ctypes.data if len(ar) else None,
+                                              len(ar), plain.ctypes.data if want_plain and len(ar) else None,
+                                              out.ctypes.data), "srtcp_unprotect")
+        self._srtcp_lens = out["len"].copy()
+        return out, plain
+
+    def rtcp_ingest_unprotected(self, entries, now_ns):
+        """lkf_rtcp_ingest_unprotected: `entries` an abi.RTCP_ENTRY_DTYPE array
+        grouped by DownTrack, naming datagrams of the last srtcp_unprotect ->
+        what rtcp_ingest returns.  The lists are sized from that call's
+        plaintext lengths (`_srtcp_lens`)."""
+        en = np.ascontiguousarray(entries, dtype=abi.RTCP_ENTRY_DTYPE)
+        ln = np.zeros(len(en), dtype=np.int64)
+        if len(en) and len(self._srtcp_lens):  # (a dgram out of range is the call's to refuse)
+            ln = np.take(self._srtcp_lens, en["dgram"], mode="clip").astype(np.int64)
+        fb_cap = int(np.maximum(1, ln // 24).sum())
+        ref_cap = int((ln // 20).sum())
+        out = np.zeros(len(en), dtype=abi.RTCP_IN_RESULT_DTYPE)
+        fb = np.zeros(max(1, fb_cap), dtype=abi.RTCP_FB_DTYPE)
+        fbo = np.zeros(max(1, fb_cap), dtype=abi.RTCP_FB_RESULT_DTYPE)
+        refs = np.zeros(max(1, ref_cap), dtype=abi.RTCP_REF_DTYPE)
+        nfb, nref, nn = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        self._chk(self.api["rtcp_ingest_unprotected"](self.h, en.ctypes.data, len(en), now_ns, out.ctypes.data,
+                                                      fb.ctypes.data, fbo.ctypes.data, len(fb), C.byref(nfb),
+                                                      refs.ctypes.data, len(refs), C.byref(nref), C.byref(nn)),
+                  "rtcp_ingest_unprotected")
+        return out, fb[:nfb.value], fbo[:nfb.value], refs[:nref.value], nn.value
+
+    def transport_srtcp(self, transport):
+        """lkf_transport_srtcp_get -> (slots [(in_use, ssrc, latest, mask)] * 16, the six counters)."""
+        st = abi.lkf_transport_srtcp()
+        self._chk(self.api["transport_srtcp_get"](self.h, transport, C.byref(st)), "transport_srtcp_get")
+        return st.as_tuple()
+
+    def srtcp_reset(self, transport):
+        self._chk(self.api["srtcp_reset"](self.h, transport), "srtcp_reset")
+
+    def srtcp_protect(self, raws, plain):
+        """lkf_srtcp_protect: `raws` an abi.SRTCP_RAW_DTYPE array of plaintext
+        compound packets in `plain` -> (abi.SRTCP_TX_RESULT_DTYPE per packet,
+        the protected arena as a uint8 array of out_len bytes)."""
+        rw = np.ascontiguousarray(raws, dtype=abi.SRTCP_RAW_DTYPE)
+        ar = np.frombuffer(plain, dtype=np.uint8) if isinstance(plain, (bytes, bytearray)) else \
+            np.ascontiguousarray(plain, dtype=np.uint8)
+        cap = int(((rw["len"].astype(np.int64) + 35) & ~15).sum())
+        out = np.zeros(max(1, cap), dtype=np.uint8)
+        res = np.zeros(len(rw), dtype=abi.SRTCP_TX_RESULT_DTYPE)
+        n = C.c_uint64()
+        self._chk(self.api["srtcp_protect"](self.h, rw.ctypes.data, len(rw), ar.ctypes.data if len(ar) else None,
+                                            len(ar), out.ctypes.data, cap, res.ctypes.data, C.byref(n)),
+                  "srtcp_protect")
+        return res, out[:n.value]
+
+    def srtcp_tx_index(self, transport, ssrc):
+        k = C.c_uint32()
+        self._chk(self.api["srtcp_tx_index"](self.h, transport, ssrc, C.byref(k)), "srtcp_tx_index")
+        return k.value
 
     def _ingested_nack_count(self):
         k = C.c_uint32()

@@ -498,6 +498,52 @@ class lkf_stream_srtp(C.Structure):
 assert C.sizeof(lkf_stream_srtp) == 56
 
 
+# SRTCP (lkf_srtcp_unprotect / lkf_rtcp_ingest_unprotected / lkf_srtcp_protect)
+LKF_SRTCP_SSRCS = 16
+(LKF_SRTCP_RX_OK, LKF_SRTCP_RX_MALFORMED, LKF_SRTCP_RX_REPLAY_OLD, LKF_SRTCP_RX_REPLAY_DUP, LKF_SRTCP_RX_AUTH,
+ LKF_SRTCP_RX_UNENCRYPTED, LKF_SRTCP_RX_NO_SLOT) = range(7)
+
+
+class lkf_srtcp_raw(C.Structure):
+    _fields_ = [("transport", C.c_int32), ("off", C.c_uint32), ("len", C.c_uint32)]
+
+
+class lkf_srtcp_rx_result(C.Structure):
+    _fields_ = [(f, C.c_uint32) for f in ("ssrc", "index", "status", "len")]
+
+
+class lkf_rtcp_entry(C.Structure):
+    _fields_ = [("dt", C.c_int32), ("dgram", C.c_uint32)]
+
+
+class lkf_srtcp_tx_result(C.Structure):
+    _fields_ = [(f, C.c_uint32) for f in ("ssrc", "index", "off", "len")]
+
+
+class lkf_transport_srtcp(C.Structure):
+    _fields_ = ([(f, C.c_uint32 * LKF_SRTCP_SSRCS) for f in ("in_use", "ssrc", "latest")]
+                + [("mask", C.c_uint64 * LKF_SRTCP_SSRCS)]
+                + [(f, C.c_uint64) for f in ("accepted", "auth_failures", "replays", "malformed", "unencrypted",
+                                             "no_slot")])
+
+    def as_tuple(self):
+        """(slots [(in_use, ssrc, latest, mask)] * 16, (the six counters))."""
+        slots = [(self.in_use[k], self.ssrc[k], self.latest[k], self.mask[k]) for k in range(LKF_SRTCP_SSRCS)]
+        return slots, (self.accepted, self.auth_failures, self.replays, self.malformed, self.unencrypted,
+                       self.no_slot)
+
+
+SRTCP_RAW_DTYPE = np.dtype([("transport", "<i4"), ("off", "<u4"), ("len", "<u4")])
+SRTCP_RX_RESULT_DTYPE = np.dtype([(f, "<u4") for f in ("ssrc", "index", "status", "len")])
+RTCP_ENTRY_DTYPE = np.dtype([("dt", "<i4"), ("dgram", "<u4")])
+SRTCP_TX_RESULT_DTYPE = np.dtype([(f, "<u4") for f in ("ssrc", "index", "off", "len")])
+assert C.sizeof(lkf_srtcp_raw) == 12 == SRTCP_RAW_DTYPE.itemsize
+assert C.sizeof(lkf_srtcp_rx_result) == 16 == SRTCP_RX_RESULT_DTYPE.itemsize
+assert C.sizeof(lkf_rtcp_entry) == 8 == RTCP_ENTRY_DTYPE.itemsize
+assert C.sizeof(lkf_srtcp_tx_result) == 16 == SRTCP_TX_RESULT_DTYPE.itemsize
+assert C.sizeof(lkf_transport_srtcp) == 368
+
+
 class lkf_seq_meta(C.Structure):
     _fields_ = [
         ("ext_sn", C.c_uint64),
@@ -747,6 +793,21 @@ def bind_engine_api(lib, prefix):
                                            [e, C.c_void_p, C.c_uint32, P(C.c_uint32)])
         api["rtx_lookup_ingested"] = _bind(lib, prefix + "rtx_lookup_ingested", C.c_int,
                                            [e, C.c_int64, C.c_void_p, C.c_uint32, P(C.c_uint32)])
+    if hasattr(lib, prefix + "srtcp_unprotect"):  # engine only: SRTCP
+        api["srtcp_unprotect"] = _bind(lib, prefix + "srtcp_unprotect", C.c_int,
+                                       [e, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p])
+        api["rtcp_ingest_unprotected"] = _bind(lib, prefix + "rtcp_ingest_unprotected", C.c_int,
+                                               [e, C.c_void_p, C.c_uint32, C.c_int64, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_uint32, P(C.c_uint32), C.c_void_p, C.c_uint32,
+                                                P(C.c_uint32), P(C.c_uint32)])
+        api["transport_srtcp_get"] = _bind(lib, prefix + "transport_srtcp_get", C.c_int,
+                                           [e, C.c_int32, P(lkf_transport_srtcp)])
+        api["srtcp_reset"] = _bind(lib, prefix + "srtcp_reset", C.c_int, [e, C.c_int32])
+        api["srtcp_protect"] = _bind(lib, prefix + "srtcp_protect", C.c_int,
+                                     [e, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
+                                      C.c_void_p, P(C.c_uint64)])
+        api["srtcp_tx_index"] = _bind(lib, prefix + "srtcp_tx_index", C.c_int,
+                                      [e, C.c_int32, C.c_uint32, P(C.c_uint32)])
     api["blank_frames"] = _bind(lib, prefix + "blank_frames", C.c_int,
                                 [e, C.c_void_p, C.c_uint32, C.c_int64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64,
                                  P(C.c_uint32), P(C.c_uint64)])

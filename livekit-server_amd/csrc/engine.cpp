@@ -486,6 +486,23 @@ struct lkf_engine {
   Event rxRing[256][2];             // unprotect stage start / end per call (timing)
   uint64_t nUnprotects = 0;
   uint32_t lastUnprotectN = 0;
+  // SRTCP: the second session key set, the receive slot tables with their
+  // speculated copies and the per-call ranges (all as long as dSrtpKeys, grown
+  // with it); the calls' scratch (one family per direction) and staging
+  DevBuf<SrtpKeys> dSrtcpKeys;
+  DevBuf<lkf_transport_srtcp> dSrtcpRx, dSrtcpRxSpec;
+  DevBuf<uint32_t> dSrtcpRange;
+  DevBuf<lkf_srtcp_raw> dScIn;
+  DevBuf<lkf_srtcp_rx_result> dScSpec, dScRes;
+  DevBuf<uint32_t> dScAuth;
+  DevBuf<uint8_t> dScArena, dScPlain;  // (padded: the kernels' 16-B reads stay inside)
+  DevBuf<SrtcpTx> dScTx;
+  DevBuf<uint8_t> dScTxIn, dScTxOut;
+  // the last lkf_srtcp_unprotect, for lkf_rtcp_ingest_unprotected: each
+  // datagram's offset and plaintext length in dScPlain
+  std::vector<uint32_t> scOff, scLen;
+  uint64_t scPlainLen = 0;
+  std::map<std::pair<int32_t, uint32_t>, uint32_t> scTxIndex;  // (transport, SSRC) -> the last index sent
   // ingress (one buffer.Buffer per stream) + speakers
   uint32_t maxStreams = 0;
   DevBuf<DevStream> dStreams;
@@ -2650,13 +2667,34 @@ int32_t lkf_add_transport(lkf_engine *e, const lkf_transport_params *p) {
              "copy transports");
       HIPCHK(hipMemcpy(nk, e->dSrtpKeys, t * sizeof(SrtpKeys), hipMemcpyDeviceToDevice), "copy keys");
     }
+    // the SRTCP keys, slot tables and ranges (the tables of new handles start empty)
+    DevBuf<SrtpKeys> nck;
+    DevBuf<lkf_transport_srtcp> nrx, nspec;
+    DevBuf<uint32_t> nrange;
+    HIPCHK(nck.alloc(cap), "alloc srtcp keys");
+    HIPCHK(nrx.alloc(cap), "alloc srtcp rx state");
+    HIPCHK(nspec.alloc(cap), "alloc srtcp rx spec state");
+    HIPCHK(nrange.alloc(2 * size_t(cap)), "alloc srtcp ranges");
+    HIPCHK(hipMemset(nrx, 0, cap * sizeof(lkf_transport_srtcp)), "srtcp rx init");
+    if (t) {
+      HIPCHK(hipMemcpy(nck, e->dSrtcpKeys, t * sizeof(SrtpKeys), hipMemcpyDeviceToDevice), "copy srtcp keys");
+      HIPCHK(hipMemcpy(nrx, e->dSrtcpRx, t * sizeof(lkf_transport_srtcp), hipMemcpyDeviceToDevice),
+             "copy srtcp rx state");
+    }
+    rc = upload_done(e);  // (the sender stream does not order against these)
+    if (rc) return rc;
     e->dTransports = std::move(np);
     e->dSrtpKeys = std::move(nk);
+    e->dSrtcpKeys = std::move(nck);
+    e->dSrtcpRx = std::move(nrx);
+    e->dSrtcpRxSpec = std::move(nspec);
+    e->dSrtcpRange = std::move(nrange);
   }
   e->transports.push_back(*p);
   HIPCHK(hipMemcpyAsync(e->dTransports + t, &e->transports.back(), sizeof(*p), hipMemcpyHostToDevice, e->own),
          "transport copy");
-  HIPCHK(launch_srtp_keys(e->own, e->dTransports + t, t, 1, e->dAesTab, e->dSrtpKeys), "srtp keys");
+  HIPCHK(launch_srtp_keys(e->own, e->dTransports + t, t, 1, e->dAesTab, e->dSrtpKeys, 0), "srtp keys");
+  HIPCHK(launch_srtp_keys(e->own, e->dTransports + t, t, 1, e->dAesTab, e->dSrtcpKeys, 3), "srtcp keys");
   HIPCHK(hipStreamSynchronize(e->own), "srtp keys sync");
   return int32_t(t);
 }
@@ -3095,12 +3133,14 @@ static_assert(sizeof(lkf_rtcp_raw) == 12 && sizeof(lkf_rtcp_in_result) == 48 && 
 // Count pass -> scans -> the totals back on the host (the lists are sized by
 // them, never by a guess about the bytes) -> write pass -> k_rr_update on the
 // device-resident fb list -> the fold of its results into the entries.
-int lkf_rtcp_ingest(lkf_engine *e, const lkf_rtcp_raw *in, uint32_t n, const uint8_t *arena, uint64_t arena_len,
-                    int64_t now_ns, lkf_rtcp_in_result *out, lkf_rtcp_fb *fb, lkf_rtcp_fb_result *fb_out,
-                    uint32_t fb_cap, uint32_t *n_fb, lkf_rtcp_ref *refs, uint32_t ref_cap, uint32_t *n_refs,
-                    uint32_t *n_nacks) {
+// `arena`: the compound packets in host memory, uploaded first; NULL: they are
+// the arena_len bytes at dArena already (lkf_rtcp_ingest_unprotected).
+static int rtcp_ingest_run(lkf_engine *e, const lkf_rtcp_raw *in, uint32_t n, const uint8_t *arena,
+                           const uint8_t *dArena, uint64_t arena_len, int64_t now_ns, lkf_rtcp_in_result *out,
+                           lkf_rtcp_fb *fb, lkf_rtcp_fb_result *fb_out, uint32_t fb_cap, uint32_t *n_fb,
+                           lkf_rtcp_ref *refs, uint32_t ref_cap, uint32_t *n_refs, uint32_t *n_nacks) {
   if (!e || !n_fb || !n_refs || (n && (!in || !out)) || (fb_cap && (!fb || !fb_out)) || (ref_cap && !refs) ||
-      (arena_len && !arena))
+      (arena_len && !arena && !dArena))
     return LKF_EINVAL;
   *n_fb = *n_refs = 0;
   if (n_nacks) *n_nacks = 0;
@@ -3129,14 +3169,14 @@ int lkf_rtcp_ingest(lkf_engine *e, const lkf_rtcp_raw *in, uint32_t n, const uin
               want(e->dRiNackOff, n, 4096, m), want(e->dRiRes, n, 4096, m), want(e->dRiTot, 4, 4),
               want(e->dRiScan, words(n), 0, words(m)), want(e->dRiRefOff, n, 4096, m)));
   if (f.grew) HIPCHK(hipMemsetAsync(e->dRiScan, 0, e->dRiScan.cap() * sizeof(uint64_t), s), "rtcp scan state reset");
-  STEP(f.grow("alloc rtcp arena", want(e->dRiArena, arena_len, 1 << 16, 2 * arena_len)));  // (a family of its own)
+  if (arena) STEP(f.grow("alloc rtcp arena", want(e->dRiArena, arena_len, 1 << 16, 2 * arena_len)));  // (a family of its own)
   STEP(f.up(e->dRiIn, in, size_t(n) * sizeof(lkf_rtcp_raw), "rtcp raw copy"));
-  if (arena_len) STEP(f.up(e->dRiArena, arena, arena_len, "rtcp arena copy"));
+  if (arena && arena_len) STEP(f.up(e->dRiArena, arena, arena_len, "rtcp arena copy"));
   STEP(f.up(e->dRiGEntry, g.data(), g.size() * sizeof(uint32_t), "rtcp groups copy"));
   RtcpInLaunch a{};
   a.in = e->dRiIn;
   a.n = n;
-  a.arena = e->dRiArena;
+  a.arena = arena ? e->dRiArena.get() : dArena;
   a.arenaLen = arena_len;
   a.dts = e->dDTs;
   a.hot = e->dHot;
@@ -3214,6 +3254,16 @@ int lkf_rtcp_ingest(lkf_engine *e, const lkf_rtcp_raw *in, uint32_t n, const uin
   return LKF_OK;
 }
 
+int lkf_rtcp_ingest(lkf_engine *e, const lkf_rtcp_raw *in, uint32_t n, const uint8_t *arena, uint64_t arena_len,
+                    int64_t now_ns, lkf_rtcp_in_result *out, lkf_rtcp_fb *fb, lkf_rtcp_fb_result *fb_out,
+                    uint32_t fb_cap, uint32_t *n_fb, lkf_rtcp_ref *refs, uint32_t ref_cap, uint32_t *n_refs,
+                    uint32_t *n_nacks) {
+  if (arena_len && !arena) return LKF_EINVAL;
+  static const uint8_t none = 0;  // (an empty arena is still the caller's)
+  return rtcp_ingest_run(e, in, n, arena ? arena : &none, nullptr, arena_len, now_ns, out, fb, fb_out, fb_cap, n_fb, refs,
+                         ref_cap, n_refs, n_nacks);
+}
+
 int lkf_rtcp_ingested_nacks(lkf_engine *e, lkf_nack *out, uint32_t cap, uint32_t *n_out) {
   if (!e || !n_out) return LKF_EINVAL;
   *n_out = e->riNacks;
@@ -3258,6 +3308,148 @@ int lkf_rtx_lookup_ingested(lkf_engine *e, int64_t now_ns, lkf_rtx *out, uint32_
   STEP(f.up(e->dNackG, gb.data(), gb.size() * sizeof(uint32_t), "groups copy"));
   return rtx_lookup_run(f, inPlace ? e->dRiNacks.get() : e->dNacks.get(), uint32_t(keep.size()), m, now_ns, out, cap,
                         n_out);
+}
+
+// ---- SRTCP (srtp_kernels.hip k_srtcp_*; the receive steps are srtcp_device.h) ----
+static_assert(sizeof(lkf_srtcp_raw) == 12 && sizeof(lkf_srtcp_rx_result) == 16 && sizeof(lkf_rtcp_entry) == 8 &&
+                  sizeof(lkf_transport_srtcp) == 368 && sizeof(lkf_srtcp_tx_result) == 16,
+              "SRTCP records");
+
+// Control-rate, the RTCP calls' frame (Order::BehindSender).  The datagrams go
+// into the engine's own staging, padded so that the kernels' 16-B reads of a
+// datagram's last chunk stay inside it; the plaintext arena stays on the device.
+int lkf_srtcp_unprotect(lkf_engine *e, const lkf_srtcp_raw *in, uint32_t n, const uint8_t *srtcp, uint64_t srtcp_len,
+                        uint8_t *plain, lkf_srtcp_rx_result *out) {
+  if (!e || (n && (!in || !out)) || (srtcp_len && !srtcp)) return LKF_EINVAL;
+  Frame f(e, Order::BehindSender);
+  STEP(f.open());
+  e->scOff.assign(n, 0);
+  e->scLen.assign(n, 0);
+  e->scPlainLen = srtcp_len;
+  if (!n) return LKF_OK;
+  for (uint32_t i = 0; i < n; i++) e->scOff[i] = in[i].off;
+  if (e->transports.empty()) {  // every handle is unknown
+    for (uint32_t i = 0; i < n; i++) out[i] = lkf_srtcp_rx_result{0, 0, LKF_SRTCP_RX_MALFORMED, 0};
+    return LKF_OK;
+  }
+  STEP(f.grow("alloc srtcp rx scratch", want(e->dScIn, n, 4096, 2 * uint64_t(n)),
+              want(e->dScSpec, n, 4096, 2 * uint64_t(n)), want(e->dScAuth, n, 4096, 2 * uint64_t(n)),
+              want(e->dScRes, n, 4096, 2 * uint64_t(n))));
+  STEP(f.grow("alloc srtcp arenas", want(e->dScArena, srtcp_len + 64, 1 << 16, 2 * srtcp_len + 64),
+              want(e->dScPlain, srtcp_len + 64, 1 << 16, 2 * srtcp_len + 64)));
+  STEP(f.up(e->dScIn, in, size_t(n) * sizeof(lkf_srtcp_raw), "srtcp raw copy"));
+  if (srtcp_len) STEP(f.up(e->dScArena, srtcp, srtcp_len, "srtcp arena copy"));
+  SrtcpRxArgs a{};
+  a.tab = e->dAesTab;
+  a.in = e->dScIn;
+  a.n = n;
+  a.ntransports = uint32_t(e->transports.size());
+  a.srtcp = e->dScArena;
+  a.srtcpLen = srtcp_len;
+  a.plain = e->dScPlain;
+  a.rx = e->dSrtcpRx;
+  a.rxSpec = e->dSrtcpRxSpec;
+  a.range = e->dSrtcpRange;
+  a.keys = e->dSrtcpKeys;
+  a.spec = e->dScSpec;
+  a.auth = e->dScAuth;
+  a.res = e->dScRes;
+  HIPCHK(launch_srtcp_unprotect(f.s, a), "srtcp unprotect");
+  STEP(f.wait());
+  D2H(out, e->dScRes, size_t(n) * sizeof(lkf_srtcp_rx_result), "srtcp results copy");
+  if (plain && srtcp_len) D2H(plain, e->dScPlain, srtcp_len, "srtcp plaintext copy");
+  for (uint32_t i = 0; i < n; i++) e->scLen[i] = out[i].len;
+  return LKF_OK;
+}
+
+int lkf_rtcp_ingest_unprotected(lkf_engine *e, const lkf_rtcp_entry *in, uint32_t n, int64_t now_ns,
+                                lkf_rtcp_in_result *out, lkf_rtcp_fb *fb, lkf_rtcp_fb_result *fb_out, uint32_t fb_cap,
+                                uint32_t *n_fb, lkf_rtcp_ref *refs, uint32_t ref_cap, uint32_t *n_refs,
+                                uint32_t *n_nacks) {
+  if (!e || (n && !in)) return LKF_EINVAL;
+  std::vector<lkf_rtcp_raw> raw(n);
+  for (uint32_t i = 0; i < n; i++) {
+    if (in[i].dgram >= e->scOff.size()) return LKF_EINVAL;
+    const uint32_t len = e->scLen[in[i].dgram];  // (a rejected datagram: an empty entry at the arena's start)
+    raw[i] = lkf_rtcp_raw{in[i].dt, len ? e->scOff[in[i].dgram] : 0u, len};
+  }
+  static const uint8_t none = 0;  // (no datagram was accepted yet: every entry has len 0)
+  const uint8_t *host = e->dScPlain ? nullptr : &none;
+  return rtcp_ingest_run(e, raw.data(), n, host, e->dScPlain, host ? 0 : e->scPlainLen, now_ns, out, fb, fb_out, fb_cap,
+                         n_fb, refs, ref_cap, n_refs, n_nacks);
+}
+
+int lkf_transport_srtcp_get(lkf_engine *e, int32_t transport, lkf_transport_srtcp *out) {
+  if (!e || !out || transport < 0 || transport >= int32_t(e->transports.size())) return LKF_EINVAL;
+  STEP(quiesce(e, false));
+  D2H(out, e->dSrtcpRx + transport, sizeof(*out), "srtcp rx state copy");
+  return LKF_OK;
+}
+
+int lkf_srtcp_reset(lkf_engine *e, int32_t transport) {
+  if (!e || transport < 0 || transport >= int32_t(e->transports.size())) return LKF_EINVAL;
+  STEP(quiesce(e, false));
+  HIPCHK(hipMemset(e->dSrtcpRx + transport, 0, sizeof(lkf_transport_srtcp)), "srtcp rx reset");
+  e->scTxIndex.erase(e->scTxIndex.lower_bound({transport, 0u}), e->scTxIndex.upper_bound({transport, 0xffffffffu}));
+  return upload_done(e);
+}
+
+// The index counters live here: the input is trusted and host-resident, and a
+// call that fails its checks must consume none.
+int lkf_srtcp_protect(lkf_engine *e, const lkf_srtcp_raw *in, uint32_t n, const uint8_t *plain, uint64_t plain_len,
+                      uint8_t *out, uint64_t out_cap, lkf_srtcp_tx_result *res, uint64_t *out_len) {
+  if (!e || (n && (!in || !plain || !res))) return LKF_EINVAL;
+  uint64_t total = 0;
+  for (uint32_t i = 0; i < n; i++) {
+    if (in[i].transport < 0 || in[i].transport >= int32_t(e->transports.size()) || in[i].len < 8 ||
+        uint64_t(in[i].off) + in[i].len > plain_len || (plain[in[i].off] >> 6) != 2)
+      return LKF_EINVAL;
+    total += (uint64_t(in[i].len) + 20 + 15) & ~15ull;
+  }
+  if (out_len) *out_len = total;
+  if (total > 0xffffffffull) return LKF_EINVAL;
+  if (total > out_cap || (total && !out)) return LKF_ENOSPC;
+  if (!n) return LKF_OK;
+  // the plaintext laid out where the protected packets go, zeros between
+  std::vector<uint8_t> stage(total, 0);
+  std::vector<SrtcpTx> tx(n);
+  uint64_t off = 0;
+  for (uint32_t i = 0; i < n; i++) {
+    const uint8_t *p = plain + in[i].off;
+    std::memcpy(stage.data() + off, p, in[i].len);
+    const uint32_t ssrc = (uint32_t(p[4]) << 24) | (uint32_t(p[5]) << 16) | (uint32_t(p[6]) << 8) | p[7];
+    uint32_t &idx = e->scTxIndex[{in[i].transport, ssrc}];
+    idx = (idx + 1) & 0x7fffffffu;  // pion's srtcpIndex++ before use
+    const bool gcm = e->transports[size_t(in[i].transport)].profile == LKF_SRTP_AEAD_AES_128_GCM;
+    tx[i] = SrtcpTx{uint32_t(in[i].transport), uint32_t(off), in[i].len, idx};
+    res[i] = lkf_srtcp_tx_result{ssrc, idx, uint32_t(off), in[i].len + (gcm ? 20u : 14u)};
+    off += (uint64_t(in[i].len) + 20 + 15) & ~15ull;
+  }
+  Frame f(e, Order::BehindSender);
+  STEP(f.open());
+  STEP(f.grow("alloc srtcp tx scratch", want(e->dScTx, n, 1024, 2 * uint64_t(n)),
+              want(e->dScTxIn, total, 1 << 16, 2 * total), want(e->dScTxOut, total, 1 << 16, 2 * total)));
+  STEP(f.up(e->dScTx, tx.data(), size_t(n) * sizeof(SrtcpTx), "srtcp tx copy"));
+  STEP(f.up(e->dScTxIn, stage.data(), total, "srtcp plaintext copy"));
+  HIPCHK(hipMemsetAsync(e->dScTxOut, 0, total, f.s), "srtcp out clear");  // (the slack behind each packet reads 0)
+  SrtcpTxArgs a{};
+  a.tab = e->dAesTab;
+  a.pk = e->dScTx;
+  a.n = n;
+  a.src = e->dScTxIn;
+  a.dst = e->dScTxOut;
+  a.keys = e->dSrtcpKeys;
+  HIPCHK(launch_srtcp_protect(f.s, a), "srtcp protect");
+  STEP(f.wait());  // (also: the pageable uploads above have left the host vectors)
+  D2H(out, e->dScTxOut, total, "srtcp protected copy");
+  return LKF_OK;
+}
+
+int lkf_srtcp_tx_index(lkf_engine *e, int32_t transport, uint32_t ssrc, uint32_t *index) {
+  if (!e || !index || transport < 0 || transport >= int32_t(e->transports.size())) return LKF_EINVAL;
+  const auto it = e->scTxIndex.find({transport, ssrc});
+  *index = it == e->scTxIndex.end() ? 0 : it->second;
+  return LKF_OK;
 }
 
 static int rtx_emit_common(Frame &f, const lkf_rtx *rtx, uint32_t n, const uint8_t *srcArena,

@@ -5,6 +5,7 @@
 
 #include "../../include/lkfwd.h"
 #include "fwd_state.h"
+#include "srtcp_device.h"
 #include "srtp_rx_device.h"
 
 namespace lkf {
@@ -331,8 +332,9 @@ struct SrtpProtectArgs {
   uint32_t absVal;   // abs-send-time, 24 bits
 };
 hipError_t launch_aes_tables(hipStream_t s, uint32_t *tab);
+// labelBase: 0 for the SRTP session keys (labels 0, 1, 2), 3 for the SRTCP ones (3, 4, 5)
 hipError_t launch_srtp_keys(hipStream_t s, const lkf_transport_params *in, uint32_t first, uint32_t n,
-                            const uint32_t *tab, SrtpKeys *keys);
+                            const uint32_t *tab, SrtpKeys *keys, uint32_t labelBase);
 hipError_t launch_srtp_protect(hipStream_t s, const SrtpProtectArgs &a, uint32_t ndts, const uint32_t *perm,
                                const uint64_t *recBase, const uint32_t *fwdCnt);
 
@@ -360,6 +362,37 @@ struct SrtpRxArgs {  // the three kernels' arguments
   lkf_srtp_rx_result *res;
 };
 hipError_t launch_srtp_unprotect(hipStream_t s, const SrtpRxArgs &a);
+
+// ---- SRTCP (srtp_kernels.hip; the receive steps are srtcp_device.h) ----
+struct SrtcpRxArgs {  // the receive kernels' arguments
+  const uint32_t *tab;  // AES te[256] + S-box
+  const lkf_srtcp_raw *in;
+  uint32_t n;
+  uint32_t ntransports;
+  const uint8_t *srtcp;  // 16-B aligned, readable to the next multiple of 16 past srtcpLen
+  uint64_t srtcpLen;
+  uint8_t *plain;               // srtcpLen bytes
+  lkf_transport_srtcp *rx;      // per transport: the committed slot table and counters
+  lkf_transport_srtcp *rxSpec;  // per transport: the table if every checked datagram authenticates
+  uint32_t *range;              // per transport: first datagram of the call, ~last (0xffffffff each: none)
+  const SrtpKeys *keys;         // the SRTCP session keys (labels 3, 4, 5)
+  lkf_srtcp_rx_result *spec;    // per datagram: ssrc, index and the verdict before authentication
+  uint32_t *auth;               // per datagram: 1 = the tag matched
+  lkf_srtcp_rx_result *res;
+};
+hipError_t launch_srtcp_unprotect(hipStream_t s, const SrtcpRxArgs &a);
+struct SrtcpTx {  // one packet to protect: plaintext at src + off, protected packet at dst + off
+  uint32_t transport, off, len, index;
+};
+struct SrtcpTxArgs {
+  const uint32_t *tab;
+  const SrtcpTx *pk;
+  uint32_t n;
+  const uint8_t *src;  // 16-B aligned slots of (len + 20 + 15) & ~15 bytes, zero after the plaintext
+  uint8_t *dst;
+  const SrtpKeys *keys;
+};
+hipError_t launch_srtcp_protect(hipStream_t s, const SrtcpTxArgs &a);
 
 hipError_t launch_seq_lookup(hipStream_t s, DTHot *hot, SeqMeta *seq, uint32_t seqSize, uint8_t *srm,
                              uint64_t srmStride, uint32_t srmCap, uint32_t d,

@@ -26,7 +26,9 @@
 //                  per 64 B), not HBM-bound.
 // The receive direction (unprotect in front of ingress: k_srtp_rx_index,
 // k_srtp_unprotect, k_srtp_rx_commit) follows the protect kernel below and
-// shares its AES, SHA-1 and GHASH code.
+// shares its AES, SHA-1 and GHASH code.  SRTCP in both directions (k_srtcp_*,
+// at the end of the file) is the same code on the SRTCP framing, under a second
+// key set that k_srtp_keys derives with label base 3.
 // =============================================================================
 #include <hip/hip_runtime.h>
 
@@ -177,7 +179,7 @@ __device__ __forceinline__ u32 be32(const u8 *p) {
 }
 
 __global__ void k_srtp_keys(const lkf_transport_params *__restrict__ in, u32 first, u32 n, const u32 *__restrict__ tab,
-                            SrtpKeys *__restrict__ keys) {
+                            SrtpKeys *__restrict__ keys, u32 labelBase) {
   const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const lkf_transport_params &p = in[i];
@@ -202,10 +204,10 @@ __global__ void k_srtp_keys(const lkf_transport_params *__restrict__ in, u32 fir
     aes_encrypt(t, mrk, out[0], out[1], out[2], out[3]);
   };
   u32 sk[4], a0[4], a1[4], sl[4];
-  derive(0, 0, sk);
-  derive(1, 0, a0);
-  derive(1, 1, a1);
-  derive(2, 0, sl);
+  derive(labelBase, 0, sk);  // labels 0, 1, 2: SRTP; 3, 4, 5: SRTCP (RFC 3711 §4.3.2)
+  derive(labelBase + 1, 0, a0);
+  derive(labelBase + 1, 1, a1);
+  derive(labelBase + 2, 0, sl);
   SrtpKeys &K = keys[first + i];
   u32 rk[44];
   aes_expand(t, sk, rk);
@@ -1062,6 +1064,433 @@ __global__ void __launch_bounds__(64) k_srtp_rx_commit(SrtpRxArgs A) {
   if (lane == 0) A.rx[s] = st;
 }
 
+// ---- SRTCP ---------------------------------------------------------------------
+// include/lkfwd.h "SRTCP": the same AES, SHA-1 and GHASH code on the SRTCP
+// framing.  Against the SRTP helpers above: the clear header is a fixed 8 bytes
+// (two words), the SSRC is word 1, the counter's last word and the GCM IV come
+// from the explicit 31-bit index, the AES-CM HMAC covers the E || index word
+// after the encrypted region and appends nothing, and the GCM AAD is 12 bytes
+// whose last word sits after the tag.  An SRTCP datagram need not be a multiple
+// of 4 bytes long (a forged one), so the encrypted region's last word is masked
+// by bytes.  One function per profile serves both directions (SEAL: protect).
+//   k_srtcp_rx_range   one lane per datagram: each transport's first and last
+//                      datagram of the call
+//   k_srtcp_rx_index   one wave per transport with datagrams, 64 at a time: the
+//                      slot table one slot per lane, the lookup a compare and
+//                      ballot, under the speculation that every checked
+//                      datagram authenticates
+//   k_srtcp_unprotect  one lane per datagram that parsed with E set, whatever
+//                      its replay verdict (the index is in the packet: the
+//                      crypto result never depends on the state)
+//   k_srtcp_rx_commit  one wave per transport: the speculated table adopted, or
+//                      the same walk again with the true outcomes
+//   k_srtcp_protect    one lane per packet
+using srtcp::Slot;
+
+// Message words of block b of the inner HMAC from the 64 bytes `ch` of the
+// packet: pkt[0 : M] || 0x80 || 0... (the length goes into the last block's
+// words 14 and 15 at the caller)
+__device__ __forceinline__ void srtcp_hmac_words(const uint4 ch[4], u32 b, u32 M, u32 W[16]) {
+#pragma unroll
+  for (int j = 0; j < 16; j++) {
+    const u32 v = (j & 3) == 0 ? ch[j >> 2].x : (j & 3) == 1 ? ch[j >> 2].y : (j & 3) == 2 ? ch[j >> 2].z : ch[j >> 2].w;
+    const long long dlt = (long long)M - 4ll * (16ll * b + j);
+    if (dlt >= 4)
+      W[j] = bswap(v);
+    else if (dlt > 0)
+      W[j] = (bswap(v) & (0xFFFFFFFFu << (8 * (4 - int(dlt))))) | (0x80000000u >> (8 * int(dlt)));
+    else
+      W[j] = dlt == 0 ? 0x80000000u : 0u;
+  }
+}
+
+// AES_CM_128_HMAC_SHA1_80 of one SRTCP packet whose header and body are E bytes.
+// Open: src holds E + 14 bytes, the plaintext (E bytes) is written either way,
+// true if the tag matches.  Seal: src holds the E plaintext bytes followed by
+// zeros, dst receives E + 14 bytes.
+template <bool SEAL, class Tab>
+__device__ bool srtcp_cm(const Tab &tb, const SrtpKeys *K, const u8 *srcB, u8 *dstB, u32 E, u32 index) {
+  const uint4 *src = reinterpret_cast<const uint4 *>(srcB);
+  const RkG rk{K->rk};
+  const u32 M = E + 4;  // the authenticated portion: header, body, E || index
+  const u32 trailer = bswap(0x80000000u | index);  // as a little-endian load sees it
+  const u32 ssrc = bswap(src[0].y);
+  const u32 ctr0 = K->salt[0], ctr1 = K->salt[1] ^ ssrc, ctr2 = K->salt[2] ^ (index >> 16),
+            ctr3 = K->salt[3] ^ (index << 16);
+  u32 hs[5];
+  for (int k = 0; k < 5; k++) hs[k] = K->ih[k];
+  // keystream window: slot 4k + w = word w of AES block blk0 + k; message word j
+  // of a block reads slot j + 2 (byte 8 is keystream byte 0)
+  int blk0 = -1;
+  u32 win[20];
+#pragma unroll
+  for (int k = 0; k < 4; k++) win[k] = 0;
+  const u64 bits = (64 + u64(M)) * 8;
+  const u32 nb = u32((u64(M) + 9 + 63) / 64);
+  const u32 inLen = SEAL ? E : M, outLen = SEAL ? M : E;
+  for (u32 b = 0; b < nb; b++) {
+    uint4 ch[4];
+#pragma unroll
+    for (int c = 0; c < 4; c++) ch[c] = (64 * b + 16 * c < inLen) ? src[4 * b + c] : make_uint4(0, 0, 0, 0);
+#pragma unroll
+    for (int k = 1; k <= 4; k++) {
+      u32 a0 = ctr0, a1 = ctr1, a2 = ctr2, a3 = ctr3 + u32(blk0 + k);
+      aes_encrypt(tb, rk, a0, a1, a2, a3);
+      win[4 * k] = a0;
+      win[4 * k + 1] = a1;
+      win[4 * k + 2] = a2;
+      win[4 * k + 3] = a3;
+    }
+    u32 W[16];
+    if (!SEAL) srtcp_hmac_words(ch, b, M, W);  // over the ciphertext as loaded
+#pragma unroll
+    for (int j = 0; j < 16; j++) {
+      u32 &v = (j & 3) == 0 ? ch[j >> 2].x : (j & 3) == 1 ? ch[j >> 2].y : (j & 3) == 2 ? ch[j >> 2].z : ch[j >> 2].w;
+      const u32 p = 4 * (16 * b + u32(j));
+      if (p >= 8 && p < E) {
+        u32 ks = bswap(win[j + 2]);
+        if (E - p < 4) ks &= (1u << (8 * (E - p))) - 1;
+        v ^= ks;
+      }
+      if (SEAL) {  // E || index after the body, at any byte alignment
+        const int d = int(p) - int(E);
+        if (d == 0)
+          v = trailer;
+        else if (d < 0 && d > -4)
+          v = (v & ((1u << (8 * -d)) - 1)) | (trailer << (8 * -d));
+        else if (d > 0 && d < 4)
+          v = trailer >> (8 * d);
+      }
+    }
+    if (SEAL) srtcp_hmac_words(ch, b, M, W);
+    if (b == nb - 1) {
+      W[14] = u32(bits >> 32);
+      W[15] = u32(bits);
+    }
+#pragma unroll
+    for (int c = 0; c < 4; c++) {
+      const u32 base = 64 * b + 16 * c;
+      if (base < outLen) store_chunk(dstB, base, ch[c], outLen - base);
+    }
+    sha1_block(hs, W);
+#pragma unroll
+    for (int k = 0; k < 4; k++) win[k] = win[16 + k];
+    blk0 += 4;
+  }
+  u32 ho[5] = {K->oh[0], K->oh[1], K->oh[2], K->oh[3], K->oh[4]};
+  {
+    u32 w[16] = {hs[0], hs[1], hs[2], hs[3], hs[4], 0x80000000u, 0, 0, 0, 0, 0, 0, 0, 0, 0, (64 + 20) * 8};
+    sha1_block(ho, w);
+  }
+  u32 diff = 0;
+#pragma unroll
+  for (int k = 0; k < 10; k++) {
+    const u32 t = (ho[k / 4] >> (24 - 8 * (k & 3))) & 255;
+    if (SEAL)
+      dstB[M + k] = u8(t);
+    else
+      diff |= u32(srcB[M + k]) ^ t;
+  }
+  return diff == 0;
+}
+
+struct SrtcpGcmDefer {  // a GCM packet's GHASH inputs, carried from the CTR pass
+  const u8 *p;  // where header and ciphertext are read: the received datagram, or the sealed output
+  u32 E;        // header + ciphertext bytes; the tag follows, then the trailer word
+  u32 trailer;  // E || index
+  u32 key;
+  u32 ej[4];  // E(K, J0)
+};
+
+// AEAD_AES_128_GCM of one SRTCP packet, CTR half: IV = (00 00 || SSRC || 00 00 ||
+// index) XOR salt, counter blocks IV || 2, 3, .. from byte 8.  Writes the E
+// bytes (and, sealing, the trailer word behind the tag's place); the tag is
+// srtcp_ghash_wave's.
+template <bool SEAL, class Tab>
+__device__ void srtcp_gcm_ctr(const Tab &tb, const SrtpKeys *K, const u8 *srcB, u8 *dstB, u32 E, u32 index,
+                              SrtcpGcmDefer &g) {
+  const uint4 *src = reinterpret_cast<const uint4 *>(srcB);
+  const RkG rk{K->rk};
+  const u32 ssrc = bswap(src[0].y);
+  const u32 iv0 = (ssrc >> 16) ^ K->salt[0], iv1 = (ssrc << 16) ^ K->salt[1], iv2 = index ^ K->salt[2];
+  u32 win[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // the previous keystream block, then chunk c's (word j reads slot j + 2)
+  const u32 nch = (E + 15) / 16;
+  for (u32 c = 0; c < nch; c++) {
+#pragma unroll
+    for (int k = 0; k < 4; k++) win[k] = win[4 + k];
+    u32 a0 = iv0, a1 = iv1, a2 = iv2, a3 = 2 + c;
+    aes_encrypt(tb, rk, a0, a1, a2, a3);
+    win[4] = a0, win[5] = a1, win[6] = a2, win[7] = a3;
+    uint4 ch = src[c];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      u32 &v = j == 0 ? ch.x : j == 1 ? ch.y : j == 2 ? ch.z : ch.w;
+      const u32 p = 16 * c + 4 * u32(j);
+      if (p >= 8 && p < E) {
+        u32 ks = bswap(win[j + 2]);
+        if (E - p < 4) ks &= (1u << (8 * (E - p))) - 1;
+        v ^= ks;
+      }
+    }
+    store_chunk(dstB, 16 * c, ch, E - 16 * c);
+  }
+  u32 e0 = iv0, e1 = iv1, e2 = iv2, e3 = 1u;  // E(K, J0)
+  aes_encrypt(tb, rk, e0, e1, e2, e3);
+  g.p = SEAL ? dstB : srcB;
+  g.E = E;
+  g.trailer = 0x80000000u | index;
+  g.ej[0] = e0, g.ej[1] = e1, g.ej[2] = e2, g.ej[3] = e3;
+  if (SEAL)
+    for (int k = 0; k < 4; k++) dstB[E + 16 + k] = u8(g.trailer >> (24 - 8 * k));
+}
+
+// GHASH(H, A = header || trailer, C) of the wave's deferred SRTCP packets, one
+// transport's table at a time as gcm_ghash_wave; the tag E(K, J0) ^ S written
+// after the ciphertext (SEAL) or compared with the 16 bytes there (true: it
+// matches).  Every lane of the wave calls it.
+template <bool SEAL>
+__device__ bool srtcp_ghash_wave(const SrtpKeys *keys, const SrtcpGcmDefer &g, bool on, uint4 *M, const u32 *L4) {
+  const u32 lane = threadIdx.x & 63;
+  u64 pend = __ballot(on);
+  bool ok = false;
+  while (pend) {
+    const u32 key = __shfl(g.key, __ffsll((long long)pend) - 1);
+    if (lane < 16) {  // this transport's table: lane n builds M[n]
+      const SrtpKeys &K = keys[key];
+      u32 b[4] = {K.ih[0], K.ih[1], K.ih[2], K.ih[3]};  // H = M[8]
+      u32 m[4] = {0, 0, 0, 0};
+#pragma unroll
+      for (int bit = 3; bit >= 0; bit--) {
+        if ((lane >> bit) & 1) m[0] ^= b[0], m[1] ^= b[1], m[2] ^= b[2], m[3] ^= b[3];
+        const u32 r = 0xE1000000u & (0u - (b[3] & 1u));  // * x
+        b[3] = (b[3] >> 1) | (b[2] << 31);
+        b[2] = (b[2] >> 1) | (b[1] << 31);
+        b[1] = (b[1] >> 1) | (b[0] << 31);
+        b[0] = (b[0] >> 1) ^ r;
+      }
+      M[lane] = make_uint4(m[0], m[1], m[2], m[3]);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    const bool mine = on && g.key == key;
+    if (mine) {
+      const u32 *ow = reinterpret_cast<const u32 *>(g.p);
+      const u32 lc = g.E - 8;  // ciphertext bytes
+      u32 y[4] = {bswap(ow[0]), bswap(ow[1]), g.trailer, 0};
+      gf_mul_tab(y, M, L4);
+      for (u32 blk = 0; 16 * blk < lc; blk++) {
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+          const int left = int(lc) - int(16 * blk + 4 * j);  // bytes of this word inside the ciphertext
+          const u32 v = left > 0 ? bswap(ow[2 + 4 * blk + j]) : 0u;
+          y[j] ^= left >= 4 ? v : left > 0 ? (v & (0xFFFFFFFFu << (8 * (4 - left)))) : 0u;
+        }
+        gf_mul_tab(y, M, L4);
+      }
+      y[1] ^= 96u;  // len(A) || len(C) in bits
+      y[3] ^= 8u * lc;
+      gf_mul_tab(y, M, L4);
+      u32 diff = 0;
+#pragma unroll
+      for (int k = 0; k < 16; k++) {
+        const u32 t = ((g.ej[k / 4] ^ y[k / 4]) >> (24 - 8 * (k & 3))) & 255;
+        if (SEAL)
+          const_cast<u8 *>(g.p)[g.E + k] = u8(t);
+        else
+          diff |= u32(g.p[g.E + k]) ^ t;
+      }
+      ok = diff == 0;
+    }
+    pend &= ~__ballot(mine);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // table reads done before the next rebuild
+    __builtin_amdgcn_wave_barrier();
+  }
+  return ok;
+}
+
+__global__ void k_srtcp_rx_range(SrtcpRxArgs A) {
+  const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= A.n) return;
+  const u32 t = u32(A.in[i].transport);
+  if (t >= A.ntransports) return;
+  atomicMin(A.range + 2 * t, i);
+  atomicMin(A.range + 2 * t + 1, ~i);
+}
+
+// the datagram range [lo, hi) of transport `t` in the call; false: none
+__device__ __forceinline__ bool srtcp_range(const SrtcpRxArgs &A, u32 t, u32 &lo, u32 &hi) {
+  if (t >= A.ntransports) return false;
+  lo = A.range[2 * t];
+  if (lo == 0xffffffffu) return false;
+  hi = ~A.range[2 * t + 1] + 1;
+  return hi <= A.n;
+}
+
+// Steps 1 to 6 over transport t's datagrams of [lo, hi) in order, from the
+// committed table: lane s < 16 holds slot s, lane c < 6 counter c.  AUTHED: with
+// the authentication outcomes of k_srtcp_unprotect, results to A.res and the
+// table to A.rx; otherwise every checked datagram taken to authenticate,
+// verdicts to A.spec and the table to A.rxSpec.
+template <bool AUTHED>
+__device__ void srtcp_walk(const SrtcpRxArgs &A, u32 t, u32 lo, u32 hi) {
+  const u32 lane = threadIdx.x;
+  const lkf_transport_srtcp &T0 = A.rx[t];
+  lkf_transport_srtcp &T1 = AUTHED ? A.rx[t] : A.rxSpec[t];
+  Slot sl{0, 0, 0, 0};
+  if (lane < srtcp::kSlots) sl = Slot{T0.in_use[lane], T0.ssrc[lane], T0.latest[lane], T0.mask[lane]};
+  u64 cnt = lane < 6 ? (&T0.accepted)[lane] : 0;
+  const u32 tag = rx_tag_len(A.keys + t);
+  for (u32 base = lo; base < hi; base += 64) {
+    const u32 i = base + lane;
+    bool mine = false;
+    srtcp::Parsed pr{LKF_SRTCP_RX_MALFORMED, 0, 0};
+    u32 au = 1, len = 0;
+    if (i < hi) {
+      const lkf_srtcp_raw rp = A.in[i];
+      mine = u32(rp.transport) == t;
+      if (mine) {
+        pr = srtcp::parse(A.srtcp, A.srtcpLen, rp.off, rp.len, tag);
+        len = rp.len;
+        if (AUTHED) au = A.auth[i];
+      }
+    }
+    u64 m = __ballot(mine);
+    u32 mySt = LKF_SRTCP_RX_MALFORMED;
+    while (m) {  // the transport's datagrams of this chunk, in order (wave-uniform)
+      const u32 k = u32(__ffsll((long long)m)) - 1;
+      m &= m - 1;
+      const u32 ssrc = __shfl(pr.ssrc, k), index = __shfl(pr.index, k);
+      u32 stt = __shfl(pr.st, k);
+      if (stt == LKF_SRTCP_RX_OK) {
+        const u64 hit = __ballot(lane < srtcp::kSlots && sl.inUse && sl.ssrc == ssrc);
+        const u64 fre = __ballot(lane < srtcp::kSlots && !sl.inUse);
+        const bool found = hit != 0;
+        const u32 slot = found ? u32(__ffsll((long long)hit)) - 1 : fre ? u32(__ffsll((long long)fre)) - 1 : 0;
+        const u32 latest = __shfl(sl.latest, slot);
+        const u64 mask = (u64(__shfl(u32(sl.mask >> 32), slot)) << 32) | __shfl(u32(sl.mask), slot);
+        stt = srtcp::check(found, fre != 0, latest, mask, index);
+        if (stt == LKF_SRTCP_RX_OK && !__shfl(au, k)) stt = LKF_SRTCP_RX_AUTH;
+        if (stt == LKF_SRTCP_RX_OK && lane == slot) srtcp::accept(sl, found, ssrc, index);
+      }
+      if (lane == srtcp::counter_of(stt)) cnt++;
+      if (lane == k) mySt = stt;
+    }
+    if (mine) {
+      if (AUTHED)
+        A.res[i] = lkf_srtcp_rx_result{pr.ssrc, pr.index, mySt, mySt == LKF_SRTCP_RX_OK ? len - 4 - tag : 0u};
+      else
+        A.spec[i] = lkf_srtcp_rx_result{pr.ssrc, pr.index, mySt, 0};
+    }
+  }
+  if (lane < srtcp::kSlots) {
+    T1.in_use[lane] = sl.inUse;
+    T1.ssrc[lane] = sl.ssrc;
+    T1.latest[lane] = sl.latest;
+    T1.mask[lane] = sl.mask;
+  }
+  if (lane < 6) (&T1.accepted)[lane] = cnt;
+}
+
+__global__ void __launch_bounds__(64) k_srtcp_rx_index(SrtcpRxArgs A) {
+  u32 lo, hi;
+  if (srtcp_range(A, blockIdx.x, lo, hi)) srtcp_walk<false>(A, blockIdx.x, lo, hi);
+}
+
+__global__ void __launch_bounds__(SRTP_T) k_srtcp_unprotect(SrtcpRxArgs A) {
+  __shared__ u32 sTe[256 * 32];
+  __shared__ uint4 sGt[SRTP_T / 64][16];  // per-wave GHASH table
+  __shared__ u32 sL4[16];
+  const u32 tid = threadIdx.x;
+  for (u32 k = tid; k < 256 * 32; k += SRTP_T) sTe[k] = A.tab[k >> 5];
+  if (tid < 16)
+    sL4[tid] = ((tid & 1) ? 0x1C20u : 0u) ^ ((tid & 2) ? 0x3840u : 0u) ^ ((tid & 4) ? 0x7080u : 0u) ^
+               ((tid & 8) ? 0xE100u : 0u);
+  __syncthreads();
+  const u32 i = blockIdx.x * SRTP_T + tid;
+  const AesLds tb{sTe, tid & 31};
+  lkf_srtcp_raw rp{};
+  lkf_srtcp_rx_result sp{0, 0, LKF_SRTCP_RX_MALFORMED, 0};
+  if (i < A.n) {
+    rp = A.in[i];
+    if (u32(rp.transport) < A.ntransports) sp = A.spec[i];
+  }
+  // replay- and slot-rejected datagrams are opened as well (their verdict
+  // stands): should an earlier datagram fail to authenticate, the commit walk
+  // may reach step 5 with them
+  const bool crypt = sp.status != LKF_SRTCP_RX_MALFORMED && sp.status != LKF_SRTCP_RX_UNENCRYPTED;
+  SrtcpGcmDefer g{};
+  bool ok = false, gcm = false;
+  u32 tag = 0;
+  if (crypt) {
+    const SrtpKeys *K = A.keys + rp.transport;
+    tag = rx_tag_len(K);
+    const u32 E = rp.len - 4 - tag;
+    if (tag == 16) {
+      srtcp_gcm_ctr<false>(tb, K, A.srtcp + rp.off, A.plain + rp.off, E, sp.index, g);
+      g.key = u32(rp.transport);
+      gcm = true;
+    } else {
+      ok = srtcp_cm<false>(tb, K, A.srtcp + rp.off, A.plain + rp.off, E, sp.index);
+    }
+  }
+  const bool gok = srtcp_ghash_wave<false>(A.keys, g, gcm, sGt[tid >> 6], sL4);
+  if (i >= A.n) return;
+  if (gcm) ok = gok;
+  if (crypt) {
+    A.auth[i] = ok ? 1u : 0u;
+    if (!ok && sp.status == LKF_SRTCP_RX_OK) sp.status = LKF_SRTCP_RX_AUTH;
+  }
+  sp.len = sp.status == LKF_SRTCP_RX_OK ? rp.len - 4 - tag : 0u;
+  A.res[i] = sp;
+}
+
+__global__ void __launch_bounds__(64) k_srtcp_rx_commit(SrtcpRxArgs A) {
+  const u32 t = blockIdx.x, lane = threadIdx.x;
+  u32 lo, hi;
+  if (!srtcp_range(A, t, lo, hi)) return;
+  bool fail = false;
+  for (u32 base = lo; base < hi; base += 64) {
+    const u32 i = base + lane;
+    if (i < hi && u32(A.in[i].transport) == t && A.spec[i].status == LKF_SRTCP_RX_OK && !A.auth[i]) fail = true;
+  }
+  if (__ballot(fail) == 0) {  // the speculation held
+    const u32 *s = reinterpret_cast<const u32 *>(A.rxSpec + t);
+    u32 *d = reinterpret_cast<u32 *>(A.rx + t);
+    for (u32 k = lane; k < sizeof(lkf_transport_srtcp) / 4; k += 64) d[k] = s[k];
+    return;
+  }
+  srtcp_walk<true>(A, t, lo, hi);  // a failed authentication: the walk with the true outcomes
+}
+
+__global__ void __launch_bounds__(SRTP_T) k_srtcp_protect(SrtcpTxArgs A) {
+  __shared__ u32 sTe[256 * 32];
+  __shared__ uint4 sGt[SRTP_T / 64][16];  // per-wave GHASH table
+  __shared__ u32 sL4[16];
+  const u32 tid = threadIdx.x;
+  for (u32 k = tid; k < 256 * 32; k += SRTP_T) sTe[k] = A.tab[k >> 5];
+  if (tid < 16)
+    sL4[tid] = ((tid & 1) ? 0x1C20u : 0u) ^ ((tid & 2) ? 0x3840u : 0u) ^ ((tid & 4) ? 0x7080u : 0u) ^
+               ((tid & 8) ? 0xE100u : 0u);
+  __syncthreads();
+  const u32 i = blockIdx.x * SRTP_T + tid;
+  const AesLds tb{sTe, tid & 31};
+  SrtcpGcmDefer g{};
+  bool gcm = false;
+  if (i < A.n) {
+    const SrtcpTx pk = A.pk[i];
+    const SrtpKeys *K = A.keys + pk.transport;
+    if (K->profile == LKF_SRTP_AEAD_AES_128_GCM) {
+      srtcp_gcm_ctr<true>(tb, K, A.src + pk.off, A.dst + pk.off, pk.len, pk.index, g);
+      g.key = pk.transport;
+      gcm = true;
+    } else {
+      srtcp_cm<true>(tb, K, A.src + pk.off, A.dst + pk.off, pk.len, pk.index);
+    }
+  }
+  srtcp_ghash_wave<true>(A.keys, g, gcm, sGt[tid >> 6], sL4);
+}
+
 }  // namespace
 
 hipError_t launch_aes_tables(hipStream_t s, uint32_t *tab) {
@@ -1070,9 +1499,9 @@ hipError_t launch_aes_tables(hipStream_t s, uint32_t *tab) {
 }
 
 hipError_t launch_srtp_keys(hipStream_t s, const lkf_transport_params *in, uint32_t first, uint32_t n,
-                            const uint32_t *tab, SrtpKeys *keys) {
+                            const uint32_t *tab, SrtpKeys *keys, uint32_t labelBase) {
   if (!n) return hipSuccess;
-  hipLaunchKernelGGL(k_srtp_keys, dim3((n + 63) / 64), dim3(64), 0, s, in, first, n, tab, keys);
+  hipLaunchKernelGGL(k_srtp_keys, dim3((n + 63) / 64), dim3(64), 0, s, in, first, n, tab, keys, labelBase);
   return hipGetLastError();
 }
 
@@ -1094,6 +1523,25 @@ hipError_t launch_srtp_unprotect(hipStream_t s, const SrtpRxArgs &a) {
   }
   hipLaunchKernelGGL(k_srtp_unprotect, dim3((a.n + SRTP_T - 1) / SRTP_T), dim3(SRTP_T), 0, s, a);
   if (a.nstreams) hipLaunchKernelGGL(k_srtp_rx_commit, dim3(a.nstreams), dim3(64), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_srtcp_unprotect(hipStream_t s, const SrtcpRxArgs &a) {
+  if (!a.n) return hipSuccess;
+  if (a.ntransports) {
+    const hipError_t r = hipMemsetAsync(a.range, 0xff, sizeof(u32) * 2 * a.ntransports, s);
+    if (r != hipSuccess) return r;
+    hipLaunchKernelGGL(k_srtcp_rx_range, dim3((a.n + 255) / 256), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_srtcp_rx_index, dim3(a.ntransports), dim3(64), 0, s, a);
+  }
+  hipLaunchKernelGGL(k_srtcp_unprotect, dim3((a.n + SRTP_T - 1) / SRTP_T), dim3(SRTP_T), 0, s, a);
+  if (a.ntransports) hipLaunchKernelGGL(k_srtcp_rx_commit, dim3(a.ntransports), dim3(64), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_srtcp_protect(hipStream_t s, const SrtcpTxArgs &a) {
+  if (!a.n) return hipSuccess;
+  hipLaunchKernelGGL(k_srtcp_protect, dim3((a.n + SRTP_T - 1) / SRTP_T), dim3(SRTP_T), 0, s, a);
   return hipGetLastError();
 }
 
