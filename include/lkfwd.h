@@ -1479,8 +1479,9 @@ typedef struct lkf_rtcp_entry { /* one handleRTCP call on DownTrack dt with data
  * device: entry i is the whole plaintext of datagram in[i].dgram (a rejected
  * datagram is an entry of len 0, LKF_RTCP_IN_MALFORMED by the rule above);
  * several entries may name one datagram.  Which DownTracks a decrypted
- * compound addresses (pion's DestinationSSRC) is the host's to decide between
- * the two calls.  The grouping rule, the outputs and the error codes are
+ * compound addresses (pion's DestinationSSRC) lkf_rtcp_demux_unprotected
+ * below answers on the device, in the order this call wants; a host may also
+ * decide it itself.  The grouping rule, the outputs and the error codes are
  * lkf_rtcp_ingest's; a dgram out of range is LKF_EINVAL before anything runs.
  * lkf_rtcp_ref.off / len index the plaintext arena lkf_srtcp_unprotect
  * returned. */
@@ -1488,6 +1489,85 @@ int lkf_rtcp_ingest_unprotected(lkf_engine *e, const lkf_rtcp_entry *in, uint32_
                                 lkf_rtcp_in_result *out, lkf_rtcp_fb *fb, lkf_rtcp_fb_result *fb_out, uint32_t fb_cap,
                                 uint32_t *n_fb, lkf_rtcp_ref *refs, uint32_t ref_cap, uint32_t *n_refs,
                                 uint32_t *n_nacks);
+/* ---- RTCP demultiplexing: which DownTracks a compound addresses ---------- *
+ * pion's SessionSRTCP.decrypt writes a decrypted compound to the read stream
+ * of every SSRC that rtcp DestinationSSRC names; the DownTrack whose
+ * RTCPReader.OnPacket is bound to that SSRC then runs handleRTCP on the whole
+ * compound.  The demux calls do that fan-out on the device: datagrams in,
+ * lkf_rtcp_entry {dt, dgram} out, ready for lkf_rtcp_ingest_unprotected.
+ *
+ * The routing table: every active DownTrack bound to a receive transport
+ * with lkf_set_downtrack_rtcp_transport, keyed by (transport, SSRC).  Two
+ * active DownTracks with one key: the higher handle wins (Factory.GetOrNew
+ * hands both the same RTCPReader and the later OnPacket replaces the
+ * callback, downtrack.go:400-404).  A removed DownTrack is addressed by
+ * nothing.  The table is rebuilt on the host and uploaded inside the next
+ * demux call after a bind, lkf_add_downtrack, lkf_remove_downtrack or
+ * lkf_remove_track; lkf_run never looks at it.
+ *
+ * A datagram routes only when the framing and the size checks of the RTCP
+ * ingress table above pass for every packet: a compound lkf_rtcp_ingest would
+ * call MALFORMED routes to nobody (rtcp.Unmarshal fails before DestinationSSRC
+ * runs), so every entry the demux yields ingests with LKF_RTCP_IN_OK.
+ *
+ * The destination SSRCs of one packet, by type (pion/rtcp v1.2.13
+ * DestinationSSRC; q = the packet's first byte, size = its bytes with the
+ * header, big-endian 32-bit words):
+ *
+ *   PT / fmt                              destinations
+ *   201       RR                          each report block's SSRC (bytes 8 + 24k, k < count)
+ *   200       SR                          each report block's SSRC (bytes 28 + 24k, k < count),
+ *                                         then the sender SSRC (bytes 4..7)
+ *   205 / 1   NACK, 205 / 15 Transport-   the media SSRC, bytes 8..11
+ *             LayerCC, 206 / 1 PLI
+ *   205 / 5   RRR, 206 / 2 SLI            the media SSRC, bytes 8..11, when size >= 12; otherwise
+ *                                         none (the ingress table puts no size check on them and
+ *                                         the demux adds none: a short one is still not malformed)
+ *   206 / 4   FIR                         each entry's SSRC (bytes 12 + 8k); the media SSRC field
+ *                                         is not a destination
+ *   206 / 15  REMB                        the numSSRC (byte 16) SSRCs from byte 20
+ *   others                                none (SDES, BYE, APP, XR, 205 / 11, unknown types and
+ *                                         formats)
+ *
+ * Divergence: pion also returns SDES chunk sources, BYE sources and XR
+ * sub-block SSRCs; the engine does not walk those bodies (as in RTCP ingress).
+ * They are the browser's own SSRCs, never a DownTrack's.
+ *
+ * An SSRC that several packets of one compound name yields one entry; dests
+ * and unrouted count occurrences, not distinct SSRCs.  An EMPTY or MALFORMED
+ * datagram reports dests = unrouted = entries = 0. */
+#define LKF_RTCP_DMX_OK 0
+#define LKF_RTCP_DMX_EMPTY 1     /* len 0: a datagram lkf_srtcp_unprotect rejected */
+#define LKF_RTCP_DMX_MALFORMED 2 /* routes to nobody */
+typedef struct lkf_rtcp_dmx_result { /* per datagram; 16 B */
+  uint32_t status;   /* LKF_RTCP_DMX_* */
+  uint32_t dests;    /* destination-SSRC occurrences in the compound */
+  uint32_t unrouted; /* of those, occurrences with no DownTrack on this transport */
+  uint32_t entries;  /* distinct DownTracks addressed = entries this datagram yields */
+} lkf_rtcp_dmx_result;
+/* Binds a DownTrack to the transport its subscriber's RTCP arrives on (the
+ * PeerConnection's receive-direction context; -1: none, the default).  Used
+ * only by the demux calls below; independent of lkf_set_downtrack_transport.
+ * Host bookkeeping only: no device memory is touched until the next demux. */
+int lkf_set_downtrack_rtcp_transport(lkf_engine *e, int32_t dt, int32_t transport);
+/* Demultiplexes the plaintext the last lkf_srtcp_unprotect left on the device
+ * (res: one per datagram of that call; a rejected datagram is EMPTY).
+ * entries[] is sorted by DownTrack handle ascending and by dgram ascending
+ * within a DownTrack — the grouping lkf_rtcp_ingest_unprotected demands, so
+ * the array passes to it unchanged; the order is a function of the data alone.
+ * *n_entries = the number of entries; cap < *n_entries returns LKF_ENOSPC with
+ * *n_entries and res[] filled.  The calls keep no state, so a call may simply
+ * be repeated.  Before any unprotect, or after one with n = 0: LKF_OK, zero
+ * entries.  Control-rate, as lkf_srtcp_unprotect. */
+int lkf_rtcp_demux_unprotected(lkf_engine *e, lkf_rtcp_dmx_result *res, lkf_rtcp_entry *entries, uint32_t cap,
+                               uint32_t *n_entries);
+/* The same on the caller's own plaintext: in[i] = {transport, off, len} in
+ * arena; entries[k].dgram indexes in[], and the lkf_rtcp_raw for
+ * lkf_rtcp_ingest is {entries[k].dt, in[dgram].off, in[dgram].len}.  An
+ * unknown transport handle, off + len > arena_len or len > LKF_RTCP_MAX_LEN is
+ * LKF_EINVAL before anything runs. */
+int lkf_rtcp_demux(lkf_engine *e, const lkf_srtcp_raw *in, uint32_t n, const uint8_t *arena, uint64_t arena_len,
+                   lkf_rtcp_dmx_result *res, lkf_rtcp_entry *entries, uint32_t cap, uint32_t *n_entries);
 typedef struct lkf_transport_srtcp { /* one transport's SRTCP receive slots and counters; 368 B */
   uint32_t in_use[LKF_SRTCP_SSRCS], ssrc[LKF_SRTCP_SSRCS], latest[LKF_SRTCP_SSRCS];
   uint64_t mask[LKF_SRTCP_SSRCS];

@@ -421,6 +421,43 @@ class Engine:
                   "rtcp_ingest_unprotected")
         return out, fb[:nfb.value], fbo[:nfb.value], refs[:nref.value], nn.value
 
+    def set_downtrack_rtcp_transport(self, dt, transport):
+        """lkf_set_downtrack_rtcp_transport: the transport DownTrack `dt`'s
+        subscriber sends its RTCP on (-1: none)."""
+        self._chk(self.api["set_downtrack_rtcp_transport"](self.h, dt, transport), "set_downtrack_rtcp_transport")
+
+    def _rtcp_demux(self, what, n, call):
+        # sized by the call itself: once for the count, again on LKF_ENOSPC (the calls keep no state)
+        res = np.zeros(n, dtype=abi.RTCP_DMX_RESULT_DTYPE)
+        ent = np.zeros(max(1, n), dtype=abi.RTCP_ENTRY_DTYPE)
+        k = C.c_uint32()
+        rc = call(res, ent, k)
+        if rc == -28:  # LKF_ENOSPC
+            ent = np.zeros(k.value, dtype=abi.RTCP_ENTRY_DTYPE)
+            rc = call(res, ent, k)
+        self._chk(rc, what)
+        return res, ent[:k.value]
+
+    def rtcp_demux(self, raws, arena):
+        """lkf_rtcp_demux: `raws` an abi.SRTCP_RAW_DTYPE array {transport, off,
+        len} of plaintext compounds in `arena` -> (abi.RTCP_DMX_RESULT_DTYPE
+        per datagram, abi.RTCP_ENTRY_DTYPE entries sorted by DownTrack, then
+        datagram)."""
+        rw = np.ascontiguousarray(raws, dtype=abi.SRTCP_RAW_DTYPE)
+        ar = np.frombuffer(arena, dtype=np.uint8) if isinstance(arena, (bytes, bytearray)) else \
+            np.ascontiguousarray(arena, dtype=np.uint8)
+        return self._rtcp_demux("rtcp_demux", len(rw), lambda res, ent, k: self.api["rtcp_demux"](
+            self.h, rw.ctypes.data, len(rw), ar.ctypes.data if len(ar) else None, len(ar), res.ctypes.data,
+            ent.ctypes.data, len(ent), C.byref(k)))
+
+    def rtcp_demux_unprotected(self):
+        """lkf_rtcp_demux_unprotected on the last srtcp_unprotect's plaintext
+        -> what rtcp_demux returns; the entries pass to
+        rtcp_ingest_unprotected unchanged."""
+        return self._rtcp_demux("rtcp_demux_unprotected", len(self._srtcp_lens),
+                                lambda res, ent, k: self.api["rtcp_demux_unprotected"](
+                                    self.h, res.ctypes.data, ent.ctypes.data, len(ent), C.byref(k)))
+
     def transport_srtcp(self, transport):
         """lkf_transport_srtcp_get -> (slots [(in_use, ssrc, latest, mask)] * 16, the six counters)."""
         st = abi.lkf_transport_srtcp()

@@ -516,6 +516,14 @@ class lkf_rtcp_entry(C.Structure):
     _fields_ = [("dt", C.c_int32), ("dgram", C.c_uint32)]
 
 
+# RTCP demultiplexing (lkf_rtcp_demux / lkf_rtcp_demux_unprotected)
+LKF_RTCP_DMX_OK, LKF_RTCP_DMX_EMPTY, LKF_RTCP_DMX_MALFORMED = range(3)
+
+
+class lkf_rtcp_dmx_result(C.Structure):
+    _fields_ = [(f, C.c_uint32) for f in ("status", "dests", "unrouted", "entries")]
+
+
 class lkf_srtcp_tx_result(C.Structure):
     _fields_ = [(f, C.c_uint32) for f in ("ssrc", "index", "off", "len")]
 
@@ -540,6 +548,8 @@ SRTCP_TX_RESULT_DTYPE = np.dtype([(f, "<u4") for f in ("ssrc", "index", "off", "
 assert C.sizeof(lkf_srtcp_raw) == 12 == SRTCP_RAW_DTYPE.itemsize
 assert C.sizeof(lkf_srtcp_rx_result) == 16 == SRTCP_RX_RESULT_DTYPE.itemsize
 assert C.sizeof(lkf_rtcp_entry) == 8 == RTCP_ENTRY_DTYPE.itemsize
+RTCP_DMX_RESULT_DTYPE = np.dtype([(f, "<u4") for f in ("status", "dests", "unrouted", "entries")])
+assert C.sizeof(lkf_rtcp_dmx_result) == 16 == RTCP_DMX_RESULT_DTYPE.itemsize
 assert C.sizeof(lkf_srtcp_tx_result) == 16 == SRTCP_TX_RESULT_DTYPE.itemsize
 assert C.sizeof(lkf_transport_srtcp) == 368
 
@@ -808,6 +818,14 @@ def bind_engine_api(lib, prefix):
                                       C.c_void_p, P(C.c_uint64)])
         api["srtcp_tx_index"] = _bind(lib, prefix + "srtcp_tx_index", C.c_int,
                                       [e, C.c_int32, C.c_uint32, P(C.c_uint32)])
+    if hasattr(lib, prefix + "rtcp_demux"):  # engine only: RTCP demultiplexing
+        api["set_downtrack_rtcp_transport"] = _bind(lib, prefix + "set_downtrack_rtcp_transport", C.c_int,
+                                                    [e, C.c_int32, C.c_int32])
+        api["rtcp_demux_unprotected"] = _bind(lib, prefix + "rtcp_demux_unprotected", C.c_int,
+                                              [e, C.c_void_p, C.c_void_p, C.c_uint32, P(C.c_uint32)])
+        api["rtcp_demux"] = _bind(lib, prefix + "rtcp_demux", C.c_int,
+                                  [e, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                   C.c_uint32, P(C.c_uint32)])
     api["blank_frames"] = _bind(lib, prefix + "blank_frames", C.c_int,
                                 [e, C.c_void_p, C.c_uint32, C.c_int64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64,
                                  P(C.c_uint32), P(C.c_uint64)])

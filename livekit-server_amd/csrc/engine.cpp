@@ -502,6 +502,28 @@ struct lkf_engine {
   // datagram's offset and plaintext length in dScPlain
   std::vector<uint32_t> scOff, scLen;
   uint64_t scPlainLen = 0;
+  // ... and for lkf_rtcp_demux_unprotected each datagram's transport, and
+  // whether that call's list and results reached dScIn / dScRes
+  std::vector<int32_t> scTransport;
+  bool scOnDevice = false;
+  // RTCP demultiplexing (lkf_rtcp_demux): each DownTrack's receive-direction
+  // transport; the routing table (rows by (transport, SSRC), its CSR, the rows
+  // in DownTrack order, and the per-row counts / offsets / scan state, one
+  // family sized by the table), rebuilt inside the next demux call when dirty;
+  // one call's datagram list, bitmap rows, per-transport datagram lists,
+  // results and entries
+  std::vector<int32_t> dtRtcpTransport;
+  bool dmxDirty = true;
+  std::vector<uint32_t> dmxTFirst;  // the CSR's host copy (each transport's row count)
+  uint32_t dmxRows = 0;
+  DevBuf<RtcpDmxRow> dDmxRows;
+  DevBuf<uint32_t> dDmxTFirst, dDmxByDt, dDmxCnt, dDmxTdFirst;
+  DevBuf<uint64_t> dDmxOff, dDmxTot, dDmxScan;
+  DevBuf<lkf_srtcp_raw> dDmxIn;
+  DevBuf<uint32_t> dDmxBmOff, dDmxTdList, dDmxBits;
+  DevBuf<uint8_t> dDmxArena;
+  DevBuf<lkf_rtcp_dmx_result> dDmxRes;
+  DevBuf<lkf_rtcp_entry> dDmxEntries;
   std::map<std::pair<int32_t, uint32_t>, uint32_t> scTxIndex;  // (transport, SSRC) -> the last index sent
   // ingress (one buffer.Buffer per stream) + speakers
   uint32_t maxStreams = 0;
@@ -1408,6 +1430,8 @@ int32_t lkf_add_downtrack(lkf_engine *e, const lkf_downtrack_params *p) {
   std::memcpy(d.playout, p->playout_delay, 3);
   d.active = 1;
   e->dtTransport.push_back(-1);
+  e->dtRtcpTransport.push_back(-1);
+  e->dmxDirty = true;
   if (p->ext_transport_cc) e->anyTwcc = e->twccDirty = true;
   e->pendDTs.push_back(d);  // uploaded by flush_topology (one copy per batch of adds)
   e->schedDirty = true;
@@ -1427,6 +1451,7 @@ int lkf_remove_downtrack(lkf_engine *e, int32_t dt) {
   if (!e || dt < 0 || dt >= int32_t(e->dtp.size())) return LKF_EINVAL;
   STEP(quiesce(e));
   e->active[dt] = 0;
+  e->dmxDirty = true;
   e->topoGen++;
   uint8_t zero = 0;
   HIPCHK(hipMemcpy(reinterpret_cast<uint8_t *>(e->dDTs + dt) + offsetof(DevDT, active), &zero, 1,
@@ -1446,6 +1471,7 @@ int lkf_remove_track(lkf_engine *e, int32_t track) {
   for (size_t d = 0; d < e->dtp.size(); d++)  // closeTracks: every DownTrack of the receiver
     if (e->dtp[d].track == track && e->active[d]) {
       e->active[d] = 0;
+      e->dmxDirty = true;
       e->topoGen++;
       HIPCHK(hipMemcpy(reinterpret_cast<uint8_t *>(e->dDTs + d) + offsetof(DevDT, active), &zero, 1,
                        hipMemcpyHostToDevice),
@@ -2720,6 +2746,15 @@ int lkf_set_downtrack_transport(lkf_engine *e, int32_t dt, int32_t t) {
   return upload_done(e);
 }
 
+// Host bookkeeping alone: the next demux call rebuilds the routing table.
+int lkf_set_downtrack_rtcp_transport(lkf_engine *e, int32_t dt, int32_t t) {
+  if (!e || dt < 0 || dt >= int32_t(e->dtp.size()) || t < -1 || t >= int32_t(e->transports.size()))
+    return LKF_EINVAL;
+  e->dtRtcpTransport[size_t(dt)] = t;
+  e->dmxDirty = true;
+  return LKF_OK;
+}
+
 // pion/rtp NewAbsSendTimeExtension(t).Marshal(): NTP time >> 14, 24 bits
 static uint32_t abs_send_time(int64_t unixNs) {
   const uint64_t u = uint64_t(unixNs);
@@ -3325,9 +3360,11 @@ int lkf_srtcp_unprotect(lkf_engine *e, const lkf_srtcp_raw *in, uint32_t n, cons
   STEP(f.open());
   e->scOff.assign(n, 0);
   e->scLen.assign(n, 0);
+  e->scTransport.assign(n, -1);
+  e->scOnDevice = false;
   e->scPlainLen = srtcp_len;
   if (!n) return LKF_OK;
-  for (uint32_t i = 0; i < n; i++) e->scOff[i] = in[i].off;
+  for (uint32_t i = 0; i < n; i++) e->scOff[i] = in[i].off, e->scTransport[i] = in[i].transport;
   if (e->transports.empty()) {  // every handle is unknown
     for (uint32_t i = 0; i < n; i++) out[i] = lkf_srtcp_rx_result{0, 0, LKF_SRTCP_RX_MALFORMED, 0};
     return LKF_OK;
@@ -3359,6 +3396,7 @@ int lkf_srtcp_unprotect(lkf_engine *e, const lkf_srtcp_raw *in, uint32_t n, cons
   D2H(out, e->dScRes, size_t(n) * sizeof(lkf_srtcp_rx_result), "srtcp results copy");
   if (plain && srtcp_len) D2H(plain, e->dScPlain, srtcp_len, "srtcp plaintext copy");
   for (uint32_t i = 0; i < n; i++) e->scLen[i] = out[i].len;
+  e->scOnDevice = true;
   return LKF_OK;
 }
 
@@ -3377,6 +3415,186 @@ int lkf_rtcp_ingest_unprotected(lkf_engine *e, const lkf_rtcp_entry *in, uint32_
   const uint8_t *host = e->dScPlain ? nullptr : &none;
   return rtcp_ingest_run(e, raw.data(), n, host, e->dScPlain, host ? 0 : e->scPlainLen, now_ns, out, fb, fb_out, fb_cap,
                          n_fb, refs, ref_cap, n_refs, n_nacks);
+}
+
+// ---- RTCP demultiplexing (rtcp_kernels.hip k_rtcp_dmx_*; the walk is rtcp_dmx_device.h) ----
+static_assert(sizeof(lkf_rtcp_dmx_result) == 16, "RTCP demux records");
+
+// The routing table from the host's lists: the active DownTracks with a
+// receive transport, one row per (transport, SSRC), the highest handle of a
+// key kept; its CSR by transport; the rows in ascending DownTrack order.
+// Uploaded on the call's stream (the family grows only here, so the table
+// stays on the device until it is dirty again).
+static int rtcp_dmx_rebuild(lkf_engine *e, Frame &f) {
+  std::vector<RtcpDmxRow> rows;
+  for (size_t d = 0; d < e->dtp.size(); d++)
+    if (e->active[d] && e->dtRtcpTransport[d] >= 0)
+      rows.push_back({uint32_t(e->dtRtcpTransport[d]), e->dtp[d].ssrc, int32_t(d)});
+  std::sort(rows.begin(), rows.end(), [](const RtcpDmxRow &a, const RtcpDmxRow &b) {
+    return std::tie(a.transport, a.ssrc, a.dt) < std::tie(b.transport, b.ssrc, b.dt);
+  });
+  size_t k = 0;
+  for (size_t i = 0; i < rows.size(); i++)  // the last of a key's run: the highest handle
+    if (i + 1 == rows.size() || rows[i + 1].transport != rows[i].transport || rows[i + 1].ssrc != rows[i].ssrc)
+      rows[k++] = rows[i];
+  rows.resize(k);
+  const size_t nt = e->transports.size();
+  std::vector<uint32_t> tFirst(nt + 1, 0), byDt(rows.size());
+  for (const auto &r : rows) tFirst[r.transport + 1]++;
+  for (size_t t = 0; t < nt; t++) tFirst[t + 1] += tFirst[t];
+  for (size_t i = 0; i < byDt.size(); i++) byDt[i] = uint32_t(i);
+  std::sort(byDt.begin(), byDt.end(), [&](uint32_t a, uint32_t b) { return rows[a].dt < rows[b].dt; });
+  const uint64_t nr = rows.size(), m = 2 * nr;
+  auto words = [](uint64_t q) {
+    return uint64_t(scan_state_words(uint32_t(std::min<uint64_t>(std::max<uint64_t>(q, 4096), 0xffffffffu))));
+  };
+  STEP(f.grow("alloc rtcp demux table", want(e->dDmxRows, nr, 1024, m), want(e->dDmxByDt, nr, 1024, m),
+              want(e->dDmxCnt, nr, 1024, m), want(e->dDmxOff, nr, 1024, m), want(e->dDmxTFirst, nt + 1, 256, 2 * nt + 1),
+              want(e->dDmxTdFirst, nt + 1, 256, 2 * nt + 1), want(e->dDmxTot, 1, 1),
+              want(e->dDmxScan, words(nr), 0, words(m))));
+  if (f.grew)
+    HIPCHK(hipMemsetAsync(e->dDmxScan, 0, e->dDmxScan.cap() * sizeof(uint64_t), f.s), "rtcp demux scan state reset");
+  if (nr) {
+    STEP(f.up(e->dDmxRows, rows.data(), nr * sizeof(RtcpDmxRow), "rtcp demux rows copy"));
+    STEP(f.up(e->dDmxByDt, byDt.data(), nr * sizeof(uint32_t), "rtcp demux order copy"));
+  }
+  STEP(f.up(e->dDmxTFirst, tFirst.data(), tFirst.size() * sizeof(uint32_t), "rtcp demux csr copy"));
+  STEP(f.wait());  // (the uploads read this function's vectors)
+  e->dmxTFirst = std::move(tFirst);
+  e->dmxRows = uint32_t(nr);
+  e->dmxDirty = false;
+  return LKF_OK;
+}
+
+// The two calls' body.  tr / len: each datagram's transport and plaintext
+// length on the host (an empty datagram's transport is not looked at).  `in`:
+// the list in host memory, uploaded with `arena`; NULL: the list is dIn with
+// the lengths in dRx, the bytes the arena_len at dArena (the last unprotect's).
+// Mark pass -> count pass -> scan -> the total back on the host (the entry
+// list is sized by it) -> write pass.
+static int rtcp_dmx_run(lkf_engine *e, const int32_t *tr, const uint32_t *len, uint32_t n, const lkf_srtcp_raw *in,
+                        const uint8_t *arena, const lkf_srtcp_raw *dIn, const lkf_srtcp_rx_result *dRx,
+                        const uint8_t *dArena, uint64_t arena_len, lkf_rtcp_dmx_result *res, lkf_rtcp_entry *entries,
+                        uint32_t cap, uint32_t *n_entries) {
+  Frame f(e, Order::BehindSender);
+  STEP(f.open());
+  if (!n) return LKF_OK;
+  const size_t nt = e->transports.size();
+  if (e->dmxDirty || e->dmxTFirst.size() != nt + 1) STEP(rtcp_dmx_rebuild(e, f));
+  // each datagram's bitmap row and each transport's datagrams, in call order
+  std::vector<uint32_t> bmOff(size_t(n) + 1, 0), tdFirst(nt + 1, 0), tdList;
+  uint64_t bmWords = 0;
+  auto live = [&](uint32_t i) { return len[i] && tr[i] >= 0 && size_t(tr[i]) < nt; };
+  for (uint32_t i = 0; i < n; i++) {
+    if (live(i)) {
+      bmWords += (e->dmxTFirst[size_t(tr[i]) + 1] - e->dmxTFirst[size_t(tr[i])] + 31) / 32;
+      tdFirst[size_t(tr[i]) + 1]++;
+    }
+    if (bmWords > 0xffffffffull) {
+      e->err = "RTCP demux: the bitmap rows of one call exceed 2^32 - 1 words";
+      return LKF_EINVAL;
+    }
+    bmOff[size_t(i) + 1] = uint32_t(bmWords);
+  }
+  for (size_t t = 0; t < nt; t++) tdFirst[t + 1] += tdFirst[t];
+  tdList.resize(tdFirst[nt]);
+  {
+    std::vector<uint32_t> at(tdFirst.begin(), tdFirst.end() - 1);
+    for (uint32_t i = 0; i < n; i++)
+      if (live(i)) tdList[at[size_t(tr[i])]++] = i;
+  }
+  const uint64_t m = 2 * uint64_t(n);
+  STEP(f.grow("alloc rtcp demux scratch", want(e->dDmxIn, n, 4096, m), want(e->dDmxBmOff, uint64_t(n) + 1, 4097, m + 1),
+              want(e->dDmxTdList, n, 4096, m), want(e->dDmxRes, n, 4096, m)));
+  STEP(f.grow("alloc rtcp demux bitmap", want(e->dDmxBits, bmWords, 4096, 2 * bmWords)));
+  if (in) {
+    STEP(f.grow("alloc rtcp demux arena", want(e->dDmxArena, arena_len, 1 << 16, 2 * arena_len)));
+    STEP(f.up(e->dDmxIn, in, size_t(n) * sizeof(lkf_srtcp_raw), "rtcp demux list copy"));
+    if (arena_len) STEP(f.up(e->dDmxArena, arena, arena_len, "rtcp demux arena copy"));
+  }
+  STEP(f.up(e->dDmxBmOff, bmOff.data(), bmOff.size() * sizeof(uint32_t), "rtcp demux bitmap rows copy"));
+  STEP(f.up(e->dDmxTdFirst, tdFirst.data(), tdFirst.size() * sizeof(uint32_t), "rtcp demux ranges copy"));
+  if (!tdList.empty())
+    STEP(f.up(e->dDmxTdList, tdList.data(), tdList.size() * sizeof(uint32_t), "rtcp demux datagram lists copy"));
+  if (bmWords) HIPCHK(hipMemsetAsync(e->dDmxBits, 0, bmWords * sizeof(uint32_t), f.s), "rtcp demux bitmap reset");
+  RtcpDmxLaunch a{};
+  a.in = in ? e->dDmxIn.get() : dIn;
+  a.rx = in ? nullptr : dRx;
+  a.n = n;
+  a.arena = in ? e->dDmxArena.get() : dArena;
+  a.arenaLen = arena_len;
+  a.rows = e->dDmxRows;
+  a.nrows = e->dmxRows;
+  a.tFirst = e->dDmxTFirst;
+  a.ntransports = uint32_t(nt);
+  a.byDt = e->dDmxByDt;
+  a.bmOff = e->dDmxBmOff;
+  a.bits = e->dDmxBits;
+  a.bmWords = bmWords;
+  a.tdFirst = e->dDmxTdFirst;
+  a.tdList = e->dDmxTdList;
+  a.res = e->dDmxRes;
+  a.cnt = e->dDmxCnt;
+  a.off = e->dDmxOff;
+  HIPCHK(launch_rtcp_dmx_mark(f.s, a), "rtcp demux mark");
+  uint64_t total = 0;
+  if (a.nrows) {
+    HIPCHK(launch_rtcp_dmx_count(f.s, a), "rtcp demux count");
+    HIPCHK(launch_scan(f.s, 2, nullptr, nullptr, nullptr, e->dDmxCnt, nullptr, a.nrows, e->dDmxScan, nullptr, e->dDmxOff,
+                       nullptr, e->dDmxTot, nullptr, nullptr),
+           "rtcp demux scan");
+    STEP(f.down(&total, e->dDmxTot, sizeof(total), "rtcp demux total copy"));
+  }
+  STEP(f.wait());
+  D2H(res, e->dDmxRes, size_t(n) * sizeof(lkf_rtcp_dmx_result), "rtcp demux results copy");
+  if (total > 0xffffffffull) {  // (or a scan that gave up: ~0)
+    e->err = "RTCP demux: one call yields more than 2^32 - 1 entries";
+    return LKF_EINVAL;
+  }
+  *n_entries = uint32_t(total);
+  if (total > cap) return LKF_ENOSPC;
+  if (!total) return LKF_OK;
+  HIPCHK(e->dDmxEntries.reserve(total, 4096), "alloc rtcp demux entries");  // (the stream is idle here)
+  a.entries = e->dDmxEntries;
+  a.entryCap = total;
+  HIPCHK(launch_rtcp_dmx_write(f.s, a), "rtcp demux write");
+  STEP(f.wait());
+  D2H(entries, e->dDmxEntries, size_t(total) * sizeof(lkf_rtcp_entry), "rtcp demux entries copy");
+  return LKF_OK;
+}
+
+int lkf_rtcp_demux_unprotected(lkf_engine *e, lkf_rtcp_dmx_result *res, lkf_rtcp_entry *entries, uint32_t cap,
+                               uint32_t *n_entries) {
+  if (!e || !n_entries) return LKF_EINVAL;
+  *n_entries = 0;
+  const uint32_t n = uint32_t(e->scLen.size());
+  if ((n && !res) || (cap && !entries)) return LKF_EINVAL;
+  for (uint32_t i = 0; i < n; i++)
+    if (e->scLen[i] > LKF_RTCP_MAX_LEN) return LKF_EINVAL;  // (as lkf_rtcp_ingest_unprotected would)
+  if (!e->scOnDevice) {  // no datagram of that call reached the device: every one was rejected
+    for (uint32_t i = 0; i < n; i++) res[i] = lkf_rtcp_dmx_result{LKF_RTCP_DMX_EMPTY, 0, 0, 0};
+    return LKF_OK;
+  }
+  return rtcp_dmx_run(e, e->scTransport.data(), e->scLen.data(), n, nullptr, nullptr, e->dScIn, e->dScRes, e->dScPlain,
+                      e->scPlainLen, res, entries, cap, n_entries);
+}
+
+int lkf_rtcp_demux(lkf_engine *e, const lkf_srtcp_raw *in, uint32_t n, const uint8_t *arena, uint64_t arena_len,
+                   lkf_rtcp_dmx_result *res, lkf_rtcp_entry *entries, uint32_t cap, uint32_t *n_entries) {
+  if (!e || !n_entries || (n && (!in || !res)) || (cap && !entries) || (arena_len && !arena)) return LKF_EINVAL;
+  *n_entries = 0;
+  std::vector<int32_t> tr(n);
+  std::vector<uint32_t> len(n);
+  for (uint32_t i = 0; i < n; i++) {
+    if (in[i].transport < 0 || in[i].transport >= int32_t(e->transports.size()) || in[i].len > LKF_RTCP_MAX_LEN ||
+        uint64_t(in[i].off) + in[i].len > arena_len)
+      return LKF_EINVAL;
+    tr[i] = in[i].transport;
+    len[i] = in[i].len;
+  }
+  static const uint8_t none = 0;  // (an empty arena is still the caller's)
+  return rtcp_dmx_run(e, tr.data(), len.data(), n, in, arena ? arena : &none, nullptr, nullptr, nullptr, arena_len, res,
+                      entries, cap, n_entries);
 }
 
 int lkf_transport_srtcp_get(lkf_engine *e, int32_t transport, lkf_transport_srtcp *out) {

@@ -626,10 +626,53 @@ struct RtcpInLaunch {
 hipError_t launch_rtcp_in_count(hipStream_t s, const RtcpInLaunch &a);
 hipError_t launch_rtcp_in_write(hipStream_t s, const RtcpInLaunch &a);
 hipError_t launch_rtcp_in_fold(hipStream_t s, const RtcpInLaunch &a);
+// RTCP demultiplexing (lkf_rtcp_demux; the walk and the lookup are
+// rtcp_dmx_device.h).  The routing table: rows sorted by (transport, ssrc),
+// tFirst its CSR by transport, byDt the row indices in ascending DownTrack
+// order.  Per call, from the host: each datagram's bitmap row (bmOff, one bit
+// per row of its transport; none for an empty datagram) and the datagrams of
+// each transport in call order (tdFirst / tdList).
+//   k_rtcp_dmx_mark   one lane per datagram: walks the compound, sets the bit
+//                     of every row a destination finds in the lane's own
+//                     (zeroed) bitmap row, writes res
+//   k_rtcp_dmx_count  one lane per byDt position: its row's set bits over its
+//                     transport's datagrams -> cnt (the engine scans it into off)
+//   k_rtcp_dmx_write  the same walk, {dt, dgram} at off + j: DownTrack
+//                     ascending, datagram ascending, no atomics anywhere
+struct RtcpDmxRow {  // (= rtcpdmx::Row)
+  uint32_t transport, ssrc;
+  int32_t dt;
+};
+struct RtcpDmxLaunch {
+  const lkf_srtcp_raw *in;  // {transport, off, len} per datagram
+  const lkf_srtcp_rx_result *rx;  // non-null: the datagram's len is rx[i].len (the last unprotect's results)
+  uint32_t n;
+  const uint8_t *arena;
+  uint64_t arenaLen;
+  const RtcpDmxRow *rows;
+  uint32_t nrows;
+  const uint32_t *tFirst;  // ntransports + 1
+  uint32_t ntransports;
+  const uint32_t *byDt;     // nrows
+  const uint32_t *bmOff;    // n + 1: first word of each datagram's bitmap row
+  uint32_t *bits;           // bmWords words, zeroed before the mark pass
+  uint64_t bmWords;
+  const uint32_t *tdFirst;  // ntransports + 1
+  const uint32_t *tdList;   // n (empty datagrams left out)
+  lkf_rtcp_dmx_result *res;
+  uint32_t *cnt;            // nrows, byDt order
+  const uint64_t *off;      // nrows: the exclusive scan of cnt
+  lkf_rtcp_entry *entries;
+  uint64_t entryCap;
+};
+hipError_t launch_rtcp_dmx_mark(hipStream_t s, const RtcpDmxLaunch &a);
+hipError_t launch_rtcp_dmx_count(hipStream_t s, const RtcpDmxLaunch &a);
+hipError_t launch_rtcp_dmx_write(hipStream_t s, const RtcpDmxLaunch &a);
 // -DLKF_CHECKED=1 builds of rtcp_kernels.hip: its own {violations, first site,
 // index, capacity} (sites 101 DownTrack handle, 102 ring slot, 103 entry /
-// request index, 104 arena byte, 105 / 106 / 107 fb / NACK / ref list index);
-// lkf_debug_check folds it into the record
+// request index, 104 arena byte, 105 / 106 / 107 fb / NACK / ref list index,
+// 108 routing-table row, 109 transport, 110 bitmap word, 111 datagram index,
+// 112 demux entry index); lkf_debug_check folds it into the record
 hipError_t read_check_rtcp(unsigned long long out[4], int reset);
 
 }  // namespace lkf

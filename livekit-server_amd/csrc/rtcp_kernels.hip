@@ -19,14 +19,20 @@
 //                   NACKed sequence numbers and pass-through records at the
 //                   scanned offsets (input order, no cursors), fold the
 //                   reports' results into the entry's rtt_ms.
+//   k_rtcp_dmx_*    RTCP demultiplexing (lkf_rtcp_demux): one lane per datagram
+//                   marks the routing-table rows its destination SSRCs find in
+//                   a bitmap row of its own; one lane per DownTrack of the
+//                   table then counts and, behind a scan, writes its {dt,
+//                   dgram} entries in datagram order.  No atomics, no sort.
 //
-// The semantics are rtcp_device.h's and rtcp_in_device.h's (shared with the
-// host unit programs).
+// The semantics are rtcp_device.h's, rtcp_in_device.h's and rtcp_dmx_device.h's
+// (shared with the host unit programs).
 #include <hip/hip_runtime.h>
 
 #include "kernels.h"
 #include "rtcp_device.h"
 #include "rtcp_in_device.h"
+#include "rtcp_dmx_device.h"
 
 namespace lkf {
 namespace {
@@ -48,7 +54,12 @@ enum : u32 {
   CK_RTCP_ARENA = 104,
   CK_RTCP_FB = 105,
   CK_RTCP_NACK = 106,
-  CK_RTCP_REF = 107
+  CK_RTCP_REF = 107,
+  CK_DMX_ROW = 108,
+  CK_DMX_TRANSPORT = 109,
+  CK_DMX_WORD = 110,
+  CK_DMX_DGRAM = 111,
+  CK_DMX_ENTRY = 112
 };
 #if LKF_CHECKED
 __device__ unsigned long long g_chk_rtcp[4];
@@ -300,6 +311,96 @@ __global__ void k_rtcp_in_fold(RtcpInLaunch A) {
       if (A.fbOut[k].flags & LKF_FB_RTT_CHANGED) rtt = A.fbOut[k].rtt_ms;  // rttToReport (downtrack.go:1529-1531)
   A.res[i].rtt_ms = rtt;
 }
+
+// ---- RTCP demultiplexing (lkf_rtcp_demux): rtcp_dmx_device.h's walk and lookup
+static_assert(sizeof(RtcpDmxRow) == sizeof(rtcpdmx::Row) && sizeof(RtcpDmxRow) == 12, "routing-table row");
+
+__global__ void k_rtcp_dmx_mark(RtcpDmxLaunch A) {
+  const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= A.n) return;
+  const lkf_srtcp_raw r = A.in[i];
+  const u32 len = A.rx ? A.rx[i].len : r.len;
+  lkf_rtcp_dmx_result o = {};
+  o.status = LKF_RTCP_DMX_EMPTY;
+  if (len) {
+    o.status = LKF_RTCP_DMX_MALFORMED;
+    const u32 t = u32(r.transport);
+    const u32 w0 = A.bmOff[i], w1 = A.bmOff[i + 1];
+    CHK(t < A.ntransports, CK_DMX_TRANSPORT, t, A.ntransports);
+    CHK(u64(r.off) + len <= A.arenaLen, CK_RTCP_ARENA, u64(r.off) + len, A.arenaLen);
+    CHK(w0 <= w1 && w1 <= A.bmWords, CK_DMX_WORD, w1, A.bmWords);
+    if (t < A.ntransports && u64(r.off) + len <= A.arenaLen && w0 <= w1 && w1 <= A.bmWords) {
+      const u32 lo = A.tFirst[t], hi = A.tFirst[t + 1];
+      CHK(lo <= hi && hi <= A.nrows, CK_DMX_ROW, hi, A.nrows);
+      if (lo <= hi && hi <= A.nrows) {
+        CHK(w1 - w0 == rtcpdmx::row_words(hi - lo), CK_DMX_WORD, w1 - w0, rtcpdmx::row_words(hi - lo));
+        u32 *bits = A.bits + w0;
+        rtcpdmx::Mark m{reinterpret_cast<const rtcpdmx::Row *>(A.rows), lo, hi, bits, w1 - w0};
+        if (rtcpdmx::walk(A.arena + r.off, len, m) == LKF_RTCP_DMX_OK) {
+          o.status = LKF_RTCP_DMX_OK;
+          o.dests = m.dests;
+          o.unrouted = m.unrouted;
+          for (u32 w = 0; w < w1 - w0; w++) o.entries += u32(__popc(bits[w]));
+        } else {  // a malformed packet behind marked ones: the datagram routes to nobody
+          for (u32 w = 0; w < w1 - w0; w++) bits[w] = 0;
+        }
+      }
+    }
+  }
+  A.res[i] = o;
+}
+
+// position k of the ascending-DownTrack order: its row's datagrams, in call order
+template <bool Write>
+__device__ __forceinline__ void dmx_gather(const RtcpDmxLaunch &A, u32 k) {
+  const u32 r = A.byDt[k];
+  CHK(r < A.nrows, CK_DMX_ROW, r, A.nrows);
+  u32 c = 0;
+  if (r < A.nrows) {
+    const RtcpDmxRow row = A.rows[r];
+    const u32 t = row.transport;
+    CHK(t < A.ntransports, CK_DMX_TRANSPORT, t, A.ntransports);
+    if (t < A.ntransports) {
+      const u32 lo = A.tFirst[t], j0 = A.tdFirst[t], j1 = A.tdFirst[t + 1];
+      CHK(lo <= r, CK_DMX_ROW, lo, r);
+      CHK(j0 <= j1 && j1 <= A.n, CK_DMX_DGRAM, j1, A.n);
+      if (lo <= r && j0 <= j1 && j1 <= A.n) {
+        const u32 bit = r - lo;
+        const u64 o = Write ? A.off[k] : 0;
+        for (u32 j = j0; j < j1; j++) {
+          const u32 i = A.tdList[j];
+          CHK(i < A.n, CK_DMX_DGRAM, i, A.n);
+          if (i >= A.n) continue;
+          const u64 w = u64(A.bmOff[i]) + (bit >> 5);
+          CHK(w < A.bmOff[i + 1] && w < A.bmWords, CK_DMX_WORD, w, A.bmWords);
+          if (w >= A.bmOff[i + 1] || w >= A.bmWords) continue;
+          if (!((A.bits[w] >> (bit & 31)) & 1)) continue;
+          if (Write) {
+            CHK(o + c < A.entryCap, CK_DMX_ENTRY, o + c, A.entryCap);
+            if (o + c < A.entryCap) {
+              lkf_rtcp_entry x;
+              x.dt = row.dt;
+              x.dgram = i;
+              A.entries[o + c] = x;
+            }
+          }
+          c++;
+        }
+      }
+    }
+  }
+  if (!Write) A.cnt[k] = c;
+}
+
+__global__ void k_rtcp_dmx_count(RtcpDmxLaunch A) {
+  const u32 k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k < A.nrows) dmx_gather<false>(A, k);
+}
+
+__global__ void k_rtcp_dmx_write(RtcpDmxLaunch A) {
+  const u32 k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k < A.nrows) dmx_gather<true>(A, k);
+}
 }  // namespace
 
 hipError_t launch_rr_update(hipStream_t s, const RrUpdateLaunch &a) {
@@ -335,6 +436,24 @@ hipError_t launch_rtcp_in_write(hipStream_t s, const RtcpInLaunch &a) {
 hipError_t launch_rtcp_in_fold(hipStream_t s, const RtcpInLaunch &a) {
   if (!a.n) return hipSuccess;
   hipLaunchKernelGGL(k_rtcp_in_fold, dim3((a.n + 63) / 64), dim3(64), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_rtcp_dmx_mark(hipStream_t s, const RtcpDmxLaunch &a) {
+  if (!a.n) return hipSuccess;
+  hipLaunchKernelGGL(k_rtcp_dmx_mark, dim3((a.n + 63) / 64), dim3(64), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_rtcp_dmx_count(hipStream_t s, const RtcpDmxLaunch &a) {
+  if (!a.nrows) return hipSuccess;
+  hipLaunchKernelGGL(k_rtcp_dmx_count, dim3((a.nrows + 63) / 64), dim3(64), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_rtcp_dmx_write(hipStream_t s, const RtcpDmxLaunch &a) {
+  if (!a.nrows) return hipSuccess;
+  hipLaunchKernelGGL(k_rtcp_dmx_write, dim3((a.nrows + 63) / 64), dim3(64), 0, s, a);
   return hipGetLastError();
 }
 
