@@ -1287,6 +1287,150 @@ int lkf_ingest_nacks(lkf_engine *e, lkf_rtcp_nack *out, uint32_t cap, lkf_nack_p
  * next ingest on (0 is ignored, as in the reference). */
 int lkf_stream_set_rtt(lkf_engine *e, int32_t stream, uint32_t rtt_ms);
 
+/* ---- the publisher RTCP loop (the RTCP half of buffer.RTPStatsReceiver) ---- *
+ * What a Buffer exchanges with its publisher, over the per-stream state
+ * lkf_stream_rtcp beside the per-packet counters lkf_stream_stats shows:
+ *   mediatrack.go:193-208 -> Buffer.SetSenderReportData -> RTPStatsReceiver.
+ *     SetRtcpSenderReportData (rtpstats_receiver.go:243-322), with
+ *     maybeAdjustFirstPacketTime (rtpstats_base.go:469-515)
+ *                                   lkf_stream_sender_reports / lkf_stream_rtcp_ingest
+ *   Buffer.doReports -> getRTCP -> buildReceptionReport -> GetRtcpReceptionReport
+ *     (buffer.go:688-770, rtpstats_receiver.go:340-396)    lkf_stream_receiver_reports
+ *   Buffer.doNACKs' packets (buffer.go:673-712)            lkf_ingest_nacks_wire
+ * Control-rate calls: each waits for every queued stage (the ingests that write
+ * the streams' state among them), runs on the ingress stream and copies its
+ * results back before it returns.  Nothing of it runs inside lkf_run.
+ *
+ * Times are the virtual clock, as for the DownTrack loop: now_ns is time.Now()
+ * and the sender report's At; time.Since(x) is now_ns - x.  startTime, which
+ * the reference sets beside firstTime at the first packet, is the stream's
+ * first_time_ns as the first of these calls that finds the stream initialized
+ * sees it; only the sender-report path moves first_time_ns after that.
+ *
+ * Parity unpinned: NtpTime.Time() is the definition of
+ * the DownTrack loop above, and two float conversions are amd64 Go's:
+ *   uint8(float32)   the low 8 bits of the value truncated to int32
+ *                    (0x80000000 for NaN and what int32 does not hold): a loss
+ *                    rate of 1.0 gives 256 -> 0
+ *   uint32(float64)  the low 32 bits of the value truncated to int64
+ *                    (0x8000000000000000 for NaN and what int64 does not hold)
+ * Kept from the reference: LastSequenceNumber is uint32(extHighest + 1), not
+ * the highest sequence number received; a sender report's SSRC is not compared
+ * with the stream's (mediatrack.go:204-205 does not); the report blocks inside
+ * a sender report are not read.
+ *
+ * After lkf_remove_track the sender-report calls change nothing and answer
+ * CLOSED; a reception report request answers a record that is not VALID. */
+typedef struct lkf_stream_sr { /* one Buffer.SetSenderReportData(rtp, ntp); 16 B */
+  int32_t stream;
+  uint32_t rtp;
+  uint64_t ntp;
+} lkf_stream_sr;
+#define LKF_SSR_IGNORED_UNINIT 0x01      /* no packet yet: returns at :247 */
+#define LKF_SSR_ANACHRONOUS 0x02         /* NTP behind the newest report's: returns at :252 */
+#define LKF_SSR_CLOCK_SKEW 0x04          /* clockSkewCount++ (:283-297) */
+#define LKF_SSR_RESET_FIRST 0x08         /* extended RTP time behind the newest: srFirst reset, counted (:300-316) */
+#define LKF_SSR_FIRST_TIME_ADJUSTED 0x10 /* maybeAdjustFirstPacketTime moved first_time_ns earlier */
+#define LKF_SSR_ADJUST_TOO_BIG 0x20      /* ... would have, by more than 5 min: refused */
+#define LKF_SSR_CLOSED 0x40              /* the stream's track was removed */
+typedef struct lkf_stream_sr_result { /* 24 B */
+  uint64_t ntp, rtp_ext; /* what was stored as srNewest (0 when nothing was): the host forwards them to
+                            lkf_sender_report (onRtcpSenderReport -> StreamTrackerManager) */
+  uint32_t flags;        /* LKF_SSR_* */
+  uint32_t reserved;
+} lkf_stream_sr_result;
+/* Entries grouped by stream (a stream's entries contiguous, applied in list
+ * order; LKF_EORDER otherwise).  out[i] answers in[i].  The order inside
+ * SetRtcpSenderReportData is the reference's: not initialized; anachronous NTP;
+ * tsCycles from srNewest (the forward-wrap rule); maybeAdjustFirstPacketTime
+ * (writes first_time_ns: within 2 min of startTime, samplesDuration =
+ * int64(float64(int32(rtp - startTS)) / float64(clockRate) * 1e9), earlier
+ * only, by at most 5 min); the clock-skew test against srNewest and srFirst
+ * (each beyond 0.2 s and off by more than 20 %); the reset of srFirst; store. */
+int lkf_stream_sender_reports(lkf_engine *e, const lkf_stream_sr *in, uint32_t n, int64_t now_ns,
+                              lkf_stream_sr_result *out);
+
+typedef struct lkf_stream_rr_req {
+  int32_t stream;
+  uint32_t proxy_fraction_lost; /* Buffer.lastFractionLostToReport (SetLastFractionLostReport; the low 8 bits) */
+} lkf_stream_rr_req;
+#define LKF_SRR_VALID 0x1 /* a report was built; 0: GetRtcpReceptionReport returned nil (the other fields are 0) */
+typedef struct lkf_stream_rr { /* rtcp.ReceptionReport; 40 B */
+  int32_t stream;
+  uint32_t flags;
+  uint32_t ssrc; /* the stream's */
+  uint32_t fraction_lost, total_lost, last_sequence_number, jitter, last_sender_report, delay;
+  uint32_t reserved;
+} lkf_stream_rr;
+/* GetRtcpReceptionReport for each request (each stream at most once;
+ * LKF_EORDER otherwise).  getAndResetSnapshot replaces the snapshot even when
+ * the call then answers nil (nothing expected, or more than 65,536).  The
+ * fraction lost goes through float32 and then takes the proxy value if that is
+ * larger; total_lost saturates at 0xffffff; delay = uint32((now_ns - at) /
+ * 1000 * 65536 / 1000000) in int64.  The host owns the proxy value and the
+ * one-second ReportDelta gate of doReports.  wire32 (NULL: none) receives, per
+ * request, the 32 bytes of rtcp.ReceiverReport{SSRC, one report}.Marshal():
+ * 0x81, PT 201, length 7, the stream's SSRC, the 24-byte block; zeros when the
+ * record is not VALID. */
+int lkf_stream_receiver_reports(lkf_engine *e, const lkf_stream_rr_req *req, uint32_t n, int64_t now_ns,
+                                lkf_stream_rr *out, uint8_t *wire32);
+
+typedef struct lkf_stream_rtcp_raw { /* one rtcpReader.OnPacket(bytes) of stream's Buffer; 12 B */
+  int32_t stream;
+  uint32_t off, len; /* the compound packet in the call's arena; len <= LKF_RTCP_MAX_LEN */
+} lkf_stream_rtcp_raw;
+typedef struct lkf_stream_rtcp_entry { /* ... with datagram dgram's plaintext; 8 B */
+  int32_t stream;
+  uint32_t dgram; /* index into the last lkf_srtcp_unprotect's list */
+} lkf_stream_rtcp_entry;
+typedef struct lkf_stream_rtcp_in_result { /* 32 B */
+  uint32_t status;       /* LKF_RTCP_IN_OK / LKF_RTCP_IN_MALFORMED */
+  uint32_t n_sr;         /* sender report packets of the compound (0 when malformed) */
+  uint32_t flags;        /* the OR of the LKF_SSR_* flags of its sender reports */
+  uint32_t reserved;
+  uint64_t ntp, rtp_ext; /* the last one stored (0: none) */
+} lkf_stream_rtcp_in_result;
+/* The publisher's compound packets from the bytes.  Framing and size checks
+ * are the RTCP ingress table's above, unchanged; a malformed packet anywhere
+ * voids the entry (rtcp.Unmarshal fails before the loop of mediatrack.go:200).
+ * In an OK entry every PT 200 packet, in packet order, is applied as
+ * lkf_stream_sender_reports would apply {stream, bytes 16..19, bytes 8..15};
+ * every other packet type is skipped by its size (SDES: "do nothing for now").
+ * Entries grouped by stream (LKF_EORDER otherwise); an entry beyond arena_len,
+ * with len above LKF_RTCP_MAX_LEN, or a handle out of range is LKF_EINVAL
+ * before anything runs. */
+int lkf_stream_rtcp_ingest(lkf_engine *e, const lkf_stream_rtcp_raw *in, uint32_t n, const uint8_t *arena,
+                           uint64_t arena_len, int64_t now_ns, lkf_stream_rtcp_in_result *out);
+/* ... on the plaintext the last lkf_srtcp_unprotect left on the device (a
+ * rejected datagram is an entry of len 0: MALFORMED); a dgram out of range is
+ * LKF_EINVAL before anything runs. */
+int lkf_stream_rtcp_ingest_unprotected(lkf_engine *e, const lkf_stream_rtcp_entry *in, uint32_t n, int64_t now_ns,
+                                       lkf_stream_rtcp_in_result *out);
+
+typedef struct lkf_stream_rtcp_pkt { /* one marshalled rtcp.TransportLayerNack; 16 B */
+  uint32_t datagram, stream; /* as its lkf_rtcp_nack record */
+  uint32_t off, len;         /* in the call's arena: len = 12 + 4 * n_pairs */
+} lkf_stream_rtcp_pkt;
+/* lkf_ingest_nacks's list as packets, marshalled on the device: record i is
+ * 0x81, PT 205, length 2 + n_pairs, sender SSRC = media SSRC = the stream's,
+ * then its pairs (PID:16, BLP:16), at off = 12 * i + 4 * pair_off[i].  *n_out
+ * and *arena_len are set even when a capacity is too small (LKF_ENOSPC). */
+int lkf_ingest_nacks_wire(lkf_engine *e, lkf_stream_rtcp_pkt *pkts, uint32_t cap, uint8_t *arena, uint64_t arena_cap,
+                          uint32_t *n_out, uint64_t *arena_len);
+
+typedef struct lkf_stream_rtcp { /* 112 B */
+  lkf_rtcp_sr_data sr_first, sr_newest; /* GetSenderReportData; valid 0: nil */
+  uint32_t snapshot_is_valid;           /* the rrSnapshotId snapshot: the fields the reception report reads */
+  uint32_t started;                     /* start_time_ns holds the first packet's time */
+  int64_t snapshot_start_time_ns;
+  uint64_t snapshot_ext_start_sn, snapshot_packets_lost;
+  int64_t start_time_ns;
+  uint32_t clock_skew_count, out_of_order_sender_report_count;
+} lkf_stream_rtcp;
+/* The whole publisher RTCP state of one stream (tests; GetSenderReportData).
+ * Waits for queued work. */
+int lkf_stream_rtcp_get(lkf_engine *e, int32_t stream, lkf_stream_rtcp *out);
+
 /* ---- SRTP unprotect, in front of ingress ---------------------------------- *
  * What a publisher's PeerConnection hands the server is SRTP: in the
  * reference every received packet is authenticated, replay-checked and

@@ -538,6 +538,72 @@ class Engine:
             self._chk(self.api["sender_rtcp_get"](self.h, int(d), out[i:i + 1].ctypes.data), "sender_rtcp_get")
         return out
 
+    # ---- the publisher RTCP loop ----
+    def stream_sender_reports(self, entries, now_ns):
+        """lkf_stream_sender_reports: `entries` an abi.STREAM_SR_DTYPE array
+        {stream, rtp, ntp} grouped by stream -> abi.STREAM_SR_RESULT_DTYPE
+        array (one row per entry)."""
+        ent = np.ascontiguousarray(entries, dtype=abi.STREAM_SR_DTYPE)
+        out = np.zeros(len(ent), dtype=abi.STREAM_SR_RESULT_DTYPE)
+        self._chk(self.api["stream_sender_reports"](self.h, ent.ctypes.data, len(ent), now_ns, out.ctypes.data),
+                  "stream_sender_reports")
+        return out
+
+    def stream_receiver_reports(self, reqs, now_ns, wire=False):
+        """lkf_stream_receiver_reports: `reqs` an abi.STREAM_RR_REQ_DTYPE array
+        -> abi.STREAM_RR_DTYPE array, and with wire=True also a uint8 [n, 32]
+        array of the marshalled rtcp.ReceiverReport packets."""
+        rq = np.ascontiguousarray(reqs, dtype=abi.STREAM_RR_REQ_DTYPE)
+        out = np.zeros(len(rq), dtype=abi.STREAM_RR_DTYPE)
+        w = np.zeros((len(rq), 32), dtype=np.uint8) if wire else None
+        self._chk(self.api["stream_receiver_reports"](self.h, rq.ctypes.data, len(rq), now_ns, out.ctypes.data,
+                                                      w.ctypes.data if wire else None), "stream_receiver_reports")
+        return (out, w) if wire else out
+
+    def stream_rtcp_ingest(self, raws, arena, now_ns):
+        """lkf_stream_rtcp_ingest: `raws` an abi.STREAM_RTCP_RAW_DTYPE array
+        grouped by stream, `arena` the publishers' compound packets (bytes or a
+        uint8 array) -> abi.STREAM_RTCP_IN_RESULT_DTYPE array."""
+        rw = np.ascontiguousarray(raws, dtype=abi.STREAM_RTCP_RAW_DTYPE)
+        ar = np.frombuffer(arena, dtype=np.uint8) if isinstance(arena, (bytes, bytearray)) else \
+            np.ascontiguousarray(arena, dtype=np.uint8)
+        out = np.zeros(len(rw), dtype=abi.STREAM_RTCP_IN_RESULT_DTYPE)
+        self._chk(self.api["stream_rtcp_ingest"](self.h, rw.ctypes.data, len(rw), ar.ctypes.data if len(ar) else None,
+                                                 len(ar), now_ns, out.ctypes.data), "stream_rtcp_ingest")
+        return out
+
+    def stream_rtcp_ingest_unprotected(self, entries, now_ns):
+        """lkf_stream_rtcp_ingest_unprotected: `entries` an
+        abi.STREAM_RTCP_ENTRY_DTYPE array grouped by stream, naming datagrams of
+        the last srtcp_unprotect -> what stream_rtcp_ingest returns."""
+        en = np.ascontiguousarray(entries, dtype=abi.STREAM_RTCP_ENTRY_DTYPE)
+        out = np.zeros(len(en), dtype=abi.STREAM_RTCP_IN_RESULT_DTYPE)
+        self._chk(self.api["stream_rtcp_ingest_unprotected"](self.h, en.ctypes.data, len(en), now_ns,
+                                                             out.ctypes.data), "stream_rtcp_ingest_unprotected")
+        return out
+
+    def ingest_nacks_wire(self):
+        """lkf_ingest_nacks_wire: the last ingest's NACKs as marshalled
+        rtcp.TransportLayerNack packets -> (abi.STREAM_RTCP_PKT_DTYPE array,
+        the packets' bytes as a uint8 array).  Sized by the call itself."""
+        n, alen = C.c_uint32(), C.c_uint64()
+        rc = self.api["ingest_nacks_wire"](self.h, None, 0, None, 0, C.byref(n), C.byref(alen))
+        if rc != -28:  # LKF_ENOSPC: there are packets
+            self._chk(rc, "ingest_nacks_wire")
+        pk = np.zeros(n.value, dtype=abi.STREAM_RTCP_PKT_DTYPE)
+        ar = np.zeros(alen.value, dtype=np.uint8)
+        if n.value:
+            self._chk(self.api["ingest_nacks_wire"](self.h, pk.ctypes.data, len(pk), ar.ctypes.data, len(ar),
+                                                    C.byref(n), C.byref(alen)), "ingest_nacks_wire")
+        return pk, ar
+
+    def stream_rtcp(self, streams):
+        """lkf_stream_rtcp_get for each stream handle in `streams` -> abi.STREAM_RTCP_DTYPE array."""
+        out = np.zeros(len(streams), dtype=abi.STREAM_RTCP_DTYPE)
+        for i, s in enumerate(streams):
+            self._chk(self.api["stream_rtcp_get"](self.h, int(s), out[i:i + 1].ctypes.data), "stream_rtcp_get")
+        return out
+
     def stats(self):
         st = abi.lkf_stats()
         self._chk(self.api["get_stats"](self.h, C.byref(st)), "get_stats")

@@ -264,6 +264,72 @@ assert C.sizeof(lkf_rtcp_fb_result) == 8 == RTCP_FB_RESULT_DTYPE.itemsize
 assert C.sizeof(lkf_rtcp_sr_req) == 8 == RTCP_SR_REQ_DTYPE.itemsize
 assert C.sizeof(lkf_rtcp_sr) == 40 == RTCP_SR_DTYPE.itemsize
 assert C.sizeof(lkf_rtp_delta_info) == 120 == RTP_DELTA_INFO_DTYPE.itemsize
+
+
+# ---- the publisher RTCP loop (lkf_stream_sender_reports / lkf_stream_receiver_reports / lkf_stream_rtcp_ingest) ----
+class lkf_stream_sr(C.Structure):
+    _fields_ = [("stream", C.c_int32), ("rtp", C.c_uint32), ("ntp", C.c_uint64)]
+
+
+class lkf_stream_sr_result(C.Structure):
+    _fields_ = [("ntp", C.c_uint64), ("rtp_ext", C.c_uint64), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class lkf_stream_rr_req(C.Structure):
+    _fields_ = [("stream", C.c_int32), ("proxy_fraction_lost", C.c_uint32)]
+
+
+class lkf_stream_rr(C.Structure):
+    _fields_ = [("stream", C.c_int32)] + [(f, C.c_uint32) for f in (
+        "flags", "ssrc", "fraction_lost", "total_lost", "last_sequence_number", "jitter", "last_sender_report", "delay",
+        "reserved")]
+
+
+class lkf_stream_rtcp_raw(C.Structure):
+    _fields_ = [("stream", C.c_int32), ("off", C.c_uint32), ("len", C.c_uint32)]
+
+
+class lkf_stream_rtcp_entry(C.Structure):
+    _fields_ = [("stream", C.c_int32), ("dgram", C.c_uint32)]
+
+
+class lkf_stream_rtcp_in_result(C.Structure):
+    _fields_ = ([(f, C.c_uint32) for f in ("status", "n_sr", "flags", "reserved")]
+                + [("ntp", C.c_uint64), ("rtp_ext", C.c_uint64)])
+
+
+class lkf_stream_rtcp_pkt(C.Structure):
+    _fields_ = [(f, C.c_uint32) for f in ("datagram", "stream", "off", "len")]
+
+
+class lkf_stream_rtcp(C.Structure):
+    _fields_ = [("sr_first", lkf_rtcp_sr_data), ("sr_newest", lkf_rtcp_sr_data), ("snapshot_is_valid", C.c_uint32),
+                ("started", C.c_uint32), ("snapshot_start_time_ns", C.c_int64), ("snapshot_ext_start_sn", C.c_uint64),
+                ("snapshot_packets_lost", C.c_uint64), ("start_time_ns", C.c_int64), ("clock_skew_count", C.c_uint32),
+                ("out_of_order_sender_report_count", C.c_uint32)]
+
+
+(LKF_SSR_IGNORED_UNINIT, LKF_SSR_ANACHRONOUS, LKF_SSR_CLOCK_SKEW, LKF_SSR_RESET_FIRST, LKF_SSR_FIRST_TIME_ADJUSTED,
+ LKF_SSR_ADJUST_TOO_BIG, LKF_SSR_CLOSED) = (1 << k for k in range(7))
+LKF_SRR_VALID = 0x1
+STREAM_SR_DTYPE = _dtype_of(lkf_stream_sr)
+STREAM_SR_RESULT_DTYPE = _dtype_of(lkf_stream_sr_result)
+STREAM_RR_REQ_DTYPE = _dtype_of(lkf_stream_rr_req)
+STREAM_RR_DTYPE = _dtype_of(lkf_stream_rr)
+STREAM_RTCP_RAW_DTYPE = _dtype_of(lkf_stream_rtcp_raw)
+STREAM_RTCP_ENTRY_DTYPE = _dtype_of(lkf_stream_rtcp_entry)
+STREAM_RTCP_IN_RESULT_DTYPE = _dtype_of(lkf_stream_rtcp_in_result)
+STREAM_RTCP_PKT_DTYPE = _dtype_of(lkf_stream_rtcp_pkt)
+STREAM_RTCP_DTYPE = _dtype_of(lkf_stream_rtcp)
+assert C.sizeof(lkf_stream_sr) == 16 == STREAM_SR_DTYPE.itemsize
+assert C.sizeof(lkf_stream_sr_result) == 24 == STREAM_SR_RESULT_DTYPE.itemsize
+assert C.sizeof(lkf_stream_rr_req) == 8 == STREAM_RR_REQ_DTYPE.itemsize
+assert C.sizeof(lkf_stream_rr) == 40 == STREAM_RR_DTYPE.itemsize
+assert C.sizeof(lkf_stream_rtcp_raw) == 12 == STREAM_RTCP_RAW_DTYPE.itemsize
+assert C.sizeof(lkf_stream_rtcp_entry) == 8 == STREAM_RTCP_ENTRY_DTYPE.itemsize
+assert C.sizeof(lkf_stream_rtcp_in_result) == 32 == STREAM_RTCP_IN_RESULT_DTYPE.itemsize
+assert C.sizeof(lkf_stream_rtcp_pkt) == 16 == STREAM_RTCP_PKT_DTYPE.itemsize
+assert C.sizeof(lkf_stream_rtcp) == 112 == STREAM_RTCP_DTYPE.itemsize
 # NACK -> RTX (lkf_nack / lkf_rtx)
 NACK_DTYPE = np.dtype([("dt", "<i4"), ("sn", "<u2"), ("reserved", "<u2")])
 assert NACK_DTYPE.itemsize == 8
@@ -826,6 +892,19 @@ def bind_engine_api(lib, prefix):
         api["rtcp_demux"] = _bind(lib, prefix + "rtcp_demux", C.c_int,
                                   [e, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
                                    C.c_uint32, P(C.c_uint32)])
+    if hasattr(lib, prefix + "stream_sender_reports"):  # engine only: the publisher RTCP loop
+        api["stream_sender_reports"] = _bind(lib, prefix + "stream_sender_reports", C.c_int,
+                                             [e, C.c_void_p, C.c_uint32, C.c_int64, C.c_void_p])
+        api["stream_receiver_reports"] = _bind(lib, prefix + "stream_receiver_reports", C.c_int,
+                                               [e, C.c_void_p, C.c_uint32, C.c_int64, C.c_void_p, C.c_void_p])
+        api["stream_rtcp_ingest"] = _bind(lib, prefix + "stream_rtcp_ingest", C.c_int,
+                                          [e, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_int64, C.c_void_p])
+        api["stream_rtcp_ingest_unprotected"] = _bind(lib, prefix + "stream_rtcp_ingest_unprotected", C.c_int,
+                                                      [e, C.c_void_p, C.c_uint32, C.c_int64, C.c_void_p])
+        api["ingest_nacks_wire"] = _bind(lib, prefix + "ingest_nacks_wire", C.c_int,
+                                         [e, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, P(C.c_uint32),
+                                          P(C.c_uint64)])
+        api["stream_rtcp_get"] = _bind(lib, prefix + "stream_rtcp_get", C.c_int, [e, C.c_int32, C.c_void_p])
     api["blank_frames"] = _bind(lib, prefix + "blank_frames", C.c_int,
                                 [e, C.c_void_p, C.c_uint32, C.c_int64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64,
                                  P(C.c_uint32), P(C.c_uint64)])

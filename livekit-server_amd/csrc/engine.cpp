@@ -566,6 +566,15 @@ struct lkf_engine {
   DevBuf<uint64_t> dNackPartA;  // the compaction's scan state (side stream)
   DevBuf<lkf_rtcp_nack> dNackOut;
   DevBuf<lkf_nack_pair> dNackPairsOut;
+  // ... and the same list as packets (lkf_ingest_nacks_wire), sized by its totals
+  DevBuf<lkf_stream_rtcp_pkt> dNackPkts;
+  DevBuf<uint8_t> dNackWire;
+  // the publisher RTCP loop (rtcp_kernels.hip k_pub_*): per stream state,
+  // zeroed when the stream is added, and one call's scratch family (input
+  // bytes, group bounds, result bytes) with the compounds' arena beside it
+  DevBuf<StreamRtcp> dStreamRtcp;
+  DevBuf<uint8_t> dPubIn, dPubOut, dPubArena;
+  DevBuf<uint32_t> dPubGroups;
   uint32_t lastIngestN = 0;
   const lkf_raw_pkt *ingRaws = nullptr;  // the last ingest's datagram descriptors (device)
   // speaker ranking tables (rebuilt when topology changes)
@@ -960,6 +969,7 @@ static int flush_topology(lkf_engine *e) {
            "streams upload");
     HIPCHK(hipMemcpy(e->dStreamHot + first, hot.data(), k * sizeof(StreamHot), hipMemcpyHostToDevice),
            "stream state upload");
+    HIPCHK(hipMemset(e->dStreamRtcp + first, 0, k * sizeof(StreamRtcp)), "stream rtcp reset");
     HIPCHK(hipMemset(e->dHist + first * kHistWords, 0, k * kHistWords * sizeof(uint64_t)), "history reset");
     HIPCHK(hipMemset(e->dRxGap + first * kGapWords, 0, k * kGapWords * sizeof(uint32_t)), "gap histogram reset");
     e->pendStreams.clear();
@@ -994,8 +1004,12 @@ static int write_row(lkf_engine *e, T *dst, const T &row, const char *what) {
 //                 protect stages keep overlapping the call
 //   BehindSender  the sender stream, behind every queued stage that updates
 //                 RTPStatsSender (sender_after_queued)
+//   Ingress       the ingest stream, which owns the streams' receive state,
+//                 every stream drained first as for Quiesced (the NACK queues
+//                 and bucket copies of an ingest run on other streams);
+//                 blocking uploads, closed by uploaded()
 static int rebuild_twcc(lkf_engine *e);
-enum class Order { Quiesced, BehindDecide, BehindSender };
+enum class Order { Quiesced, BehindDecide, BehindSender, Ingress };
 
 struct Frame {
   lkf_engine *e;
@@ -1006,12 +1020,16 @@ struct Frame {
   Frame(lkf_engine *eng, Order o)
       : e(eng),
         order(o),
-        s(o == Order::Quiesced ? eng->own.get() : o == Order::BehindDecide ? eng->decS.get() : eng->sendS.get()) {}
+        s(o == Order::Quiesced       ? eng->own.get()
+          : o == Order::BehindDecide ? eng->decS.get()
+          : o == Order::Ingress      ? eng->ingS.get()
+                                     : eng->sendS.get()) {}
+  bool drained() const { return order == Order::Quiesced || order == Order::Ingress; }
 
   // flush: the pending topology first; twcc: then the transport-wide counters'
   // lists of a transport-cc DownTrack added or bound since the last run
   int open(bool flush = true, bool twcc = false) {
-    if (order == Order::Quiesced) return quiesce(e, flush);
+    if (drained()) return quiesce(e, flush);
     if (flush)
       if (const int rc = flush_topology(e)) return rc;
     HIPCHK(hipSetDevice(e->dev), "hipSetDevice");
@@ -1038,16 +1056,16 @@ struct Frame {
     return r ? fail(e, what, static_cast<hipError_t>(r)) : LKF_OK;
   }
 
-  // host -> device: ahead of the frame's kernels on its stream; Quiesced: a
-  // blocking copy (uploaded() after the last one, before the first launch)
+  // host -> device: ahead of the frame's kernels on its stream; Quiesced and
+  // Ingress: a blocking copy (uploaded() after the last one, before the first launch)
   int up(void *dst, const void *src, size_t bytes, const char *what) {
-    if (order == Order::Quiesced)
+    if (drained())
       HIPCHK(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice), what);
     else
       HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s), what);
     return LKF_OK;
   }
-  int uploaded() { return order == Order::Quiesced ? upload_done(e) : LKF_OK; }
+  int uploaded() { return drained() ? upload_done(e) : LKF_OK; }
 
   // device -> host, range-checked, behind the frame's kernels: dst holds the
   // bytes after wait().  (Once the stream is idle a call may also copy with
@@ -1204,6 +1222,7 @@ lkf_engine *lkf_create(int hip_device, const lkf_cfg *cfg) {
   e->maxStreams = c.max_streams ? c.max_streams : 3 * c.max_tracks;
   A(e->dStreams.alloc(e->maxStreams));
   A(e->dStreamHot.alloc(e->maxStreams));
+  A(e->dStreamRtcp.alloc(e->maxStreams));
   A(e->dHist.alloc(size_t(e->maxStreams) * kHistWords));
   A(e->dRxGap.alloc(size_t(e->maxStreams) * kGapWords));
   A(e->dStreamRings.alloc(size_t(e->maxStreams) * kRangeCap));
@@ -1239,6 +1258,7 @@ lkf_engine *lkf_create(int hip_device, const lkf_cfg *cfg) {
     A(hipMemset(e->dSeqDDIdx, 0xff, size_t(c.max_downtracks) * sizeof(uint32_t)));
     A(hipMemset(e->dTracks, 0, size_t(c.max_tracks) * sizeof(DevTrack)));
     A(hipMemset(e->dStreamHot, 0, size_t(e->maxStreams) * sizeof(StreamHot)));
+    A(hipMemset(e->dStreamRtcp, 0, size_t(e->maxStreams) * sizeof(StreamRtcp)));
     A(hipMemset(e->dStreamRings, 0, size_t(e->maxStreams) * kRangeCap * sizeof(RangeEntry)));
     A(hipMemset(e->dHist, 0, size_t(e->maxStreams) * kHistWords * sizeof(uint64_t)));
     {  // VideoAllocationDefault (forwarder.go:111-116)
@@ -4992,22 +5012,31 @@ int lkf_stream_stats_get(lkf_engine *e, int32_t sid, lkf_stream_stats *o) {
   return LKF_OK;
 }
 
-int lkf_ingest_nacks(lkf_engine *e, lkf_rtcp_nack *out, uint32_t cap, lkf_nack_pair *pairs, uint32_t pair_cap,
-                     uint32_t *n_out, uint32_t *n_pairs_out) {
-  if (!e || !n_out || !n_pairs_out) return LKF_EINVAL;
-  *n_out = *n_pairs_out = 0;
+// The last ingest's NACK records and pairs compacted in datagram order into
+// dNackOut / dNackPairsOut, on the side stream (behind the NACK queues of the
+// ingest that produced them), which is idle on return; tot = {records, pairs}.
+static int nack_compact_run(lkf_engine *e, uint64_t tot[2]) {
+  tot[0] = tot[1] = 0;
   HIPCHK(hipSetDevice(e->dev), "hipSetDevice");
   if (!e->dNack || !e->lastIngestN) return LKF_OK;
   const uint32_t n = e->lastIngestN;
-  hipStream_t ps = e->sideS;  // after the NACK queues of the ingest that produced them (same stream)
+  hipStream_t ps = e->sideS;
   const lkf_engine::IngSet &g = e->ing[e->ingPar];  // the last ingest's set
   HIPCHK(launch_nack_compact(ps, n, e->ingRaws, e->dStreams, g.nackInfo, g.nackPairOff, g.nackPairs,
                              e->dNackPartA, nullptr, e->dNackRecPos, e->dNackPairPos, e->dNackTot, e->dNackOut, e->dNackPairsOut),
          "nack compact");
-  uint64_t tot[2] = {0, 0};
-  CHKRANGE(e->dNackTot, sizeof(tot), "async d2h");
-  HIPCHK(hipMemcpyAsync(tot, e->dNackTot, sizeof(tot), hipMemcpyDeviceToHost, ps), "nack totals");
+  CHKRANGE(e->dNackTot, 2 * sizeof(uint64_t), "async d2h");
+  HIPCHK(hipMemcpyAsync(tot, e->dNackTot, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, ps), "nack totals");
   HIPCHK(hipStreamSynchronize(ps), "nack sync");
+  return LKF_OK;
+}
+
+int lkf_ingest_nacks(lkf_engine *e, lkf_rtcp_nack *out, uint32_t cap, lkf_nack_pair *pairs, uint32_t pair_cap,
+                     uint32_t *n_out, uint32_t *n_pairs_out) {
+  if (!e || !n_out || !n_pairs_out) return LKF_EINVAL;
+  *n_out = *n_pairs_out = 0;
+  uint64_t tot[2] = {0, 0};
+  STEP(nack_compact_run(e, tot));
   *n_out = uint32_t(tot[0]);
   *n_pairs_out = uint32_t(tot[1]);
   if (tot[0] > cap || tot[1] > pair_cap) return LKF_ENOSPC;
@@ -5017,6 +5046,190 @@ int lkf_ingest_nacks(lkf_engine *e, lkf_rtcp_nack *out, uint32_t cap, lkf_nack_p
   if (tot[1])
     D2H(pairs, e->dNackPairsOut, tot[1] * sizeof(lkf_nack_pair), "nack pairs");
   return LKF_OK;
+}
+
+// The same list as rtcp.TransportLayerNack packets (k_nack_wire): record i at
+// 12 * i + 4 * pair_off[i], so the arena is 12 * records + 4 * pairs bytes.
+int lkf_ingest_nacks_wire(lkf_engine *e, lkf_stream_rtcp_pkt *pkts, uint32_t cap, uint8_t *arena, uint64_t arena_cap,
+                          uint32_t *n_out, uint64_t *arena_len) {
+  if (!e || !n_out || !arena_len) return LKF_EINVAL;
+  *n_out = 0;
+  *arena_len = 0;
+  uint64_t tot[2] = {0, 0};
+  STEP(nack_compact_run(e, tot));
+  const uint64_t bytes = 12 * tot[0] + 4 * tot[1];
+  if (bytes > 0xffffffffull) {
+    e->err = "NACK packets of one ingest exceed 2^32 - 1 bytes";
+    return LKF_EINVAL;
+  }
+  *n_out = uint32_t(tot[0]);
+  *arena_len = bytes;
+  if (tot[0] > cap || bytes > arena_cap) return LKF_ENOSPC;
+  if (!tot[0]) return LKF_OK;
+  if (!pkts || !arena) return LKF_EINVAL;
+  // (the side stream is idle: the buffers grow without a wait)
+  HIPCHK(e->dNackPkts.reserve(tot[0], 1024), "alloc nack packets");
+  HIPCHK(e->dNackWire.reserve(bytes, 1 << 16), "alloc nack wire");
+  NackWireLaunch a;
+  a.recs = e->dNackOut;
+  a.n = uint32_t(tot[0]);
+  a.pairs = e->dNackPairsOut;
+  a.npairs = tot[1];
+  a.pkts = e->dNackPkts;
+  a.arena = e->dNackWire;
+  a.arenaCap = e->dNackWire.cap();
+  HIPCHK(launch_nack_wire(e->sideS, a), "nack wire");
+  HIPCHK(hipStreamSynchronize(e->sideS), "nack wire sync");
+  D2H(pkts, e->dNackPkts, tot[0] * sizeof(lkf_stream_rtcp_pkt), "nack packets");
+  D2H(arena, e->dNackWire, bytes, "nack wire bytes");
+  return LKF_OK;
+}
+
+// ---- the publisher RTCP loop (rtcp_kernels.hip k_pub_*; the semantics are pub_rtcp_device.h) ----
+static_assert(sizeof(lkf_stream_rtcp) == sizeof(StreamRtcp), "lkf_stream_rtcp is StreamRtcp's layout");
+static_assert(offsetof(lkf_stream_rtcp, sr_newest) == offsetof(StreamRtcp, srNewest) &&
+                  offsetof(lkf_stream_rtcp, snapshot_ext_start_sn) == offsetof(StreamRtcp, snapExtStartSN) &&
+                  offsetof(lkf_stream_rtcp, start_time_ns) == offsetof(StreamRtcp, startTime) &&
+                  offsetof(lkf_stream_rtcp, clock_skew_count) == offsetof(StreamRtcp, clockSkewCount),
+              "lkf_stream_rtcp is StreamRtcp's layout");
+static_assert(sizeof(lkf_stream_sr) == 16 && sizeof(lkf_stream_sr_result) == 24 && sizeof(lkf_stream_rr_req) == 8 &&
+                  sizeof(lkf_stream_rr) == 40 && sizeof(lkf_stream_rtcp_raw) == 12 &&
+                  sizeof(lkf_stream_rtcp_entry) == 8 && sizeof(lkf_stream_rtcp_in_result) == 32 &&
+                  sizeof(lkf_stream_rtcp_pkt) == 16,
+              "publisher RTCP call records");
+
+int lkf_stream_rtcp_get(lkf_engine *e, int32_t sid, lkf_stream_rtcp *out) {
+  if (!e || !out || sid < 0 || sid >= int32_t(e->streams.size())) return LKF_EINVAL;
+  STEP(quiesce(e));
+  D2H(out, e->dStreamRtcp + sid, sizeof(*out), "stream rtcp copy");
+  return LKF_OK;
+}
+
+// The calls' frame is Order::Ingress: every queued stage waited for, the
+// kernels on the ingest stream.  Their scratch is one family: input bytes,
+// group bounds, result bytes; the compounds' arena is a family of its own.
+static int pub_grow(Frame &f, size_t inBytes, size_t groups, size_t outBytes) {
+  lkf_engine *e = f.e;
+  return f.grow("alloc stream rtcp scratch", want(e->dPubIn, inBytes, 1 << 16, 2 * inBytes),
+                want(e->dPubGroups, groups, 4096, 2 * groups), want(e->dPubOut, outBytes, 1 << 16, 2 * outBytes));
+}
+
+int lkf_stream_sender_reports(lkf_engine *e, const lkf_stream_sr *in, uint32_t n, int64_t now_ns,
+                              lkf_stream_sr_result *out) {
+  if (!e || (n && (!in || !out))) return LKF_EINVAL;
+  if (!n) return LKF_OK;
+  // groups: one per stream's contiguous entries (a stream must not reappear)
+  std::vector<uint32_t> g;
+  STEP(check_handles(&in[0].stream, sizeof(*in), n, e->streams.size(), {Repeat::Groups, &g, true}));
+  Frame f(e, Order::Ingress);
+  STEP(f.open());
+  STEP(pub_grow(f, size_t(n) * sizeof(lkf_stream_sr), g.size(), size_t(n) * sizeof(lkf_stream_sr_result)));
+  STEP(f.up(e->dPubIn, in, size_t(n) * sizeof(lkf_stream_sr), "stream sr copy"));
+  STEP(f.up(e->dPubGroups, g.data(), g.size() * sizeof(uint32_t), "stream groups copy"));
+  STEP(f.uploaded());
+  PubSrLaunch a{};
+  a.sr = reinterpret_cast<const lkf_stream_sr *>(e->dPubIn.get());
+  a.n = n;
+  a.gBegin = e->dPubGroups;
+  a.ngroups = uint32_t(g.size() - 1);
+  a.now = now_ns;
+  a.streams = e->dStreams;
+  a.hot = e->dStreamHot;
+  a.rtcp = e->dStreamRtcp;
+  a.nstreams = uint32_t(e->streams.size());
+  a.srOut = reinterpret_cast<lkf_stream_sr_result *>(e->dPubOut.get());
+  HIPCHK(launch_pub_sr_apply(f.s, a), "stream sr apply");
+  STEP(f.down(out, e->dPubOut, size_t(n) * sizeof(lkf_stream_sr_result), "stream sr results copy"));
+  return f.wait();
+}
+
+int lkf_stream_receiver_reports(lkf_engine *e, const lkf_stream_rr_req *req, uint32_t n, int64_t now_ns,
+                                lkf_stream_rr *out, uint8_t *wire32) {
+  if (!e || (n && (!req || !out))) return LKF_EINVAL;
+  if (!n) return LKF_OK;
+  // one thread per request: a stream's state has one writer
+  STEP(check_handles(&req[0].stream, sizeof(*req), n, e->streams.size(), {Repeat::DistinctEorder}));
+  // results: n records (40 B each, so the wire bytes behind them stay 4-B aligned), then 32 B per request
+  const size_t recBytes = size_t(n) * sizeof(lkf_stream_rr), wireBytes = wire32 ? size_t(n) * 32 : 0;
+  Frame f(e, Order::Ingress);
+  STEP(f.open());
+  STEP(pub_grow(f, size_t(n) * sizeof(lkf_stream_rr_req), 0, recBytes + wireBytes));
+  STEP(f.up(e->dPubIn, req, size_t(n) * sizeof(lkf_stream_rr_req), "stream rr requests copy"));
+  STEP(f.uploaded());
+  PubRrLaunch a{};
+  a.req = reinterpret_cast<const lkf_stream_rr_req *>(e->dPubIn.get());
+  a.n = n;
+  a.now = now_ns;
+  a.streams = e->dStreams;
+  a.hot = e->dStreamHot;
+  a.rtcp = e->dStreamRtcp;
+  a.nstreams = uint32_t(e->streams.size());
+  a.out = reinterpret_cast<lkf_stream_rr *>(e->dPubOut.get());
+  a.wire = wire32 ? e->dPubOut.get() + recBytes : nullptr;
+  HIPCHK(launch_pub_rr_build(f.s, a), "stream rr build");
+  STEP(f.down(out, e->dPubOut, recBytes, "stream rr results copy"));
+  STEP(f.wait());
+  if (wire32) D2H(wire32, e->dPubOut.get() + recBytes, wireBytes, "stream rr wire copy");
+  return LKF_OK;
+}
+
+// `arena`: the compound packets in host memory, uploaded first; NULL: they are
+// the arena_len bytes at dArena already (lkf_stream_rtcp_ingest_unprotected).
+static int stream_rtcp_ingest_run(lkf_engine *e, const lkf_stream_rtcp_raw *in, uint32_t n, const uint8_t *arena,
+                                  const uint8_t *dArena, uint64_t arena_len, int64_t now_ns,
+                                  lkf_stream_rtcp_in_result *out) {
+  if (!e || (n && (!in || !out)) || (arena_len && !arena && !dArena)) return LKF_EINVAL;
+  if (!n) return LKF_OK;
+  std::vector<uint32_t> g;
+  STEP(check_handles(&in[0].stream, sizeof(*in), n, e->streams.size(), {Repeat::Groups, &g, true}, [&](uint32_t i) {
+    return in[i].len <= LKF_RTCP_MAX_LEN && uint64_t(in[i].off) + in[i].len <= arena_len;
+  }));
+  Frame f(e, Order::Ingress);
+  STEP(f.open());
+  STEP(pub_grow(f, size_t(n) * sizeof(lkf_stream_rtcp_raw), g.size(), size_t(n) * sizeof(lkf_stream_rtcp_in_result)));
+  if (arena) STEP(f.grow("alloc stream rtcp arena", want(e->dPubArena, arena_len, 1 << 16, 2 * arena_len)));
+  STEP(f.up(e->dPubIn, in, size_t(n) * sizeof(lkf_stream_rtcp_raw), "stream rtcp raw copy"));
+  if (arena && arena_len) STEP(f.up(e->dPubArena, arena, arena_len, "stream rtcp arena copy"));
+  STEP(f.up(e->dPubGroups, g.data(), g.size() * sizeof(uint32_t), "stream groups copy"));
+  STEP(f.uploaded());
+  PubSrLaunch a{};
+  a.raw = reinterpret_cast<const lkf_stream_rtcp_raw *>(e->dPubIn.get());
+  a.n = n;
+  a.arena = arena ? e->dPubArena.get() : dArena;
+  a.arenaLen = arena_len;
+  a.gBegin = e->dPubGroups;
+  a.ngroups = uint32_t(g.size() - 1);
+  a.now = now_ns;
+  a.streams = e->dStreams;
+  a.hot = e->dStreamHot;
+  a.rtcp = e->dStreamRtcp;
+  a.nstreams = uint32_t(e->streams.size());
+  a.res = reinterpret_cast<lkf_stream_rtcp_in_result *>(e->dPubOut.get());
+  HIPCHK(launch_pub_rtcp_check(f.s, a), "stream rtcp check");
+  HIPCHK(launch_pub_sr_apply(f.s, a), "stream sr apply");
+  STEP(f.down(out, e->dPubOut, size_t(n) * sizeof(lkf_stream_rtcp_in_result), "stream rtcp results copy"));
+  return f.wait();
+}
+
+int lkf_stream_rtcp_ingest(lkf_engine *e, const lkf_stream_rtcp_raw *in, uint32_t n, const uint8_t *arena,
+                           uint64_t arena_len, int64_t now_ns, lkf_stream_rtcp_in_result *out) {
+  if (arena_len && !arena) return LKF_EINVAL;
+  static const uint8_t none = 0;  // (an empty arena is still the caller's)
+  return stream_rtcp_ingest_run(e, in, n, arena ? arena : &none, nullptr, arena_len, now_ns, out);
+}
+
+int lkf_stream_rtcp_ingest_unprotected(lkf_engine *e, const lkf_stream_rtcp_entry *in, uint32_t n, int64_t now_ns,
+                                       lkf_stream_rtcp_in_result *out) {
+  if (!e || (n && !in)) return LKF_EINVAL;
+  std::vector<lkf_stream_rtcp_raw> raw(n);
+  for (uint32_t i = 0; i < n; i++) {
+    if (in[i].dgram >= e->scOff.size()) return LKF_EINVAL;
+    const uint32_t len = e->scLen[in[i].dgram];  // (a rejected datagram: an empty entry at the arena's start)
+    raw[i] = lkf_stream_rtcp_raw{in[i].stream, len ? e->scOff[in[i].dgram] : 0u, len};
+  }
+  static const uint8_t none = 0;  // (no datagram was accepted yet: every entry has len 0)
+  const uint8_t *host = e->dScPlain ? nullptr : &none;
+  return stream_rtcp_ingest_run(e, raw.data(), n, host, e->dScPlain, host ? 0 : e->scPlainLen, now_ns, out);
 }
 
 int lkf_stream_set_rtt(lkf_engine *e, int32_t sid, uint32_t rtt_ms) {

@@ -466,6 +466,36 @@ struct alignas(16) StreamHot {  // per-stream ingress state (256 B)
 };
 static_assert(sizeof(StreamHot) == 256, "StreamHot must be 256 B");
 
+// The RTCP half of a stream's RTPStatsReceiver (pub_rtcp_device.h,
+// rtcp_kernels.hip k_pub_*): what SetRtcpSenderReportData and
+// GetRtcpReceptionReport keep beside the per-packet counters of StreamHot
+// (rtpstats_receiver.go:243-396, rtpstats_base.go:170-191).  One per stream,
+// zeroed when it is added; the layout is lkf_stream_rtcp's (include/lkfwd.h).
+// Kept apart from StreamHot, which the stream wave rewrites every ingest.
+// Times are ns of the engine's virtual clock, 0 = the zero time.
+// startTime: the reference sets it, like firstTime, at the first packet
+// (rtpstats_receiver.go:104-107); the engine takes StreamHot.firstTime, captured
+// here (started = 1) the first time a publisher RTCP call sees S_INIT set.
+// From then on only the sender-report path (maybeAdjustFirstPacketTime) changes
+// firstTime, so the captured value is the original.
+// The one snapshot is Buffer's rrSnapshotId, only the fields the reception
+// report reads.  Buffer takes the id at Bind, before the first packet, and
+// Update initialises it with initSnapshot(startTime, extStart); the lazy
+// initialisation of getAndResetSnapshot (snapIsValid 0) yields the same value:
+// the Buffer's statistics run with IsRestartAllowed false, so the extended
+// start does not move between the first packet and the first report (checked:
+// rtpstats_receiver.go:63-64, wraparound.go:150).
+struct alignas(16) StreamRtcp {
+  RtcpSrData srFirst, srNewest;
+  uint32_t snapIsValid;
+  uint32_t started;  // startTime holds the first packet's time
+  int64_t snapStartTime;
+  uint64_t snapExtStartSN, snapPacketsLost;
+  int64_t startTime;
+  uint32_t clockSkewCount, outOfOrderSenderReportCount;
+};
+static_assert(sizeof(StreamRtcp) == 112, "StreamRtcp is 112 B");
+
 // One stream's NACK queue: mediatransportutil nack.NackQueue with
 // NackQueueParamsDefault (MaxTries 5, CacheSize 100, MinInterval 20 ms,
 // MaxInterval 400 ms, BackoffFactor 1.25) as buffer.Buffer drives it

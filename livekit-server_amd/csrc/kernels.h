@@ -668,11 +668,64 @@ struct RtcpDmxLaunch {
 hipError_t launch_rtcp_dmx_mark(hipStream_t s, const RtcpDmxLaunch &a);
 hipError_t launch_rtcp_dmx_count(hipStream_t s, const RtcpDmxLaunch &a);
 hipError_t launch_rtcp_dmx_write(hipStream_t s, const RtcpDmxLaunch &a);
+// ---- the publisher RTCP loop (lkf_stream_*; the semantics are pub_rtcp_device.h) ----
+// Sender reports in, as structs (lkf_stream_sender_reports: sr, srOut) or as
+// the publisher's compound packets (lkf_stream_rtcp_ingest: raw, arena, res).
+//   k_pub_rtcp_check  one lane per byte entry: walks the compound, writes the
+//                     status and the sender-report count into res
+//   k_pub_sr_apply    one lane per stream group: its entries in list order; a
+//                     byte entry that checked OK is walked again and each
+//                     sender report applied as it is met (no intermediate list)
+struct PubSrLaunch {
+  const lkf_stream_sr *sr;         // struct entries, or nullptr
+  const lkf_stream_rtcp_raw *raw;  // byte entries, or nullptr
+  uint32_t n;
+  const uint8_t *arena;
+  uint64_t arenaLen;
+  const uint32_t *gBegin;  // ngroups + 1
+  uint32_t ngroups;
+  int64_t now;
+  const DevStream *streams;
+  StreamHot *hot;  // firstTime is written (maybeAdjustFirstPacketTime)
+  StreamRtcp *rtcp;
+  uint32_t nstreams;
+  lkf_stream_sr_result *srOut;     // per struct entry
+  lkf_stream_rtcp_in_result *res;  // per byte entry
+};
+hipError_t launch_pub_rtcp_check(hipStream_t s, const PubSrLaunch &a);
+hipError_t launch_pub_sr_apply(hipStream_t s, const PubSrLaunch &a);
+// k_pub_rr_build: one thread per request (each stream at most once)
+struct PubRrLaunch {
+  const lkf_stream_rr_req *req;
+  uint32_t n;
+  int64_t now;
+  const DevStream *streams;
+  const StreamHot *hot;
+  StreamRtcp *rtcp;
+  uint32_t nstreams;
+  lkf_stream_rr *out;
+  uint8_t *wire;  // 32 B per request, or nullptr
+};
+hipError_t launch_pub_rr_build(hipStream_t s, const PubRrLaunch &a);
+// k_nack_wire: one lane per record of the compacted NACK list
+// (launch_nack_compact's outRecs / outPairs): its packet at 12 * i + 4 * pair_off
+struct NackWireLaunch {
+  const lkf_rtcp_nack *recs;
+  uint32_t n;
+  const lkf_nack_pair *pairs;
+  uint64_t npairs;
+  lkf_stream_rtcp_pkt *pkts;  // n
+  uint8_t *arena;
+  uint64_t arenaCap;  // bytes allocated
+};
+hipError_t launch_nack_wire(hipStream_t s, const NackWireLaunch &a);
+
 // -DLKF_CHECKED=1 builds of rtcp_kernels.hip: its own {violations, first site,
 // index, capacity} (sites 101 DownTrack handle, 102 ring slot, 103 entry /
 // request index, 104 arena byte, 105 / 106 / 107 fb / NACK / ref list index,
 // 108 routing-table row, 109 transport, 110 bitmap word, 111 datagram index,
-// 112 demux entry index); lkf_debug_check folds it into the record
+// 112 demux entry index, 113 stream handle, 114 NACK pair index); lkf_debug_check
+// folds it into the record
 hipError_t read_check_rtcp(unsigned long long out[4], int reset);
 
 }  // namespace lkf

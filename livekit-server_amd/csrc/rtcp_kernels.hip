@@ -24,15 +24,26 @@
 //                   a bitmap row of its own; one lane per DownTrack of the
 //                   table then counts and, behind a scan, writes its {dt,
 //                   dgram} entries in datagram order.  No atomics, no sort.
+//   k_pub_*        the publisher RTCP loop (lkf_stream_*): one lane per compound
+//                   checks its framing and counts its sender reports; one lane
+//                   per stream group then applies the group's sender reports
+//                   in list order (SetRtcpSenderReportData, rtpstats_receiver.go
+//                   :243-322, with maybeAdjustFirstPacketTime), a byte entry's
+//                   as the second walk meets them; one thread per request
+//                   builds a reception report (:340-396) and its 32 bytes.
+//   k_nack_wire     one lane per record of the last ingest's NACK list: its
+//                   rtcp.TransportLayerNack at 12 * i + 4 * pair_off (the
+//                   list's own prefix: no scan, no atomics).
 //
-// The semantics are rtcp_device.h's, rtcp_in_device.h's and rtcp_dmx_device.h's
-// (shared with the host unit programs).
+// The semantics are rtcp_device.h's, rtcp_in_device.h's, rtcp_dmx_device.h's
+// and pub_rtcp_device.h's (shared with the host unit programs).
 #include <hip/hip_runtime.h>
 
 #include "kernels.h"
 #include "rtcp_device.h"
 #include "rtcp_in_device.h"
 #include "rtcp_dmx_device.h"
+#include "pub_rtcp_device.h"
 
 namespace lkf {
 namespace {
@@ -59,7 +70,9 @@ enum : u32 {
   CK_DMX_TRANSPORT = 109,
   CK_DMX_WORD = 110,
   CK_DMX_DGRAM = 111,
-  CK_DMX_ENTRY = 112
+  CK_DMX_ENTRY = 112,
+  CK_PUB_STREAM = 113,
+  CK_NACK_PAIR = 114
 };
 #if LKF_CHECKED
 __device__ unsigned long long g_chk_rtcp[4];
@@ -401,6 +414,107 @@ __global__ void k_rtcp_dmx_write(RtcpDmxLaunch A) {
   const u32 k = blockIdx.x * blockDim.x + threadIdx.x;
   if (k < A.nrows) dmx_gather<true>(A, k);
 }
+
+// ---- the publisher RTCP loop (lkf_stream_*): pub_rtcp_device.h's semantics ----
+__global__ void k_pub_rtcp_check(PubSrLaunch A) {
+  const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= A.n) return;
+  const lkf_stream_rtcp_raw r = A.raw[i];
+  CHK(u64(r.off) + r.len <= A.arenaLen, CK_RTCP_ARENA, u64(r.off) + r.len, A.arenaLen);
+  lkf_stream_rtcp_in_result o = {};
+  o.status = LKF_RTCP_IN_MALFORMED;
+  if (u64(r.off) + r.len <= A.arenaLen) {
+    pubrtcp::CountSr c;
+    if (pubrtcp::walk(A.arena + r.off, r.len, c) == LKF_RTCP_IN_OK) {
+      o.status = LKF_RTCP_IN_OK;
+      o.n_sr = c.n;
+    }
+  }
+  A.res[i] = o;
+}
+
+__global__ void k_pub_sr_apply(PubSrLaunch A) {
+  const u32 g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= A.ngroups) return;
+  const u32 b = A.gBegin[g], e = A.gBegin[g + 1];
+  CHK(e <= A.n, CK_RTCP_ENTRY, e, A.n);
+  if (b >= e || e > A.n) return;
+  const u32 sid = u32(A.sr ? A.sr[b].stream : A.raw[b].stream);
+  CHK(sid < A.nstreams, CK_PUB_STREAM, sid, A.nstreams);
+  if (sid >= A.nstreams) return;
+  StreamRtcp R = A.rtcp[sid];
+  StreamHot &hot = A.hot[sid];
+  // the four members the semantics read, and the one they write
+  StreamHot H;
+  H.flags = hot.flags;
+  H.tsStart = hot.tsStart;
+  H.firstTime = hot.firstTime;
+  const i64 firstTime0 = H.firstTime;
+  const DevStream D = A.streams[sid];
+  for (u32 i = b; i < e; i++) {
+    if (A.sr) {
+      lkf_stream_sr_result o;
+      pubrtcp::set_sender_report(R, H, D, A.sr[i].rtp, A.sr[i].ntp, A.now, o);
+      A.srOut[i] = o;
+    } else {
+      lkf_stream_rtcp_in_result o = A.res[i];
+      const lkf_stream_rtcp_raw r = A.raw[i];
+      if (o.status == LKF_RTCP_IN_OK && u64(r.off) + r.len <= A.arenaLen) {
+        pubrtcp::ApplySr ap{R, H, D, A.now, o};
+        pubrtcp::walk(A.arena + r.off, r.len, ap);
+        A.res[i] = o;
+      }
+    }
+  }
+  A.rtcp[sid] = R;
+  if (H.firstTime != firstTime0) hot.firstTime = H.firstTime;
+}
+
+__global__ void k_pub_rr_build(PubRrLaunch A) {
+  const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= A.n) return;
+  const lkf_stream_rr_req q = A.req[i];
+  const u32 sid = u32(q.stream);
+  CHK(sid < A.nstreams, CK_PUB_STREAM, sid, A.nstreams);
+  if (sid >= A.nstreams) return;
+  StreamRtcp R = A.rtcp[sid];
+  const StreamHot &hot = A.hot[sid];
+  StreamHot H;
+  H.flags = hot.flags;
+  H.firstTime = hot.firstTime;
+  H.snStart = hot.snStart;
+  H.snExtHighest = hot.snExtHighest;
+  H.packetsLost = hot.packetsLost;
+  H.jitter = hot.jitter;
+  lkf_stream_rr o;
+  pubrtcp::reception_report(R, H, A.streams[sid], q.stream, q.proxy_fraction_lost, A.now, o);
+  A.rtcp[sid] = R;
+  A.out[i] = o;
+  if (A.wire) {  // 32 B per request: 4-B aligned, big-endian words
+    u32 *w = reinterpret_cast<u32 *>(A.wire + size_t(i) * 32);
+    for (int k = 0; k < 8; k++) w[k] = __builtin_bswap32(pubrtcp::receiver_report_word(o, k));
+  }
+}
+
+__global__ void k_nack_wire(NackWireLaunch A) {
+  const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= A.n) return;
+  const lkf_rtcp_nack r = A.recs[i];
+  const u64 off = pubrtcp::nack_wire_off(i, r.pair_off);
+  const u32 len = pubrtcp::nack_wire_len(r.n_pairs);
+  lkf_stream_rtcp_pkt p;
+  p.datagram = r.datagram;
+  p.stream = r.stream;
+  p.off = u32(off);
+  p.len = len;
+  A.pkts[i] = p;
+  CHK(off + len <= A.arenaCap, CK_RTCP_ARENA, off + len, A.arenaCap);
+  CHK(u64(r.pair_off) + r.n_pairs <= A.npairs, CK_NACK_PAIR, u64(r.pair_off) + r.n_pairs, A.npairs);
+  if (off + len > A.arenaCap || u64(r.pair_off) + r.n_pairs > A.npairs) return;
+  u32 *w = reinterpret_cast<u32 *>(A.arena + off);  // (every offset is a multiple of 4)
+  const lkf_nack_pair *pairs = A.pairs + r.pair_off;
+  for (u32 k = 0; k < 3u + r.n_pairs; k++) w[k] = __builtin_bswap32(pubrtcp::nack_wire_word(r, pairs, k));
+}
 }  // namespace
 
 hipError_t launch_rr_update(hipStream_t s, const RrUpdateLaunch &a) {
@@ -454,6 +568,30 @@ hipError_t launch_rtcp_dmx_count(hipStream_t s, const RtcpDmxLaunch &a) {
 hipError_t launch_rtcp_dmx_write(hipStream_t s, const RtcpDmxLaunch &a) {
   if (!a.nrows) return hipSuccess;
   hipLaunchKernelGGL(k_rtcp_dmx_write, dim3((a.nrows + 63) / 64), dim3(64), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_pub_rtcp_check(hipStream_t s, const PubSrLaunch &a) {
+  if (!a.n || !a.raw) return hipSuccess;
+  hipLaunchKernelGGL(k_pub_rtcp_check, dim3((a.n + 63) / 64), dim3(64), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_pub_sr_apply(hipStream_t s, const PubSrLaunch &a) {
+  if (!a.ngroups) return hipSuccess;
+  hipLaunchKernelGGL(k_pub_sr_apply, dim3((a.ngroups + 63) / 64), dim3(64), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_pub_rr_build(hipStream_t s, const PubRrLaunch &a) {
+  if (!a.n) return hipSuccess;
+  hipLaunchKernelGGL(k_pub_rr_build, dim3((a.n + 63) / 64), dim3(64), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_nack_wire(hipStream_t s, const NackWireLaunch &a) {
+  if (!a.n) return hipSuccess;
+  hipLaunchKernelGGL(k_nack_wire, dim3((a.n + 63) / 64), dim3(64), 0, s, a);
   return hipGetLastError();
 }
 
