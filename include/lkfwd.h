@@ -1287,6 +1287,54 @@ int lkf_ingest_nacks(lkf_engine *e, lkf_rtcp_nack *out, uint32_t cap, lkf_nack_p
  * next ingest on (0 is ignored, as in the reference). */
 int lkf_stream_set_rtt(lkf_engine *e, int32_t stream, uint32_t rtt_ms);
 
+/* ---- ingress frame rate (Buffer.doFpsCalc, buffer.go:518-543) ------------- *
+ * The PictureID frame-rate calculators of buffer/fps.go:24-315 over the
+ * ExtPackets an ingest produces, per stream and opt-in: FrameRateCalculatorVP8
+ * (one calculator, row 0) for a VP8 track, FrameRateCalculatorVP9 (one per
+ * spatial layer; complete only when all three are, fps.go:271-280, so a
+ * one-spatial VP9 stream never completes, as in the reference) for a VP9
+ * track.  A datagram counts when it produced an ExtPacket (LKF_FLOW_FORWARD)
+ * with a non-empty payload on a stream that is neither closed nor already
+ * calculated; Buffer.paused has no counterpart in the engine (a host that
+ * pauses a Buffer does not ingest its datagrams).
+ *   Buffer.GetTemporalLayerFpsForSpatial (buffer.go:857-866)   lkf_stream_fps_get: fps[s]
+ *   Buffer.OnFpsChanged (buffer.go:535-540)                    lkf_ingest_fps_changed
+ * One divergence: two distinct frames at temporal layer 3 make the reference
+ * index minFramesForCalculation out of range and panic (fps.go:155); here no
+ * rate is computed for temporal 3 and a stream that keeps sending such frames
+ * never completes.
+ * Not built: FrameRateCalculatorDD (fps.go:319-570), so a stream with a
+ * dependency-descriptor extension is refused. */
+#define LKF_FPS_NONE 0 /* never enabled */
+#define LKF_FPS_VP8 1
+#define LKF_FPS_VP9 2
+typedef struct lkf_fps_calc { /* one frameRateCalculatorVPx (fps.go:44-53), 24 B */
+  uint64_t present;  /* bit j: fnReceived[j] is set */
+  int8_t first[4];   /* firstFrames[t] as a slot of fnReceived, -1: nil */
+  int8_t second[4];  /* secondFrames[t] */
+  uint16_t base_fn;  /* baseFrame.fn */
+  uint8_t has_base;
+  uint8_t reserved;
+  uint32_t resets;   /* reset() calls, the one on completion included */
+} lkf_fps_calc;
+typedef struct lkf_stream_fps { /* 128 B */
+  float fps[3][4];      /* GetTemporalLayerFpsForSpatial(s)[t]; VP8: row 0 */
+  uint32_t kind;        /* LKF_FPS_* */
+  uint8_t calculated;   /* Buffer.frameRateCalculated */
+  uint8_t completed[3]; /* per calculator */
+  lkf_fps_calc calc[3];
+} lkf_stream_fps;
+/* Enables the calculators on a stream from the next ingest on.  LKF_EINVAL: a
+ * bad handle, an audio stream, a track codec other than VP8 / VP9, or a stream
+ * with dd_ext != 0.  Idempotent. */
+int lkf_stream_fps_enable(lkf_engine *e, int32_t stream);
+/* Waits for queued work.  A closed stream answers its last state, a stream
+ * that was never enabled kind = LKF_FPS_NONE and all zero. */
+int lkf_stream_fps_get(lkf_engine *e, int32_t stream, lkf_stream_fps *out);
+/* The streams that became calculated during the last ingest (the onFpsChanged
+ * calls), ascending.  n_out is set even when cap is too small (LKF_ENOSPC). */
+int lkf_ingest_fps_changed(lkf_engine *e, int32_t *streams, uint32_t cap, uint32_t *n_out);
+
 /* ---- the publisher RTCP loop (the RTCP half of buffer.RTPStatsReceiver) ---- *
  * What a Buffer exchanges with its publisher, over the per-stream state
  * lkf_stream_rtcp beside the per-packet counters lkf_stream_stats shows:

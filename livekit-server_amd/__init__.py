@@ -597,6 +597,31 @@ class Engine:
                                                     C.byref(n), C.byref(alen)), "ingest_nacks_wire")
         return pk, ar
 
+    def stream_fps_enable(self, stream):
+        """lkf_stream_fps_enable: the VP8 / VP9 frame-rate calculators of a
+        received stream, from the next ingest on."""
+        self._chk(self.api["stream_fps_enable"](self.h, int(stream)), "stream_fps_enable")
+
+    def stream_fps_get(self, stream):
+        """lkf_stream_fps_get -> abi.lkf_stream_fps (fps[s][t] =
+        GetTemporalLayerFpsForSpatial(s)[t]; as_dict() for exact compares)."""
+        st = abi.lkf_stream_fps()
+        self._chk(self.api["stream_fps_get"](self.h, int(stream), C.byref(st)), "stream_fps_get")
+        return st
+
+    def ingest_fps_changed(self):
+        """lkf_ingest_fps_changed: the streams that became calculated during
+        the last ingest (OnFpsChanged), ascending, as a list of handles."""
+        n = C.c_uint32()
+        rc = self.api["ingest_fps_changed"](self.h, None, 0, C.byref(n))
+        if rc != -28:  # LKF_ENOSPC: there are streams
+            self._chk(rc, "ingest_fps_changed")
+        out = np.zeros(n.value, dtype=np.int32)
+        if n.value:
+            self._chk(self.api["ingest_fps_changed"](self.h, out.ctypes.data, len(out), C.byref(n)),
+                      "ingest_fps_changed")
+        return [int(x) for x in out[:n.value]]
+
     def stream_rtcp(self, streams):
         """lkf_stream_rtcp_get for each stream handle in `streams` -> abi.STREAM_RTCP_DTYPE array."""
         out = np.zeros(len(streams), dtype=abi.STREAM_RTCP_DTYPE)

@@ -309,6 +309,30 @@ class lkf_stream_rtcp(C.Structure):
                 ("out_of_order_sender_report_count", C.c_uint32)]
 
 
+LKF_FPS_NONE, LKF_FPS_VP8, LKF_FPS_VP9 = 0, 1, 2
+
+
+class lkf_fps_calc(C.Structure):
+    _fields_ = [("present", C.c_uint64), ("first", C.c_int8 * 4), ("second", C.c_int8 * 4), ("base_fn", C.c_uint16),
+                ("has_base", C.c_uint8), ("reserved", C.c_uint8), ("resets", C.c_uint32)]
+
+
+class lkf_stream_fps(C.Structure):
+    _fields_ = [("fps", (C.c_float * 4) * 3), ("kind", C.c_uint32), ("calculated", C.c_uint8),
+                ("completed", C.c_uint8 * 3), ("calc", lkf_fps_calc * 3)]
+
+    def as_dict(self):
+        """Every field, the rates as binary32 bits (compared exactly)."""
+        import struct
+        return {
+            "kind": self.kind, "calculated": self.calculated, "completed": tuple(self.completed),
+            "fps_bits": tuple(tuple(struct.unpack("<I", struct.pack("<f", v))[0] for v in row) for row in self.fps),
+            "calc": tuple((c.present, tuple(c.first), tuple(c.second), c.base_fn, c.has_base, c.resets)
+                          for c in self.calc)}
+
+
+assert C.sizeof(lkf_fps_calc) == 24 and C.sizeof(lkf_stream_fps) == 128
+
 (LKF_SSR_IGNORED_UNINIT, LKF_SSR_ANACHRONOUS, LKF_SSR_CLOCK_SKEW, LKF_SSR_RESET_FIRST, LKF_SSR_FIRST_TIME_ADJUSTED,
  LKF_SSR_ADJUST_TOO_BIG, LKF_SSR_CLOSED) = (1 << k for k in range(7))
 LKF_SRR_VALID = 0x1
@@ -905,6 +929,11 @@ def bind_engine_api(lib, prefix):
                                          [e, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, P(C.c_uint32),
                                           P(C.c_uint64)])
         api["stream_rtcp_get"] = _bind(lib, prefix + "stream_rtcp_get", C.c_int, [e, C.c_int32, C.c_void_p])
+    if hasattr(lib, prefix + "stream_fps_enable"):  # engine only: the ingress frame-rate calculators
+        api["stream_fps_enable"] = _bind(lib, prefix + "stream_fps_enable", C.c_int, [e, C.c_int32])
+        api["stream_fps_get"] = _bind(lib, prefix + "stream_fps_get", C.c_int, [e, C.c_int32, P(lkf_stream_fps)])
+        api["ingest_fps_changed"] = _bind(lib, prefix + "ingest_fps_changed", C.c_int,
+                                          [e, C.c_void_p, C.c_uint32, P(C.c_uint32)])
     api["blank_frames"] = _bind(lib, prefix + "blank_frames", C.c_int,
                                 [e, C.c_void_p, C.c_uint32, C.c_int64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64,
                                  P(C.c_uint32), P(C.c_uint64)])

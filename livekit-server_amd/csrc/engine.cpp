@@ -575,6 +575,16 @@ struct lkf_engine {
   DevBuf<StreamRtcp> dStreamRtcp;
   DevBuf<uint8_t> dPubIn, dPubOut, dPubArena;
   DevBuf<uint32_t> dPubGroups;
+  // Ingress frame rate (k_ing_fps; allocated with the first stream it is
+  // enabled on): the enabled streams in enable order — their handles, the
+  // number of the ingest that completed each (0: not yet) and their
+  // calculators.  The three grow together; k_ing_fps (side stream) is the
+  // only kernel that touches them.
+  std::vector<int32_t> fpsHandles;
+  std::vector<int32_t> fpsIdx;  // stream handle -> position in fpsHandles (-1 or beyond the end: not enabled)
+  DevBuf<uint32_t> dFpsList, dFpsCalcAt;
+  DevBuf<fps::State> dFps;
+  uint32_t fpsEpoch = 0;  // ingests counted since the first enable
   uint32_t lastIngestN = 0;
   const lkf_raw_pkt *ingRaws = nullptr;  // the last ingest's datagram descriptors (device)
   // speaker ranking tables (rebuilt when topology changes)
@@ -4632,6 +4642,14 @@ static int ingest_common(lkf_engine *e, BatchCtx &x, const lkf_raw_pkt *dRaws, u
   a.nackPairCap = e->nackPairCap;
   a.nackIn = g.nackIn;
   a.nackAlone = e->knobs.nackAlone;
+  if (!e->fpsHandles.empty()) {  // (an empty ingest counts too: it completes nothing)
+    a.nfps = uint32_t(e->fpsHandles.size());
+    a.fpsList = e->dFpsList;
+    a.fpsCalcAt = e->dFpsCalcAt;
+    a.fpsStates = e->dFps;
+    if (!++e->fpsEpoch) e->fpsEpoch = 1;  // (0 means "not yet" in dFpsCalcAt)
+    a.fpsEpoch = e->fpsEpoch;
+  }
   BucketLaunch bl;
   if (e->bktSlots && e->bktStorePending) {  // a second ingest before lkf_run: the first one's copies read this
                                             // context's store list first
@@ -5045,6 +5063,107 @@ int lkf_ingest_nacks(lkf_engine *e, lkf_rtcp_nack *out, uint32_t cap, lkf_nack_p
   if (tot[0]) D2H(out, e->dNackOut, tot[0] * sizeof(lkf_rtcp_nack), "nack records");
   if (tot[1])
     D2H(pairs, e->dNackPairsOut, tot[1] * sizeof(lkf_nack_pair), "nack pairs");
+  return LKF_OK;
+}
+
+// ---- ingress frame rate (ingress_kernels.hip k_ing_fps; the semantics are fps_device.h) ----
+static_assert(LKF_FPS_NONE == fps::KIND_NONE && LKF_FPS_VP8 == fps::KIND_VP8 && LKF_FPS_VP9 == fps::KIND_VP9,
+              "LKF_FPS_* are fps::KIND_*");
+static_assert(sizeof(lkf_stream_fps) == 128 && sizeof(lkf_fps_calc) == 24, "lkf_stream_fps is 128 B");
+
+static int fps_index(const lkf_engine *e, int32_t stream) {
+  return size_t(stream) < e->fpsIdx.size() ? e->fpsIdx[stream] : -1;
+}
+
+int lkf_stream_fps_enable(lkf_engine *e, int32_t stream) {
+  if (!e || stream < 0 || stream >= int32_t(e->streams.size())) return LKF_EINVAL;
+  const lkf_stream_params &sp = e->streams[stream];
+  const lkf_track_params &tp = e->tracks[sp.track];
+  // buffer.go:216-227: a calculator exists for video/vp8 and video/vp9; a
+  // Buffer with a DD parser gets FrameRateCalculatorDD (buffer.go:193-198), which is not built
+  if (tp.kind != LKF_KIND_VIDEO || (tp.codec != LKF_CODEC_VP8 && tp.codec != LKF_CODEC_VP9) || sp.dd_ext)
+    return LKF_EINVAL;
+  if (fps_index(e, stream) >= 0) return LKF_OK;
+  HIPCHK(hipSetDevice(e->dev), "hipSetDevice");
+  const size_t n = e->fpsHandles.size();
+  if (n + 1 > e->dFps.cap()) {  // grow: queued k_ing_fps launches hold the old pointers
+    STEP(drain_streams(e));
+    const size_t cap = std::max<size_t>(64, 2 * (n + 1));
+    DevBuf<uint32_t> list, at;
+    DevBuf<fps::State> st;
+    HIPCHK(list.alloc(cap), "alloc fps list");
+    HIPCHK(at.alloc(cap), "alloc fps epochs");
+    HIPCHK(st.alloc(cap), "alloc fps state");
+    if (n) {
+      HIPCHK(hipMemcpy(list, e->dFpsList, n * sizeof(uint32_t), hipMemcpyDeviceToDevice), "fps list copy");
+      HIPCHK(hipMemcpy(at, e->dFpsCalcAt, n * sizeof(uint32_t), hipMemcpyDeviceToDevice), "fps epochs copy");
+      HIPCHK(hipMemcpy(st, e->dFps, n * sizeof(fps::State), hipMemcpyDeviceToDevice), "fps state copy");
+    }
+    e->dFpsList = std::move(list);
+    e->dFpsCalcAt = std::move(at);
+    e->dFps = std::move(st);
+  }
+  // (entry n is beyond every queued launch's grid: no wait)
+  fps::State s;
+  std::memset(&s, 0, sizeof(s));
+  s.kind = tp.codec == LKF_CODEC_VP8 ? fps::KIND_VP8 : fps::KIND_VP9;
+  s.clockRate = tp.clock_rate;
+  s.stream = uint32_t(stream);
+  const uint32_t h = uint32_t(stream), zero = 0;
+  HIPCHK(hipMemcpy(e->dFps + n, &s, sizeof(s), hipMemcpyHostToDevice), "fps state init");
+  HIPCHK(hipMemcpy(e->dFpsList + n, &h, sizeof(h), hipMemcpyHostToDevice), "fps list entry");
+  HIPCHK(hipMemcpy(e->dFpsCalcAt + n, &zero, sizeof(zero), hipMemcpyHostToDevice), "fps epoch entry");
+  if (e->fpsIdx.size() <= size_t(stream)) e->fpsIdx.resize(size_t(stream) + 1, -1);
+  e->fpsIdx[stream] = int32_t(n);
+  e->fpsHandles.push_back(stream);
+  return LKF_OK;
+}
+
+int lkf_stream_fps_get(lkf_engine *e, int32_t stream, lkf_stream_fps *o) {
+  if (!e || !o || stream < 0 || stream >= int32_t(e->streams.size())) return LKF_EINVAL;
+  std::memset(o, 0, sizeof(*o));
+  const int idx = fps_index(e, stream);
+  if (idx < 0) return LKF_OK;  // LKF_FPS_NONE
+  STEP(quiesce(e));
+  fps::State s;
+  D2H(&s, e->dFps + idx, sizeof(s), "fps state copy");
+  o->kind = s.kind;
+  o->calculated = uint8_t(s.calculated);
+  for (int c = 0; c < fps::kSpatial; c++) {
+    const fps::Head &h = s.c[c].h;
+    lkf_fps_calc &k = o->calc[c];
+    o->completed[c] = h.completed;
+    k.present = h.present;
+    k.base_fn = h.baseFn;
+    k.has_base = h.hasBase;
+    k.resets = h.resets;
+    for (int t = 0; t < fps::kTemporal; t++) {
+      o->fps[c][t] = h.rate[t];
+      k.first[t] = int8_t(int(fps::slot_of(h.first, t)) - 1);
+      k.second[t] = int8_t(int(fps::slot_of(h.second, t)) - 1);
+    }
+  }
+  return LKF_OK;
+}
+
+int lkf_ingest_fps_changed(lkf_engine *e, int32_t *streams, uint32_t cap, uint32_t *n_out) {
+  if (!e || !n_out) return LKF_EINVAL;
+  *n_out = 0;
+  const size_t n = e->fpsHandles.size();
+  if (!n || !e->fpsEpoch) return LKF_OK;
+  HIPCHK(hipSetDevice(e->dev), "hipSetDevice");
+  HIPCHK(hipStreamSynchronize(e->ingS), "sync ingest stream");
+  HIPCHK(hipStreamSynchronize(e->sideS), "sync side stream");  // (the calculators of the last ingest)
+  std::vector<uint32_t> at(n);
+  D2H(at.data(), e->dFpsCalcAt, n * sizeof(uint32_t), "fps epochs copy");
+  std::vector<int32_t> hit;
+  for (size_t i = 0; i < n; i++)
+    if (at[i] == e->fpsEpoch) hit.push_back(e->fpsHandles[i]);
+  std::sort(hit.begin(), hit.end());
+  *n_out = uint32_t(hit.size());
+  if (hit.size() > cap) return LKF_ENOSPC;
+  if (!hit.empty() && !streams) return LKF_EINVAL;
+  if (!hit.empty()) std::memcpy(streams, hit.data(), hit.size() * sizeof(int32_t));
   return LKF_OK;
 }
 

@@ -17,6 +17,9 @@
 //                  AddPacketWithSequenceNumber (:471-481), getExtPacket's
 //                  dependency descriptor (:599-671); in-order runs lane-parallel
 //   k_ing_nack     (side stream) the NackQueue per stream
+//   k_ing_fps      (side stream) one wave per stream with frame-rate
+//                  calculation enabled: doFpsCalc (buffer.go:518-543) over
+//                  the VP8 / VP9 PictureID calculators of fps_device.h
 //   scan           positions of the ExtPackets produced
 //   k_ing_out      thread per datagram: the ExtPacket (getExtPacket
 //                  buffer.go:599-671) as an lkf_pkt of the forwarding batch
@@ -31,6 +34,7 @@
 
 #include "../../include/lkfwd.h"
 #include "dd_device.h"
+#include "fps_device.h"
 #include "fwd_state.h"
 #include "kernels.h"
 
@@ -2837,6 +2841,136 @@ __global__ void k_bwe_pack(RoomPackLaunch a) {
 // ---------------------------------------------------------------------------
 // launch wrappers
 // ---------------------------------------------------------------------------
+// ---------------------------------------------------------------------------
+// k_ing_fps: Buffer.doFpsCalc (buffer.go:518-543) for the streams it was
+// enabled on (lkf_stream_fps_enable), one wave per entry of the compact list
+// of their handles.  The calculators are fps_device.h: the wave is the 64-frame
+// window, lane j holding slot j's timestamp and temporal layer; the heads are
+// wave-uniform.  The packet walk is serial (a recurrence) but fed lane-parallel:
+// the stream's datagram list is loaded 64 at a time, filtered by flow flags and
+// payload length, the VP9 PictureID bytes fetched, and the survivors walked
+// through their ballot with readlane.  A VP9 stream's three calculators are
+// independent of each other, so each chunk is walked once per spatial layer;
+// the stream is calculated when all are complete (fps.go:271-280), which is at
+// the packet that completed the last one.  calcAt[i] != 0 (the number of the
+// ingest that completed entry i): one load, one compare, nothing else.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ fps::Head fps_load_head(const fps::Calc *c, u32 lane) {
+  // 12 words by 12 lanes, then wave-uniform through readlane
+  const u32 *p = reinterpret_cast<const u32 *>(&c->h);
+  const u32 v = lane < sizeof(fps::Head) / 4 ? p[lane] : 0u;
+  auto w = [&](int i) { return u32(__builtin_amdgcn_readlane(int(v), i)); };
+  fps::Head h;
+  h.present = u64(w(0)) | (u64(w(1)) << 32);
+#pragma unroll
+  for (int t = 0; t < fps::kTemporal; t++) h.rate[t] = __uint_as_float(w(2 + t));
+  h.first = w(6);
+  h.second = w(7);
+  const u32 b = w(8);
+  h.baseFn = u16(b);
+  h.hasBase = u8(b >> 16);
+  h.completed = u8(b >> 24);
+  h.resets = w(9);
+  h.pad[0] = h.pad[1] = 0;
+  return h;
+}
+static_assert(__builtin_offsetof(fps::Head, rate) == 8 && __builtin_offsetof(fps::Head, first) == 24 &&
+                  __builtin_offsetof(fps::Head, baseFn) == 32 && __builtin_offsetof(fps::Head, hasBase) == 34 &&
+                  __builtin_offsetof(fps::Head, completed) == 35 && __builtin_offsetof(fps::Head, resets) == 36,
+              "fps_load_head reads Head by word");
+
+__global__ void __launch_bounds__(64) k_ing_fps(const lkf_raw_pkt *__restrict__ raws, const IngParsed *__restrict__ q,
+                                                const lkf_flow *__restrict__ flows,
+                                                const DevStream *__restrict__ streams, const u8 *__restrict__ raw,
+                                                const u32 *__restrict__ tBegin, const u32 *__restrict__ tEnd,
+                                                const u32 *__restrict__ list, const u32 *__restrict__ cnt, u32 stride,
+                                                const u32 *__restrict__ handles, u32 *__restrict__ calcAt,
+                                                fps::State *__restrict__ states, u32 epoch) {
+  const u32 i = blockIdx.x, lane = threadIdx.x;
+  if (calcAt[i]) return;  // frameRateCalculated (buffer.go:519)
+  const u32 sid = handles[i];
+  const DevStream *const sp = streams + sid;
+  if (sp->closed) return;
+  const u32 track = sp->track;
+  const i32 layer = sp->layer;
+  const u32 pb = tBegin[track], pe = tEnd[track];
+  if (pb >= pe) return;  // no datagram of its track
+  const bool useList = layer >= 0 && layer < 3;  // (k_ing_lists lists only these)
+  const u32 nIdx = useList ? cnt[track * 3 + u32(layer)] : pe - pb;
+  const u32 *lst = list + size_t(useList ? layer : 0) * stride + pb;
+  fps::State *const g = states + i;
+  const u32 kind = g->kind, clockRate = g->clockRate;
+  const int nc = kind == fps::KIND_VP9 ? fps::kSpatial : 1;
+  fps::Head h[fps::kSpatial];
+  fps::WaveWin w[fps::kSpatial];
+#pragma unroll
+  for (int c = 0; c < fps::kSpatial; c++) {
+    h[c] = fps::Head{};
+    w[c] = fps::WaveWin{0, 0, lane};
+    if (c < nc) {
+      h[c] = fps_load_head(&g->c[c], lane);
+      w[c].ts = g->c[c].ts[lane];
+      w[c].temporal = g->c[c].temporal[lane];
+    }
+  }
+  bool dirty = false;  // wave-uniform: a packet reached a calculator
+  for (u32 base = 0; base < nIdx; base += 64) {
+    const u32 k = base + lane;
+    bool ok = false;
+    u32 fn = 0, ts = 0, tmp = 0, spl = 0;
+    if (k < nIdx) {
+      const u32 ic = useList ? lst[k] : pb + k;
+      const lkf_raw_pkt rp = raws[ic];
+      const IngParsed p = q[ic];
+      // an ExtPacket with a payload (buffer.go:485-490, :519), of this stream
+      ok = rp.stream == sid && (flows[ic].flags & LKF_FLOW_FORWARD) && p.payloadLen != 0;
+      ts = p.ts;
+      tmp = p.tid;
+      if (kind == fps::KIND_VP8) {  // ep.Payload.(VP8): PictureID, TID (fps.go:211-216)
+        ok = ok && (p.flags & IP_VP8);
+        fn = p.pid;  // (0 when the I bit is clear: vp8_parse)
+      } else {       // ep.Payload.(codecs.VP9Packet): Spatial = SID (buffer.go:651-654, fps.go:264-269)
+        ok = ok && (p.flags & IP_VP9) && p.sid < fps::kSpatial;
+        spl = p.sid;
+        if (ok) {  // (the descriptor parsed: its PictureID bytes are inside the payload)
+          const u8 *pl = raw + rp.off + p.hdrSize;
+          const u8 b0 = pl[0];
+          const u8 b1 = p.payloadLen > 1 ? pl[1] : u8(0), b2 = p.payloadLen > 2 ? pl[2] : u8(0);
+          fn = fps::vp9_picture_id(b0, b1, b2);
+        }
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < fps::kSpatial; c++) {
+      if (c >= nc) continue;
+      u64 m = __ballot(ok && spl == u32(c));
+      while (m && !h[c].completed) {
+        const int x = __ffsll((long long)m) - 1;
+        m &= m - 1;
+        const u32 fx = u32(__builtin_amdgcn_readlane(int(fn), x));
+        const u32 tx = u32(__builtin_amdgcn_readlane(int(ts), x));
+        const u32 lx = u32(__builtin_amdgcn_readlane(int(tmp), x));
+        (void)fps::recv(h[c], w[c], u16(fx), tx, i32(lx), clockRate);
+        dirty = true;
+      }
+    }
+  }
+  if (!dirty) return;
+  bool all = true;
+#pragma unroll
+  for (int c = 0; c < fps::kSpatial; c++) {
+    if (c >= nc) continue;
+    if (lane == 0) g->c[c].h = h[c];
+    g->c[c].ts[lane] = w[c].ts;
+    g->c[c].temporal[lane] = u8(w[c].temporal);
+    all = all && h[c].completed;
+  }
+  if (all && lane == 0) {  // every calculator complete: frameRateCalculated, onFpsChanged (buffer.go:535-540)
+    g->calculated = 1;
+    calcAt[i] = epoch;
+  }
+}
+
 static u32 nblk(u64 n, u32 t) { return u32((n + t - 1) / t); }
 
 // Zeroes an ingest's per-track ranges, error words, ExtPacket total and (with
@@ -2866,7 +3000,8 @@ __global__ void k_nack_init(u32 n, u32 *__restrict__ info, u32 *__restrict__ pai
 }
 
 // The ingest chain on st (the prep stream: the next lkf_run's batch depends on
-// it).  The NACK queues (k_ing_nack) need only the flows: they run on `side`
+// it).  The NACK queues (k_ing_nack) need only the flows, the frame-rate
+// calculators (k_ing_fps) the flows and the parsed datagrams: they run on `side`
 // after the stream kernel, beside the bucket decisions, the ExtPacket scan and
 // the run's preparation; `sideDone` is recorded after them (the next ingest
 // waits for it: it rewrites the parsed datagrams, flows and lists they read).
@@ -2905,21 +3040,27 @@ hipError_t launch_ingest(hipStream_t st, const IngestLaunch &a, hipStream_t side
                          a.hot, a.hist, a.rings, a.tBegin, a.tEnd, a.flows, a.fwd, a.raw, a.ddStates, a.ddStructs,
                          a.ingDD, a.err, a.list, a.listCnt, a.listStride, bka, a.rxGap, a.nack ? a.nackIn : nullptr, a.nstreams, sper);
   }
-  if (a.nack && a.nstreams) {  // after the flows: the loss ranges it pushes
+  if ((a.nack || a.nfps) && a.nstreams) {  // after the flows: the loss ranges and ExtPacket flags they read
     hipError_t r = hipEventRecord(sideFork, st);
     if (r == hipSuccess) r = hipStreamWaitEvent(side, sideFork, 0);
     if (r != hipSuccess) return r;
-    hipLaunchKernelGGL(k_nack_init, dim3(std::min<u32>(nblk(a.n, 256), 1024)), dim3(256), 0, side, a.n, a.nackInfo,
-                       a.nackPairCnt);
-    // (the lane-parallel form needs >= LKF_NACK_FAST_MIN datagrams in a stream)
+    if (a.nack) {
+      hipLaunchKernelGGL(k_nack_init, dim3(std::min<u32>(nblk(a.n, 256), 1024)), dim3(256), 0, side, a.n, a.nackInfo,
+                         a.nackPairCnt);
+      // (the lane-parallel form needs >= LKF_NACK_FAST_MIN datagrams in a stream)
 #define NACK_ARGS                                                                                              \
   a.raws, a.parsed, a.flows, a.streams, a.nack, a.hot, a.tBegin, a.tEnd, a.list, a.listCnt, a.listStride, a.nackInfo, \
       a.nackPairOff, a.nackPairCnt, a.nackPairs, a.nackPairCap, a.err, a.nackIn
-    if (u64(a.n) >= u64(LKF_NACK_FAST_MIN) * a.nstreams)
-      hipLaunchKernelGGL(k_ing_nack<true>, dim3(a.nstreams), dim3(64), 0, side, NACK_ARGS);
-    else
-      hipLaunchKernelGGL(k_ing_nack<false>, dim3(a.nstreams), dim3(64), 0, side, NACK_ARGS);
+      if (u64(a.n) >= u64(LKF_NACK_FAST_MIN) * a.nstreams)
+        hipLaunchKernelGGL(k_ing_nack<true>, dim3(a.nstreams), dim3(64), 0, side, NACK_ARGS);
+      else
+        hipLaunchKernelGGL(k_ing_nack<false>, dim3(a.nstreams), dim3(64), 0, side, NACK_ARGS);
 #undef NACK_ARGS
+    }
+    if (a.nfps)  // the frame-rate calculators of the streams that have them enabled
+      hipLaunchKernelGGL(k_ing_fps, dim3(a.nfps), dim3(64), 0, side, a.raws, a.parsed, a.flows, a.streams, a.raw,
+                         a.tBegin, a.tEnd, a.list, a.listCnt, a.listStride, a.fpsList, a.fpsCalcAt, a.fpsStates,
+                         a.fpsEpoch);
     r = hipEventRecord(sideDone, side);
     if (r != hipSuccess) return r;
     *sideUsed = true;

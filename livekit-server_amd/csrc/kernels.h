@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/lkfwd.h"
+#include "fps_device.h"
 #include "fwd_state.h"
 #include "srtcp_device.h"
 #include "srtp_rx_device.h"
@@ -160,6 +161,15 @@ struct IngestLaunch {
   lkf_nack_pair *nackPairs;
   uint32_t nackPairCap;
   NackIn *nackIn;  // 3 * listStride records (nullptr: the NACK kernel reads the raw arrays)
+  // frame-rate calculators (k_ing_fps; nfps 0: no stream has them enabled and
+  // nothing is launched): the enabled streams' handles, per entry the number
+  // of the ingest that completed it (0: not yet) and its state; fpsEpoch is
+  // this ingest's number (from 1)
+  uint32_t nfps = 0;
+  const uint32_t *fpsList = nullptr;
+  uint32_t *fpsCalcAt = nullptr;
+  fps::State *fpsStates = nullptr;
+  uint32_t fpsEpoch = 0;
   const BucketLaunch *bucket = nullptr;  // the RTX buckets (nullptr: none)
   // (measurement, LKF_NACK_ALONE=1) the rest of the ingest waits for the NACK
   // queues, so a kernel trace times k_ing_nack with the GPU to itself
@@ -241,8 +251,9 @@ struct SpeakersLaunch {
   uint32_t *counts;
 };
 
-// the ingest chain on s; with NACK queues k_ing_nack forks onto `side` after the
-// stream kernel (*sideUsed: sideDone was recorded there)
+// the ingest chain on s; with NACK queues or enabled frame-rate calculators
+// k_ing_nack / k_ing_fps fork onto `side` after the stream kernel (*sideUsed:
+// sideDone was recorded there)
 hipError_t launch_ingest(hipStream_t s, const IngestLaunch &a, hipStream_t side, hipEvent_t sideFork,
                          hipEvent_t sideDone, bool *sideUsed);
 hipError_t launch_speakers(hipStream_t s, const SpeakersLaunch &a);
