@@ -1303,11 +1303,20 @@ int lkf_stream_set_rtt(lkf_engine *e, int32_t stream, uint32_t rtt_ms);
  * index minFramesForCalculation out of range and panic (fps.go:155); here no
  * rate is computed for temporal 3 and a stream that keeps sending such frames
  * never completes.
- * Not built: FrameRateCalculatorDD (fps.go:319-570), so a stream with a
- * dependency-descriptor extension is refused. */
+ * A stream with a dependency-descriptor extension (dd_ext != 0: AV1 and VP9
+ * SVC, VP8 with a descriptor) has FrameRateCalculatorDD instead (fps.go:319-570,
+ * buffer.go:191-201), whatever its codec: one calculator for all three
+ * frameRateCalculator[] entries over a 256-frame window, fed the frame diffs
+ * of every ExtPacket that has a payload and a parsed descriptor, its max layer
+ * set where DependencyDescriptorParser.Parse calls onMaxLayerChanged
+ * (dependencydescriptorparser.go:138-156).  lkf_stream_fps_enable refuses such
+ * a stream; lkf_stream_fps_enable_dd turns its calculator on.  The same
+ * divergence holds (no rate for temporal 3), and a max layer beyond (2, 3),
+ * where the reference indexes frameRates out of range, never completes. */
 #define LKF_FPS_NONE 0 /* never enabled */
 #define LKF_FPS_VP8 1
 #define LKF_FPS_VP9 2
+#define LKF_FPS_DD 3
 typedef struct lkf_fps_calc { /* one frameRateCalculatorVPx (fps.go:44-53), 24 B */
   uint64_t present;  /* bit j: fnReceived[j] is set */
   int8_t first[4];   /* firstFrames[t] as a slot of fnReceived, -1: nil */
@@ -1329,10 +1338,38 @@ typedef struct lkf_stream_fps { /* 128 B */
  * with dd_ext != 0.  Idempotent. */
 int lkf_stream_fps_enable(lkf_engine *e, int32_t stream);
 /* Waits for queued work.  A closed stream answers its last state, a stream
- * that was never enabled kind = LKF_FPS_NONE and all zero. */
+ * that was never enabled kind = LKF_FPS_NONE and all zero.  A stream enabled
+ * with lkf_stream_fps_enable_dd: kind = LKF_FPS_DD, fps[s][t], calculated, all
+ * three completed[] the one calculator's flag, calc[] zero (its state is
+ * lkf_stream_fps_dd_get's). */
 int lkf_stream_fps_get(lkf_engine *e, int32_t stream, lkf_stream_fps *out);
+/* Enables FrameRateCalculatorDD on a video stream with dd_ext != 0 (any codec)
+ * from the next ingest on; waits for queued work.  LKF_EINVAL: a bad handle, an
+ * audio stream, a stream without a dependency-descriptor extension.
+ * Idempotent.  A stream whose parser already holds a structure starts from it:
+ * the calculator reads later descriptors with that structure and takes its max
+ * layer from the parser's active mask (the reference creates the calculator
+ * at Bind, before any packet; a later enable has no counterpart there). */
+int lkf_stream_fps_enable_dd(lkf_engine *e, int32_t stream);
+typedef struct lkf_fps_dd { /* FrameRateCalculatorDD's state (fps.go:320-334), 480 B */
+  uint16_t base_fn;       /* baseFrame.fn */
+  uint8_t has_base;
+  uint8_t completed;
+  uint8_t max_spatial, max_temporal; /* SetMaxLayer */
+  uint16_t reserved;
+  uint32_t resets;        /* resets on a frame number that is not continuous, and close() */
+  uint32_t reserved2;
+  uint64_t present[4];    /* bit k of word k / 64: fnReceived[k] is set (slot k = frame base_fn + k) */
+  int16_t first[3][4];    /* firstFrames[s][t] as a slot of fnReceived, -1: nil */
+  int16_t second[3][4];   /* secondFrames[s][t] */
+  uint64_t chain[3][4][4]; /* targetFrames[s][t] as a set of slots, four words like present */
+} lkf_fps_dd;
+/* Waits for queued work.  LKF_EINVAL: a bad handle, or a stream
+ * lkf_stream_fps_enable_dd was never called on. */
+int lkf_stream_fps_dd_get(lkf_engine *e, int32_t stream, lkf_fps_dd *out);
 /* The streams that became calculated during the last ingest (the onFpsChanged
- * calls), ascending.  n_out is set even when cap is too small (LKF_ENOSPC). */
+ * calls), of either kind of calculator, ascending.  n_out is set even when cap
+ * is too small (LKF_ENOSPC). */
 int lkf_ingest_fps_changed(lkf_engine *e, int32_t *streams, uint32_t cap, uint32_t *n_out);
 
 /* ---- the publisher RTCP loop (the RTCP half of buffer.RTPStatsReceiver) ---- *

@@ -609,6 +609,17 @@ class Engine:
         self._chk(self.api["stream_fps_get"](self.h, int(stream), C.byref(st)), "stream_fps_get")
         return st
 
+    def stream_fps_enable_dd(self, stream):
+        """lkf_stream_fps_enable_dd: the dependency-descriptor frame-rate
+        calculator of a received stream with dd_ext, from the next ingest on."""
+        self._chk(self.api["stream_fps_enable_dd"](self.h, int(stream)), "stream_fps_enable_dd")
+
+    def stream_fps_dd_get(self, stream):
+        """lkf_stream_fps_dd_get -> abi.lkf_fps_dd (as_dict() for exact compares)."""
+        st = abi.lkf_fps_dd()
+        self._chk(self.api["stream_fps_dd_get"](self.h, int(stream), C.byref(st)), "stream_fps_dd_get")
+        return st
+
     def ingest_fps_changed(self):
         """lkf_ingest_fps_changed: the streams that became calculated during
         the last ingest (OnFpsChanged), ascending, as a list of handles."""

@@ -309,7 +309,7 @@ class lkf_stream_rtcp(C.Structure):
                 ("out_of_order_sender_report_count", C.c_uint32)]
 
 
-LKF_FPS_NONE, LKF_FPS_VP8, LKF_FPS_VP9 = 0, 1, 2
+LKF_FPS_NONE, LKF_FPS_VP8, LKF_FPS_VP9, LKF_FPS_DD = 0, 1, 2, 3
 
 
 class lkf_fps_calc(C.Structure):
@@ -332,6 +332,26 @@ class lkf_stream_fps(C.Structure):
 
 
 assert C.sizeof(lkf_fps_calc) == 24 and C.sizeof(lkf_stream_fps) == 128
+
+
+class lkf_fps_dd(C.Structure):
+    """FrameRateCalculatorDD's state (lkf_stream_fps_dd_get)."""
+    _fields_ = [("base_fn", C.c_uint16), ("has_base", C.c_uint8), ("completed", C.c_uint8),
+                ("max_spatial", C.c_uint8), ("max_temporal", C.c_uint8), ("reserved", C.c_uint16),
+                ("resets", C.c_uint32), ("reserved2", C.c_uint32), ("present", C.c_uint64 * 4),
+                ("first", (C.c_int16 * 4) * 3), ("second", (C.c_int16 * 4) * 3),
+                ("chain", ((C.c_uint64 * 4) * 4) * 3)]
+
+    def as_dict(self):
+        return {
+            "base_fn": self.base_fn, "has_base": self.has_base, "completed": self.completed,
+            "max_spatial": self.max_spatial, "max_temporal": self.max_temporal, "resets": self.resets,
+            "present": tuple(self.present), "first": tuple(tuple(r) for r in self.first),
+            "second": tuple(tuple(r) for r in self.second),
+            "chain": tuple(tuple(tuple(w) for w in row) for row in self.chain)}
+
+
+assert C.sizeof(lkf_fps_dd) == 480
 
 (LKF_SSR_IGNORED_UNINIT, LKF_SSR_ANACHRONOUS, LKF_SSR_CLOCK_SKEW, LKF_SSR_RESET_FIRST, LKF_SSR_FIRST_TIME_ADJUSTED,
  LKF_SSR_ADJUST_TOO_BIG, LKF_SSR_CLOSED) = (1 << k for k in range(7))
@@ -934,6 +954,9 @@ def bind_engine_api(lib, prefix):
         api["stream_fps_get"] = _bind(lib, prefix + "stream_fps_get", C.c_int, [e, C.c_int32, P(lkf_stream_fps)])
         api["ingest_fps_changed"] = _bind(lib, prefix + "ingest_fps_changed", C.c_int,
                                           [e, C.c_void_p, C.c_uint32, P(C.c_uint32)])
+    if hasattr(lib, prefix + "stream_fps_enable_dd"):  # ... and the dependency-descriptor calculator
+        api["stream_fps_enable_dd"] = _bind(lib, prefix + "stream_fps_enable_dd", C.c_int, [e, C.c_int32])
+        api["stream_fps_dd_get"] = _bind(lib, prefix + "stream_fps_dd_get", C.c_int, [e, C.c_int32, P(lkf_fps_dd)])
     api["blank_frames"] = _bind(lib, prefix + "blank_frames", C.c_int,
                                 [e, C.c_void_p, C.c_uint32, C.c_int64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64,
                                  P(C.c_uint32), P(C.c_uint64)])

@@ -29,6 +29,7 @@
 #include <cstring>
 #include <atomic>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <tuple>
@@ -585,6 +586,14 @@ struct lkf_engine {
   DevBuf<uint32_t> dFpsList, dFpsCalcAt;
   DevBuf<fps::State> dFps;
   uint32_t fpsEpoch = 0;  // ingests counted since the first enable
+  // ... and the dependency-descriptor calculators (k_ing_fps_dd), a list of
+  // their own that grows the same way; each entry has its private structure
+  // pair (dFpsDDStruct[2 i], [2 i + 1]).  fpsEpoch counts for both lists.
+  std::vector<int32_t> fpsDDHandles;
+  std::vector<int32_t> fpsDDIdx;
+  DevBuf<uint32_t> dFpsDDList, dFpsDDCalcAt;
+  DevBuf<fpsdd::State> dFpsDD;
+  DevBuf<DDStruct> dFpsDDStruct;
   uint32_t lastIngestN = 0;
   const lkf_raw_pkt *ingRaws = nullptr;  // the last ingest's datagram descriptors (device)
   // speaker ranking tables (rebuilt when topology changes)
@@ -4642,11 +4651,16 @@ static int ingest_common(lkf_engine *e, BatchCtx &x, const lkf_raw_pkt *dRaws, u
   a.nackPairCap = e->nackPairCap;
   a.nackIn = g.nackIn;
   a.nackAlone = e->knobs.nackAlone;
-  if (!e->fpsHandles.empty()) {  // (an empty ingest counts too: it completes nothing)
+  if (!e->fpsHandles.empty() || !e->fpsDDHandles.empty()) {  // (an empty ingest counts too: it completes nothing)
     a.nfps = uint32_t(e->fpsHandles.size());
     a.fpsList = e->dFpsList;
     a.fpsCalcAt = e->dFpsCalcAt;
     a.fpsStates = e->dFps;
+    a.nfpsDD = uint32_t(e->fpsDDHandles.size());
+    a.fpsDDList = e->dFpsDDList;
+    a.fpsDDCalcAt = e->dFpsDDCalcAt;
+    a.fpsDDStates = e->dFpsDD;
+    a.fpsDDStructs = e->dFpsDDStruct;
     if (!++e->fpsEpoch) e->fpsEpoch = 1;  // (0 means "not yet" in dFpsCalcAt)
     a.fpsEpoch = e->fpsEpoch;
   }
@@ -5075,6 +5089,10 @@ static int fps_index(const lkf_engine *e, int32_t stream) {
   return size_t(stream) < e->fpsIdx.size() ? e->fpsIdx[stream] : -1;
 }
 
+static int fps_dd_index(const lkf_engine *e, int32_t stream) {
+  return size_t(stream) < e->fpsDDIdx.size() ? e->fpsDDIdx[stream] : -1;
+}
+
 int lkf_stream_fps_enable(lkf_engine *e, int32_t stream) {
   if (!e || stream < 0 || stream >= int32_t(e->streams.size())) return LKF_EINVAL;
   const lkf_stream_params &sp = e->streams[stream];
@@ -5123,7 +5141,21 @@ int lkf_stream_fps_get(lkf_engine *e, int32_t stream, lkf_stream_fps *o) {
   if (!e || !o || stream < 0 || stream >= int32_t(e->streams.size())) return LKF_EINVAL;
   std::memset(o, 0, sizeof(*o));
   const int idx = fps_index(e, stream);
-  if (idx < 0) return LKF_OK;  // LKF_FPS_NONE
+  if (idx < 0) {
+    const int ddi = fps_dd_index(e, stream);
+    if (ddi < 0) return LKF_OK;  // LKF_FPS_NONE
+    STEP(quiesce(e));
+    fpsdd::State d;
+    D2H(&d, e->dFpsDD + ddi, sizeof(d), "fps dd state copy");
+    o->kind = d.kind;
+    o->calculated = uint8_t(d.calculated);
+    // (all three frameRateCalculator[] entries are the one calculator, buffer.go:195-198)
+    for (int c = 0; c < fpsdd::kSpatial; c++) {
+      o->completed[c] = d.h.completed;
+      for (int t = 0; t < fpsdd::kTemporal; t++) o->fps[c][t] = d.h.rate[c][t];
+    }
+    return LKF_OK;
+  }
   STEP(quiesce(e));
   fps::State s;
   D2H(&s, e->dFps + idx, sizeof(s), "fps state copy");
@@ -5146,19 +5178,123 @@ int lkf_stream_fps_get(lkf_engine *e, int32_t stream, lkf_stream_fps *o) {
   return LKF_OK;
 }
 
+// ---- ... with a dependency descriptor (k_ing_fps_dd; the semantics are fps_dd_device.h) ----
+static_assert(LKF_FPS_DD == fpsdd::KIND_DD, "LKF_FPS_DD is fpsdd::KIND_DD");
+static_assert(sizeof(lkf_fps_dd) == 480, "lkf_fps_dd is 480 B");
+
+int lkf_stream_fps_enable_dd(lkf_engine *e, int32_t stream) {
+  if (!e || stream < 0 || stream >= int32_t(e->streams.size())) return LKF_EINVAL;
+  const lkf_stream_params &sp = e->streams[stream];
+  const lkf_track_params &tp = e->tracks[sp.track];
+  // buffer.go:191-201: the calculator comes with the DD extension, whatever the video codec
+  if (tp.kind != LKF_KIND_VIDEO || !sp.dd_ext) return LKF_EINVAL;
+  if (fps_dd_index(e, stream) >= 0) return LKF_OK;
+  STEP(quiesce(e));  // (the stream's parser state is read below; queued launches hold the old pointers)
+  const size_t n = e->fpsDDHandles.size();
+  if (n + 1 > e->dFpsDD.cap()) {
+    const size_t cap = std::max<size_t>(16, 2 * (n + 1));
+    DevBuf<uint32_t> list, at;
+    DevBuf<fpsdd::State> st;
+    DevBuf<DDStruct> ds;
+    HIPCHK(list.alloc(cap), "alloc fps dd list");
+    HIPCHK(at.alloc(cap), "alloc fps dd epochs");
+    HIPCHK(st.alloc(cap), "alloc fps dd state");
+    HIPCHK(ds.alloc(2 * cap), "alloc fps dd structures");
+    HIPCHK(hipMemset(ds, 0, 2 * cap * sizeof(DDStruct)), "fps dd structures reset");
+    if (n) {
+      HIPCHK(hipMemcpy(list, e->dFpsDDList, n * sizeof(uint32_t), hipMemcpyDeviceToDevice), "fps dd list copy");
+      HIPCHK(hipMemcpy(at, e->dFpsDDCalcAt, n * sizeof(uint32_t), hipMemcpyDeviceToDevice), "fps dd epochs copy");
+      HIPCHK(hipMemcpy(st, e->dFpsDD, n * sizeof(fpsdd::State), hipMemcpyDeviceToDevice), "fps dd state copy");
+      HIPCHK(hipMemcpy(ds, e->dFpsDDStruct, 2 * n * sizeof(DDStruct), hipMemcpyDeviceToDevice),
+             "fps dd structures copy");
+    }
+    e->dFpsDDList = std::move(list);
+    e->dFpsDDCalcAt = std::move(at);
+    e->dFpsDD = std::move(st);
+    e->dFpsDDStruct = std::move(ds);
+  }
+  auto s = std::make_unique<fpsdd::State>();
+  std::memset(s.get(), 0, sizeof(fpsdd::State));
+  s->kind = fpsdd::KIND_DD;
+  s->clockRate = tp.clock_rate;
+  s->stream = uint32_t(stream);
+  s->vp8 = tp.codec == LKF_CODEC_VP8;
+  fpsdd::set_max_layer(s->h, 2, 3);  // DefaultMaxLayerSpatial / Temporal (fps.go:340-341)
+  // A parser that already holds a structure: the calculator starts from it and
+  // from the parser's active mask (no reference counterpart: DESIGN §2)
+  uint32_t ddIdx = 0;
+  for (int32_t k = 0; k < stream; k++) ddIdx += e->streams[k].dd_ext ? 1u : 0u;
+  if (e->dDDIng && ddIdx < e->ddStreamInit) {
+    auto ps = std::make_unique<DDIngState>();
+    D2H(ps.get(), e->dDDIng + ddIdx, sizeof(DDIngState), "dd parser copy");
+    if (ps->flags & DI_HAS_STRUCT) {
+      const DDStruct *src = e->dDDIngStruct + size_t(ddIdx) * 2 + ((ps->flags & DI_CUR) ? 1 : 0);
+      auto hs = std::make_unique<DDStruct>();
+      D2H(hs.get(), src, sizeof(DDStruct), "dd parser structure copy");
+      HIPCHK(hipMemcpy(e->dFpsDDStruct + 2 * n, src, sizeof(DDStruct), hipMemcpyDeviceToDevice),
+             "fps dd structure seed");
+      s->hasStruct = 1;
+      const uint32_t ml = fpsdd::max_layer_of(ps->activeMask, hs->numDT, hs->dtTarget, hs->dtS, hs->dtT);
+      fpsdd::set_max_layer(s->h, ml & 0xffu, ml >> 8);
+    }
+  }
+  const uint32_t h = uint32_t(stream), zero = 0;
+  HIPCHK(hipMemcpy(e->dFpsDD + n, s.get(), sizeof(fpsdd::State), hipMemcpyHostToDevice), "fps dd state init");
+  HIPCHK(hipMemcpy(e->dFpsDDList + n, &h, sizeof(h), hipMemcpyHostToDevice), "fps dd list entry");
+  HIPCHK(hipMemcpy(e->dFpsDDCalcAt + n, &zero, sizeof(zero), hipMemcpyHostToDevice), "fps dd epoch entry");
+  if (e->fpsDDIdx.size() <= size_t(stream)) e->fpsDDIdx.resize(size_t(stream) + 1, -1);
+  e->fpsDDIdx[stream] = int32_t(n);
+  e->fpsDDHandles.push_back(stream);
+  return LKF_OK;
+}
+
+int lkf_stream_fps_dd_get(lkf_engine *e, int32_t stream, lkf_fps_dd *o) {
+  if (!e || !o || stream < 0 || stream >= int32_t(e->streams.size())) return LKF_EINVAL;
+  const int idx = fps_dd_index(e, stream);
+  if (idx < 0) return LKF_EINVAL;
+  STEP(quiesce(e));
+  auto s = std::make_unique<fpsdd::State>();
+  D2H(s.get(), e->dFpsDD + idx, sizeof(fpsdd::State), "fps dd state copy");
+  std::memset(o, 0, sizeof(*o));
+  const fpsdd::Head &h = s->h;
+  o->base_fn = h.baseFn;
+  o->has_base = h.hasBase;
+  o->completed = h.completed;
+  o->max_spatial = h.maxSpatial;
+  o->max_temporal = h.maxTemporal;
+  o->resets = h.resets;
+  fpsdd::HostWin w{s->ts, s->chain, s->layer};
+  for (int j = 0; j < fpsdd::kWords; j++) o->present[j] = h.present[j];
+  for (int c = 0; c < fpsdd::kSpatial; c++)
+    for (int t = 0; t < fpsdd::kTemporal; t++) {
+      const bool has = (h.has >> (4 * c + t)) & 1;
+      o->first[c][t] = has ? int16_t(fpsdd::byte_of(h.first[c], t)) : int16_t(-1);
+      o->second[c][t] = has ? int16_t(fpsdd::byte_of(h.second[c], t)) : int16_t(-1);
+      for (int j = 0; j < fpsdd::kWords; j++) o->chain[c][t][j] = w.chain_word(4 * c + t, j);
+    }
+  return LKF_OK;
+}
+
 int lkf_ingest_fps_changed(lkf_engine *e, int32_t *streams, uint32_t cap, uint32_t *n_out) {
   if (!e || !n_out) return LKF_EINVAL;
   *n_out = 0;
-  const size_t n = e->fpsHandles.size();
-  if (!n || !e->fpsEpoch) return LKF_OK;
+  const size_t n = e->fpsHandles.size(), nd = e->fpsDDHandles.size();
+  if ((!n && !nd) || !e->fpsEpoch) return LKF_OK;
   HIPCHK(hipSetDevice(e->dev), "hipSetDevice");
   HIPCHK(hipStreamSynchronize(e->ingS), "sync ingest stream");
   HIPCHK(hipStreamSynchronize(e->sideS), "sync side stream");  // (the calculators of the last ingest)
-  std::vector<uint32_t> at(n);
-  D2H(at.data(), e->dFpsCalcAt, n * sizeof(uint32_t), "fps epochs copy");
+  std::vector<uint32_t> at(std::max(n, nd));
   std::vector<int32_t> hit;
-  for (size_t i = 0; i < n; i++)
-    if (at[i] == e->fpsEpoch) hit.push_back(e->fpsHandles[i]);
+  if (n) {
+    D2H(at.data(), e->dFpsCalcAt, n * sizeof(uint32_t), "fps epochs copy");
+    for (size_t i = 0; i < n; i++)
+      if (at[i] == e->fpsEpoch) hit.push_back(e->fpsHandles[i]);
+  }
+  if (nd) {  // the dependency-descriptor calculators: merged (sorted below)
+    D2H(at.data(), e->dFpsDDCalcAt, nd * sizeof(uint32_t), "fps dd epochs copy");
+    for (size_t i = 0; i < nd; i++)
+      if (at[i] == e->fpsEpoch) hit.push_back(e->fpsDDHandles[i]);
+  }
   std::sort(hit.begin(), hit.end());
   *n_out = uint32_t(hit.size());
   if (hit.size() > cap) return LKF_ENOSPC;

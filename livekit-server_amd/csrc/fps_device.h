@@ -32,8 +32,9 @@
 // does (temporal 3 can still count as "lower layer calculated, never seen",
 // fps.go:137-140, in a window without one).
 //
-// Not here: FrameRateCalculatorDD (fps.go:319-570).  It needs every frame's
-// FrameDiffs, which the ingress DD parse does not keep (FD_NONE, fwd_state.h).
+// Not here: FrameRateCalculatorDD (fps.go:319-570), the calculator of a stream
+// with a dependency descriptor.  It is fps_dd_device.h, run by k_ing_fps_dd,
+// and uses min_frames, rate_of and the 64-bit mask helpers of this header.
 #pragma once
 #include <stdint.h>
 

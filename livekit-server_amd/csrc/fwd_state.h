@@ -557,7 +557,9 @@ struct IngDD {  // k_ing_stream -> k_ing_out: one datagram's ExtDependencyDescri
   uint64_t extFN, extKFN;
   uint16_t ddOff;
   uint8_t ddLen, flags;  // LKF_DD_*
-  uint8_t present, sid, tid, pad;
+  uint8_t present, sid, tid;
+  uint8_t maxLayer;  // this packet changed the parser's active mask (onMaxLayerChanged,
+                     // dependencydescriptorparser.go:140-155): read by k_ing_fps_dd alone
   uint64_t pad2;
 };
 

@@ -17,6 +17,8 @@
 //                  AddPacketWithSequenceNumber (:471-481), getExtPacket's
 //                  dependency descriptor (:599-671); in-order runs lane-parallel
 //   k_ing_nack     (side stream) the NackQueue per stream
+//   k_ing_fps_dd   (side stream) one wave per stream with the dependency-
+//                  descriptor frame-rate calculator enabled
 //   k_ing_fps      (side stream) one wave per stream with frame-rate
 //                  calculation enabled: doFpsCalc (buffer.go:518-543) over
 //                  the VP8 / VP9 PictureID calculators of fps_device.h
@@ -891,6 +893,7 @@ __device__ bool dd_fold(DDIngState &d, u16 sn, const DDLite &o, bool att, IngDD 
     if (o.activeMask != d.activeMask) {
       d.activeMask = o.activeMask;
       out.flags |= LKF_DD_ACTIVE_UPDATED;
+      out.maxLayer = 1;  // (SetMaxLayer for the stream's frame-rate calculator, k_ing_fps_dd)
     }
   }
   out.extKFN = d.structureExtFN;
@@ -2971,6 +2974,248 @@ __global__ void __launch_bounds__(64) k_ing_fps(const lkf_raw_pkt *__restrict__ 
   }
 }
 
+// ---------------------------------------------------------------------------
+// k_ing_fps_dd: Buffer.doFpsCalc for the streams with a dependency descriptor
+// it was enabled on (lkf_stream_fps_enable_dd): FrameRateCalculatorDD as
+// fps_dd_device.h restates it, one wave per entry of a compact list of its own,
+// on the side stream beside k_ing_fps.  The 256-frame window is lane-held, four
+// slots per lane (timestamp, layer byte, 12 chain-membership bits each); the
+// head is wave-uniform.  The packet walk has k_ing_fps's shape: the stream's
+// datagram list loaded 64 at a time, filtered lane-parallel, the survivors
+// walked through their ballot.
+//
+// The frame diffs are not kept by the ingress parse, so the walk reads them
+// itself: each surviving datagram's extension is parsed again (dd::dd_parse,
+// wave-uniform) against a structure pair private to the calculator — the one in
+// force and the one an attached structure is read into — which advances exactly
+// at the datagrams whose IngDD carries LKF_DD_STRUCTURE_UPDATED (the attaches
+// the parser accepted), so datagram k is read with the structure the parser
+// read it with even when one ingest holds several keyframes (the stream's own
+// pair holds the end-of-batch state by now).  Template diffs come from that
+// structure's pool, custom diffs from the descriptor's bits, walked again at
+// any length.  Two shortcuts keep most datagrams out of the parse: a packet
+// that RecvPacket would ignore without a change (a frame already received, a
+// frame number behind the base, a layer out of range) is skipped on the
+// descriptor's frame number, read lane-parallel with its first bytes; and a
+// descriptor that attaches no structure is its template, named by its first
+// byte, plus the mask and the custom list read at their bit offsets, so only
+// an attaching descriptor is parsed in full.  IngDD.maxLayer marks the packets at which the parser changed its
+// active mask: SetMaxLayer with the maximum layer of the mask's decode targets,
+// before that packet's RecvPacket.  A datagram is looked at when it is an
+// ExtPacket with a payload and a descriptor (RecvPacket), or attaches a
+// structure, or changes the mask — the last two whatever became of it later
+// (a codec payload that failed to unmarshal).
+// calcAt[i] != 0: one load, one compare, nothing else.
+// ---------------------------------------------------------------------------
+struct FpsDDDiffs {  // FrameDependencies.FrameDiffs of the descriptor just parsed, in order
+  dd::BitR r;        // at the custom list (custom), else unused
+  const u8 *pool;    // the template's list in the structure's pool
+  u32 n;
+  bool custom;
+  __device__ u32 size() const { return n; }
+  __device__ u32 next() {
+    if (!custom) return *pool++;
+    u64 v, f;
+    r.bits(2, v);
+    r.bits(int(v) * 4, f);
+    return u32(u16(f + 1));
+  }
+};
+
+__device__ __forceinline__ fpsdd::Head fpsdd_load_head(const fpsdd::Head *g, u32 lane) {
+  // 32 words by 32 lanes, then wave-uniform through readlane
+  const u32 *p = reinterpret_cast<const u32 *>(g);
+  const u32 v = lane < sizeof(fpsdd::Head) / 4 ? p[lane] : 0u;
+  auto w = [&](int i) { return u32(__builtin_amdgcn_readlane(int(v), i)); };
+  fpsdd::Head h;
+#pragma unroll
+  for (int j = 0; j < fpsdd::kWords; j++) h.present[j] = u64(w(2 * j)) | (u64(w(2 * j + 1)) << 32);
+#pragma unroll
+  for (int l = 0; l < fpsdd::kLayers; l++) h.rate[l / 4][l % 4] = __uint_as_float(w(8 + l));
+#pragma unroll
+  for (int s = 0; s < fpsdd::kSpatial; s++) {
+    h.first[s] = w(20 + s);
+    h.second[s] = w(23 + s);
+  }
+  const u32 a = w(26), b = w(27), c = w(28);
+  h.has = u16(a);
+  h.chainAny = u16(a >> 16);
+  h.baseFn = u16(b);
+  h.hasBase = u8(b >> 16);
+  h.completed = u8(b >> 24);
+  h.maxSpatial = u8(c);
+  h.maxTemporal = u8(c >> 8);
+  h.dirty = u16(c >> 16);
+  h.resets = w(29);
+  h.pad[0] = h.pad[1] = 0;
+  return h;
+}
+static_assert(__builtin_offsetof(fpsdd::Head, rate) == 32 && __builtin_offsetof(fpsdd::Head, first) == 80 &&
+                  __builtin_offsetof(fpsdd::Head, second) == 92 && __builtin_offsetof(fpsdd::Head, has) == 104 &&
+                  __builtin_offsetof(fpsdd::Head, chainAny) == 106 && __builtin_offsetof(fpsdd::Head, baseFn) == 108 &&
+                  __builtin_offsetof(fpsdd::Head, hasBase) == 110 && __builtin_offsetof(fpsdd::Head, completed) == 111 &&
+                  __builtin_offsetof(fpsdd::Head, maxSpatial) == 112 && __builtin_offsetof(fpsdd::Head, maxTemporal) == 113 &&
+                  __builtin_offsetof(fpsdd::Head, resets) == 116,
+              "fpsdd_load_head reads Head by word");
+
+__global__ void __launch_bounds__(64)
+    k_ing_fps_dd(const lkf_raw_pkt *__restrict__ raws, const IngParsed *__restrict__ q,
+                 const lkf_flow *__restrict__ flows, const IngDD *__restrict__ ingDD,
+                 const DevStream *__restrict__ streams, const u8 *__restrict__ raw, const u32 *__restrict__ tBegin,
+                 const u32 *__restrict__ tEnd, const u32 *__restrict__ list, const u32 *__restrict__ cnt, u32 stride,
+                 const u32 *__restrict__ handles, u32 *__restrict__ calcAt, fpsdd::State *__restrict__ states,
+                 DDStruct *__restrict__ structs, u32 epoch) {
+  const u32 i = blockIdx.x, lane = threadIdx.x;
+  if (calcAt[i]) return;  // frameRateCalculated (buffer.go:519)
+  const u32 sid = handles[i];
+  const DevStream *const sp = streams + sid;
+  if (sp->closed) return;
+  const u32 track = sp->track;
+  const i32 layer = sp->layer;
+  const u32 pb = tBegin[track], pe = tEnd[track];
+  if (pb >= pe) return;  // no datagram of its track
+  const bool useList = layer >= 0 && layer < 3;  // (k_ing_lists lists only these)
+  const u32 nIdx = useList ? cnt[track * 3 + u32(layer)] : pe - pb;
+  const u32 *lst = list + size_t(useList ? layer : 0) * stride + pb;
+  fpsdd::State *const g = states + i;
+  DDStruct *const st = structs + size_t(i) * 2;
+  const u32 clockRate = g->clockRate;
+  const bool vp8 = g->vp8 != 0;
+  u32 cur = g->cur & 1u;
+  bool hasStruct = g->hasStruct != 0;
+  fpsdd::Head h = fpsdd_load_head(&g->h, lane);
+  fpsdd::WaveWin w;
+  w.lane = lane;
+  w.ts0 = g->ts[lane], w.ts1 = g->ts[64 + lane], w.ts2 = g->ts[128 + lane], w.ts3 = g->ts[192 + lane];
+  w.layer = u32(g->layer[lane]) | u32(g->layer[64 + lane]) << 8 | u32(g->layer[128 + lane]) << 16 |
+            u32(g->layer[192 + lane]) << 24;
+  w.chain = u64(g->chain[lane]) | u64(g->chain[64 + lane]) << 16 | u64(g->chain[128 + lane]) << 32 |
+            u64(g->chain[192 + lane]) << 48;
+  bool dirty = false;  // wave-uniform: a datagram was looked at
+  for (u32 base = 0; base < nIdx; base += 64) {
+    const u32 k = base + lane;
+    // what: 1 RecvPacket, 2 an accepted attach, 4 the mask changed
+    u32 what = 0, off = 0, len = 0, ts = 0, lay = 0, hdr = 0;
+    if (k < nIdx) {
+      const u32 ic = useList ? lst[k] : pb + k;
+      const lkf_raw_pkt rp = raws[ic];
+      if (rp.stream == sid) {
+        const IngParsed p = q[ic];
+        const IngDD dv = ingDD[ic];
+        // an ExtPacket with a payload (buffer.go:485-490, :519) and a descriptor (fps.go:358)
+        if ((flows[ic].flags & LKF_FLOW_FORWARD) && p.payloadLen != 0 && dv.present) what |= 1u;
+        if (dv.present && (dv.flags & LKF_DD_STRUCTURE_UPDATED)) what |= 2u;
+        if (dv.maxLayer) what |= 4u;
+        // (a descriptor that parsed lies inside the datagram, and the datagram inside the arena:
+        // k_ing_parse checked both before it set ddLen)
+        if (!p.ddLen) what = 0;
+        off = rp.off + p.ddOff;
+        len = p.ddLen;
+        ts = p.ts;
+        lay = u32(dv.sid) | u32(dv.tid) << 8;
+        if (what) {  // the descriptor's mandatory bytes and its flags byte (0 when it has none), lane-parallel
+          const u8 *b = raw + off;
+          hdr = u32(b[0]) | u32(b[1]) << 8 | u32(b[2]) << 16 | (len > 3 ? u32(b[3]) << 24 : 0u);
+        }
+      }
+    }
+    u64 m = __ballot(what != 0);
+    while (m) {
+      const int x = __ffsll((long long)m) - 1;
+      m &= m - 1;
+      const u32 wx = u32(__builtin_amdgcn_readlane(int(what), x));
+      if (h.completed && !(wx & 6u)) continue;
+      const u32 ox = u32(__builtin_amdgcn_readlane(int(off), x));
+      const int lx = __builtin_amdgcn_readlane(int(len), x);
+      const u32 tx = u32(__builtin_amdgcn_readlane(int(ts), x));
+      const u32 yx = u32(__builtin_amdgcn_readlane(int(lay), x));
+      const u32 hx = u32(__builtin_amdgcn_readlane(int(hdr), x));
+      const i32 spatial = vp8 ? -1 : i32(yx & 0xffu), temporal = i32(yx >> 8);
+      const u16 fnx = u16(((hx >> 8) & 0xffu) << 8 | ((hx >> 16) & 0xffu));  // frame_number
+      // RecvPacket alone, and it would change nothing (a later packet of a frame already received,
+      // mostly): nothing to read
+      if (wx == 1u && fpsdd::recv_ignores(h, fnx, spatial, temporal)) continue;
+      dirty = true;
+      const u8 *buf = raw + ox;
+      const u32 fb = hx >> 24;  // structure | active | custom dtis | custom fdiffs | custom chains | 000
+      if (hasStruct && !(fb & 0x80u)) {
+        // No structure attached: the frame is its template but for the custom fields, which lie at
+        // bit offsets the flags and the structure's decode-target count give (the ingress parse
+        // accepted the descriptor with this structure, so template and fields exist).
+        const DDStruct *s = st + cur;
+        const u32 idx = ((hx & 0x3fu) + 64u - s->structureId) & 63u;
+        if (idx >= s->numTmpl) continue;
+        const int ndt = s->numDT;
+        if ((wx & 4u) && (fb & 0x40u)) {  // active_decode_targets_bitmask
+          dd::BitR r(buf, lx);
+          r.pos = 3;
+          r.remaining = lx * 8 - 29;
+          u64 mask;
+          if (r.bits(ndt, mask)) continue;
+          const u32 ml = fpsdd::max_layer_of(u32(mask), s->numDT, s->dtTarget, s->dtS, s->dtT);
+          fpsdd::set_max_layer(h, ml & 0xffu, ml >> 8);
+        }
+        if (!(wx & 1u) || h.completed) continue;
+        FpsDDDiffs d{dd::BitR(buf, lx), s->fdPool + s->t[idx].fdOff, s->t[idx].nfd, (fb & 0x10u) != 0};
+        if (d.custom) {
+          const int start = 29 + ((fb & 0x40u) ? ndt : 0) + ((fb & 0x20u) ? 2 * ndt : 0);
+          d.r.pos = start >> 3;
+          d.r.remaining = lx * 8 - start;
+          dd::BitR c = d.r;  // the list's length first (a 0 size ends it, as does the descriptor's end)
+          d.n = 0;
+          for (;;) {
+            u64 v, f;
+            if (c.bits(2, v) || !v || c.bits(int(v) * 4, f)) break;
+            d.n++;
+          }
+        }
+        (void)fpsdd::recv(h, w, fnx, tx, spatial, temporal, d, clockRate);
+        continue;
+      }
+      DDPkt o = {};
+      bool att = false;
+      // (every lane reads the same descriptor; an attached structure is written with the same
+      // values by all of them)
+      if (dd::dd_parse(buf, lx, hasStruct ? st + cur : nullptr, st + (cur ^ 1u), o, att)) continue;
+      if ((wx & 2u) && att) {
+        cur ^= 1u;
+        hasStruct = true;
+      }
+      if (!hasStruct) continue;
+      const DDStruct *s = st + cur;
+      if ((wx & 4u) && (o.flags & DP_ACTIVE)) {
+        const u32 ml = fpsdd::max_layer_of(o.activeMask, s->numDT, s->dtTarget, s->dtS, s->dtT);
+        fpsdd::set_max_layer(h, ml & 0xffu, ml >> 8);
+      }
+      if (!(wx & 1u) || h.completed) continue;
+      FpsDDDiffs d{dd::BitR(buf, lx), s->fdPool + s->t[o.tmplIdx].fdOff, o.nfd, (fb & 0x10u) != 0};
+      if (d.custom) {  // where the custom list starts (dependencydescriptorreader.go: the fields before it)
+        const int start = 24 + 5 + ((fb & 0x80u) ? dd::structure_bits(*s) : 0) + ((fb & 0x40u) ? s->numDT : 0) +
+                          ((fb & 0x20u) ? 2 * s->numDT : 0);
+        d.r.pos = start >> 3;
+        d.r.remaining = lx * 8 - start;
+      }
+      (void)fpsdd::recv(h, w, o.frameNumber, tx, spatial, temporal, d, clockRate);
+    }
+  }
+  if (!dirty) return;
+  g->ts[lane] = w.ts0, g->ts[64 + lane] = w.ts1, g->ts[128 + lane] = w.ts2, g->ts[192 + lane] = w.ts3;
+#pragma unroll
+  for (int j = 0; j < fpsdd::kWords; j++) {
+    g->layer[64 * j + lane] = u8(w.layer >> (8 * j));
+    g->chain[64 * j + lane] = u16(w.chain >> (16 * j));
+  }
+  if (lane == 0) {
+    g->h = h;
+    g->cur = cur;
+    g->hasStruct = hasStruct ? 1u : 0u;
+    if (h.completed) {  // frameRateCalculated, onFpsChanged (buffer.go:535-540)
+      g->calculated = 1;
+      calcAt[i] = epoch;
+    }
+  }
+}
+
 static u32 nblk(u64 n, u32 t) { return u32((n + t - 1) / t); }
 
 // Zeroes an ingest's per-track ranges, error words, ExtPacket total and (with
@@ -3040,7 +3285,7 @@ hipError_t launch_ingest(hipStream_t st, const IngestLaunch &a, hipStream_t side
                          a.hot, a.hist, a.rings, a.tBegin, a.tEnd, a.flows, a.fwd, a.raw, a.ddStates, a.ddStructs,
                          a.ingDD, a.err, a.list, a.listCnt, a.listStride, bka, a.rxGap, a.nack ? a.nackIn : nullptr, a.nstreams, sper);
   }
-  if ((a.nack || a.nfps) && a.nstreams) {  // after the flows: the loss ranges and ExtPacket flags they read
+  if ((a.nack || a.nfps || a.nfpsDD) && a.nstreams) {  // after the flows: the loss ranges and ExtPacket flags they read
     hipError_t r = hipEventRecord(sideFork, st);
     if (r == hipSuccess) r = hipStreamWaitEvent(side, sideFork, 0);
     if (r != hipSuccess) return r;
@@ -3061,6 +3306,10 @@ hipError_t launch_ingest(hipStream_t st, const IngestLaunch &a, hipStream_t side
       hipLaunchKernelGGL(k_ing_fps, dim3(a.nfps), dim3(64), 0, side, a.raws, a.parsed, a.flows, a.streams, a.raw,
                          a.tBegin, a.tEnd, a.list, a.listCnt, a.listStride, a.fpsList, a.fpsCalcAt, a.fpsStates,
                          a.fpsEpoch);
+    if (a.nfpsDD)  // ... and of the streams with a dependency descriptor
+      hipLaunchKernelGGL(k_ing_fps_dd, dim3(a.nfpsDD), dim3(64), 0, side, a.raws, a.parsed, a.flows, a.ingDD, a.streams,
+                         a.raw, a.tBegin, a.tEnd, a.list, a.listCnt, a.listStride, a.fpsDDList, a.fpsDDCalcAt,
+                         a.fpsDDStates, a.fpsDDStructs, a.fpsEpoch);
     r = hipEventRecord(sideDone, side);
     if (r != hipSuccess) return r;
     *sideUsed = true;

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/lkfwd.h"
+#include "fps_dd_device.h"
 #include "fps_device.h"
 #include "fwd_state.h"
 #include "srtcp_device.h"
@@ -170,6 +171,14 @@ struct IngestLaunch {
   uint32_t *fpsCalcAt = nullptr;
   fps::State *fpsStates = nullptr;
   uint32_t fpsEpoch = 0;
+  // ... and the dependency-descriptor calculators (k_ing_fps_dd), a list of
+  // their own with the same epoch: handles, completing ingest, state and the
+  // private structure pair of each entry (2 DDStruct)
+  uint32_t nfpsDD = 0;
+  const uint32_t *fpsDDList = nullptr;
+  uint32_t *fpsDDCalcAt = nullptr;
+  fpsdd::State *fpsDDStates = nullptr;
+  DDStruct *fpsDDStructs = nullptr;
   const BucketLaunch *bucket = nullptr;  // the RTX buckets (nullptr: none)
   // (measurement, LKF_NACK_ALONE=1) the rest of the ingest waits for the NACK
   // queues, so a kernel trace times k_ing_nack with the GPU to itself
@@ -252,7 +261,7 @@ struct SpeakersLaunch {
 };
 
 // the ingest chain on s; with NACK queues or enabled frame-rate calculators
-// k_ing_nack / k_ing_fps fork onto `side` after the stream kernel (*sideUsed:
+// k_ing_nack / k_ing_fps / k_ing_fps_dd fork onto `side` after the stream kernel (*sideUsed:
 // sideDone was recorded there)
 hipError_t launch_ingest(hipStream_t s, const IngestLaunch &a, hipStream_t side, hipEvent_t sideFork,
                          hipEvent_t sideDone, bool *sideUsed);
