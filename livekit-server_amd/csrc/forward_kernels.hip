@@ -31,8 +31,8 @@
 #define LKF_SVC_STATS 0
 #endif
 #if LKF_SVC_STATS  // (diagnostic builds: the counters, below at svc_run)
-__device__ unsigned long long g_svc[64 * 48];  // 64 copies (by workgroup) of 48 counters
-#define SVC_ADD(k, v) atomicAdd(&g_svc[(blockIdx.x & 63) * 48 + (k)], (unsigned long long)(v))
+__device__ unsigned long long g_svc[64 * 64];  // 64 copies (by workgroup) of 64 counters
+#define SVC_ADD(k, v) atomicAdd(&g_svc[(blockIdx.x & 63) * 64 + (k)], (unsigned long long)(v))
 #endif
 #include "dd_device.h"
 #include "fwd_state.h"
@@ -234,7 +234,7 @@ struct Lane {
   SeqRM *srm;  // the sequencer's RangeMap region (read only with F_SEQ_RM)
   u32 srmCap;
   // track
-  u32 kind, codec, hasRefTS, clockRate;
+  u32 kind, codec, hasRefTS, clockRate;  // (wave-uniform, like all of Lane: fw_sourceSwitch reads clockRate as a scalar)
   u32 *offs;  // the DownTrack's reference-layer offsets row (HBM; read on a source switch)
   // static DT
   u8 extPlayout, extAbs, extDD, extTcc;
@@ -875,7 +875,12 @@ __device__ bool fw_sourceSwitch(Lane &L, const PktV &p, i32 layer) {
   }
   extRefTS += L.h.refTSOffset;
   u64 extNextTS;
-  const double cr = double(L.clockRate);
+  // (opaque, so the conversion stays in this rare path: hoisted in front of a
+  // DownTrack's chunks it holds two VGPRs, or a scratch slot, across them;
+  // the rate is wave-uniform: a wave serves one DownTrack at a time)
+  u32 crU = L.clockRate;
+  asm volatile("" : "+s"(crU));
+  const double cr = double(crU);
   if (L.h.lastSSRC == 0) {
     double diffSeconds = double(i64(extExpectedTS - extRefTS)) / cr;
     if (diffSeconds >= 0.0) {
@@ -2064,10 +2069,13 @@ __device__ __forceinline__ void decide_step(Lane &L, const PktV &p, u32 k, LaneO
 // at the start of the run; the longest prefix of lanes whose packets are
 // covered is decided in parallel (ballot + popcount prefixes give the
 // offsets, output slots and sequencer slots), and the state is advanced once.
-// The first packet that is not covered (gap, reorder, duplicate, layer or
-// temporal switch point, keyframe, SSRC change, picture-id wrap, pending
-// control op) goes through decide_step — the full restatement — executed by
-// the whole wave on the broadcast packet, and the run restarts after it.
+// A late packet (behind the highest SN reached) is left out of those prefixes
+// and settled wave-uniform once the run's extent is known (LKF_OOO_RUN).
+// The first packet that is not covered (a copy of the highest SN, a late
+// packet the run cannot settle, a layer or temporal switch point, SSRC
+// change, picture-id wrap, pending control op) goes through decide_step — the
+// full restatement — executed by the whole wave on the broadcast packet, and
+// the run restarts after it.
 // ---------------------------------------------------------------------------
 
 #ifndef LKF_DECIDE_WAVES  // occupancy floor (waves per SIMD); 4 and 6 measured slower (r3, r5)
@@ -2184,6 +2192,9 @@ __global__ void __launch_bounds__(64) k_layer_index(const RunDesc *__restrict__ 
 // ---------------------------------------------------------------------------
 #ifndef LKF_SVC_CHAINS  // chain breaks / restarts decided in SVC runs (0: they end the run; A/B)
 #define LKF_SVC_CHAINS 1
+#endif
+#ifndef LKF_OOO_RUN  // late (reordered) packets settled in the simulcast / audio runs (0: each ends its run; A/B)
+#define LKF_OOO_RUN 1
 #endif
 constexpr int kSvcDDBytes = 48;  // per-lane marshal buffer (a descriptor without a structure fits)
 constexpr int kSvcFrames = 72;   // frame decisions of one run: frame cLast + up to 64 later frames
@@ -3116,6 +3127,12 @@ __global__ void __launch_bounds__(64) DECIDE_ATTR k_decide_dt(DecideArgs A_, con
       }
       u32 x;
       bool gapStop = false;  // the stopping lane starts the next run (no full step)
+#if LKF_SVC_STATS
+      // the plain DownTracks' runs (g_svc[48..54]): run iterations, full steps,
+      // those of a late packet, those of a copy of the highest SN, late
+      // packets forwarded / dropped in a run, late packets a run handed back
+      u32 whyStop = 0;
+#endif
       if (DDK && svcDT) {
         // SVC DownTrack: a run, then the stopping packet's full step (its
         // descriptor reloaded wave-uniform, so the chunk's raw registers are
@@ -3177,12 +3194,31 @@ __global__ void __launch_bounds__(64) DECIDE_ATTR k_decide_dt(DecideArgs A_, con
           cls = -2;
       }
       const bool cand = inWin && cls == -1;
-      const bool candIn = cand;  // (an out-of-order candidate is not ok: the full step)
-      const u64 candM = __ballot(candIn);
-      const int pc = prev_in(candM, lt);
-      const int pcs = pc >= 0 ? pc : int(lane);  // cross-lane reads run on every lane
-      const u64 pcEsn = sh64(p.esn, pcs);
-      const u64 prevEsn = pc >= 0 ? pcEsn : L.h.extHighestIncomingSN;
+      u64 candM = __ballot(cand);
+      int pc = prev_in(candM, lt);
+      int pcs = pc >= 0 ? pc : int(lane);  // cross-lane reads run on every lane
+      u64 pcEsn = sh64(p.esn, pcs);
+      u64 prevEsn = pc >= 0 ? pcEsn : L.h.extHighestIncomingSN;
+      // A late candidate (behind the highest SN that the state or an earlier
+      // lane reached, rtpmunger.go:219) leaves the in-order chain: the lanes
+      // behind it link to the last in-order candidate.  A lane behind its
+      // predecessor is behind the prefix maximum too, so each pass marks only
+      // late lanes, and the chain that remains when a pass finds none ascends.
+      // At most four passes (a pass per depth of late lanes nested behind one
+      // another; the generator's swaps need one): a lane still behind its
+      // predecessor after them stays in the chain, is not ok, and ends the run.
+      bool late = false;
+#if LKF_OOO_RUN
+      for (int pass = 0; pass < 4 && __ballot(cand && !late && i64(p.esn - prevEsn) < 0); pass++) {  // (in order: this one ballot)
+        late = late || (cand && i64(p.esn - prevEsn) < 0);
+        candM = __ballot(cand && !late);
+        pc = prev_in(candM, lt);
+        pcs = pc >= 0 ? pc : int(lane);
+        pcEsn = sh64(p.esn, pcs);
+        prevEsn = pc >= 0 ? pcEsn : L.h.extHighestIncomingSN;
+      }
+#endif
+      const bool candIn = cand && !late;  // (a late lane is settled apart, below)
       // A loss gap (diff > 1, rtpmunger.go:186-190) is taken in the run when it
       // is the run's first candidate: its side effects (missing/exempted
       // pictures vp8.go:218-255, skipped sequencer slots sequencer.go:179-189)
@@ -3206,6 +3242,7 @@ __global__ void __launch_bounds__(64) DECIDE_ATTR k_decide_dt(DecideArgs A_, con
       bool dropT = false;
       u64 tswM = 0;  // candidate lanes at a temporal switch point (the first ends the run)
       bool overT = false;
+      bool lateBad = false;
       if (video) {
         i32 mp = prevExt;
         if (mp > 0) mp = prevM ? (prevExt & 0x7fff) : (prevExt & 0x7f);
@@ -3236,6 +3273,7 @@ __global__ void __launch_bounds__(64) DECIDE_ATTR k_decide_dt(DecideArgs A_, con
         const bool tswOk = tsw && !gapLane && !dropT;
         ok = ok && !wrapBack && !wraps && (!tsw || tswOk) && (!dropT || L.h.snOffset == L.h.rmOpenValue);
         tswM = __ballot(inWin && ok && tsw);
+        lateBad = wrapBack || wraps || tsw;  // (a late packet that moves the wrap handler or the selector)
       }
       // (diag: run-body split below)
       const u64 tdM = __ballot(ok && dropT);
@@ -3247,7 +3285,7 @@ __global__ void __launch_bounds__(64) DECIDE_ATTR k_decide_dt(DecideArgs A_, con
       // forwarded: munged descriptor (vp8.go:283-301) + output shape
       const bool fwdIn = ok && !dropT;
       const i32 mext = ext - picOff;
-      const u16 mpid = u16(mext & 0x7fff);
+      u16 mpid = u16(mext & 0x7fff);
       const u8 mtl0 = u8(p.tl0 - L.h.tl0Off);
       const u8 mkey = u8((p.keyidx - L.h.keyIdxOff) & 0x1f);
       u64 cb = 0;
@@ -3276,36 +3314,34 @@ __global__ void __launch_bounds__(64) DECIDE_ATTR k_decide_dt(DecideArgs A_, con
                          (osn == prevOsn + 1 || (gapLane && osn - prevOsn > 1 &&
                                                  osn - prevOsn < u64(L.seqSize) - 64)) &&
                          osn - L.h.seqExtHighestSN < u64(L.seqSize) - 64;
+      // A late lane the run may settle (below, once the run's extent is known):
+      // what its full step would read is the state at its own position, and a
+      // forward writes a past sequencer slot and nothing else.  Not one that
+      // switches the source, carries no payload, would raise the sequencer's
+      // highest timestamp, or needs the sequencer's RangeMap.
+      const bool lateOk = LKF_OOO_RUN && late && !lateBad && p.plen != 0 && p.ssrc == L.h.lastSSRC &&
+                          (fl & F_SEQ_INIT) && (fl & F_STATS_INIT) && !(fl & F_SEQ_RM) && ots <= hiTS;
       const bool bad =
-          inWin && ((cls == -2) || (cls == -1 && !ok) || (fwdIn && !seqOk));
+          inWin && ((cls == -2) || (cls == -1 && !ok && !lateOk) || (fwdIn && !seqOk));
       const u64 stopM = __ballot(bad || (valid && lane >= pos && !inWin));
       x = stopM ? u32(__ffsll((long long)stopM) - 1) : n;
       if (tswM & ~((1ull << pos) - 1)) x = min(x, u32(__ffsll((long long)(tswM & ~((1ull << pos) - 1))) - 1) + 1u);
       // ---- decide lanes [pos, x) together
       if (x > pos) {
-        const u64 runM = (x >= 64 ? ~0ull : ((1ull << x) - 1)) & ~((1ull << pos) - 1);
-        const bool inRun = (runM >> lane) & 1;
-        const u64 tdR = tdM & runM;
-        fwd = fwd && inRun;
-        const u64 fwR = __ballot(fwd);             // every forwarded lane (output order)
-        const u64 fwInR = fwR;                     // in-order pushes (every forward)
-        const u64 selR = tdR | fwInR;              // lanes that advance the munger
-        o.nTuples += x - pos;
-        // the run's drops: the classification's no-state-change reasons + temporal filter
-        o.drops[LKF_DROP_MUTED] += u32(__popcll(__ballot(inRun && cls == LKF_DROP_MUTED)));
-        o.drops[LKF_DROP_PAUSED] += u32(__popcll(__ballot(inRun && cls == LKF_DROP_PAUSED)));
-        o.drops[LKF_DROP_NOT_SELECTED] += u32(__popcll(__ballot(inRun && cls == LKF_DROP_NOT_SELECTED)));
-        o.drops[LKF_DROP_DOWNGRADE] += u32(__popcll(__ballot(inRun && cls == LKF_DROP_DOWNGRADE)));
-        o.drops[LKF_DROP_TEMPORAL] += u32(__popcll(tdR));
-        // Gap lanes (forwarded after a loss) and picture drops, in lane order:
-        // the missing pictures a gap records skip the pictures dropped so far
-        // (vp8.go:218-247), a gap exempts its own picture (:249-255), and the
-        // sequencer slots it skips are invalidated (sequencer.go:179-189).
-        // Sequencer slots are the run-start highest slot + (osn - highest SN).
-        const u64 pdR = video ? __ballot(picDrop && inRun) : 0ull;
-        const u64 gR = __ballot(gapLane && inRun);
-        if (gR) {
-          for (u64 m = gR | pdR; m; m &= m - 1) {
+        u64 runM = (x >= 64 ? ~0ull : ((1ull << x) - 1)) & ~((1ull << pos) - 1);
+        bool inRun = (runM >> lane) & 1;
+        // Gap lanes (forwarded after a loss), picture drops and late lanes, in
+        // lane order: the missing pictures a gap records skip the pictures
+        // dropped so far (vp8.go:218-247), a gap exempts its own picture
+        // (:249-255), and the sequencer slots it skips are invalidated
+        // (sequencer.go:179-189).  Sequencer slots are the run-start highest
+        // slot + (osn - highest SN).
+        u64 pdR = video ? __ballot(picDrop && inRun) : 0ull;
+        u64 gR = __ballot(gapLane && inRun);
+        u64 lateR = LKF_OOO_RUN ? __ballot(late && inRun) : 0ull;
+        const bool ordered = (gR | lateR) != 0;  // (the picture drops go into their set in this loop)
+        if (ordered) {
+          for (u64 m = gR | pdR | lateR; m; m &= m - 1) {
             const u32 b = u32(__ffsll((long long)m) - 1);
             const i32 eb = i32(rl32(u32(ext), b));
             if ((pdR >> b) & 1) {
@@ -3313,6 +3349,83 @@ __global__ void __launch_bounds__(64) DECIDE_ATTR k_decide_dt(DecideArgs A_, con
               set_add(L.dropKey, L.h.dropHead, L.h.dropCount, eb, kDropKeep);
               continue;
             }
+#if LKF_OOO_RUN
+            if ((lateR >> b) & 1) {
+              // The late packet at lane b, as its full step would decide it at
+              // this position (rtpmunger.go:219-243, vp8.go:181-216,
+              // sequencer.go:123-209 into a past slot), wave-uniform.
+              const u64 key = rl64(p.esn, b);
+              const u64 below = (1ull << b) - 1;
+              const u64 tdB = tdM & runM & below;                           // temporal drops in front of it
+              const u64 sameM = __ballot(p.esn == key) & (fwC | tdM | lateR) & runM & below;  // its SN earlier in this run
+              const u64 pfM = fwC & runM & below;                           // in-order pushes in front of it
+              int dr = -1;  // the drop reason, -1 forward, -2 not settled here: the run ends in front of it
+              u64 lsn = 0, lcb = 0;
+              int lcbLen = 0;
+              u16 lpid = 0;
+              if (sameM & ~tdB) {
+                dr = -2;  // (a copy of a lane that shares its sequencer slot)
+              } else if (sameM) {
+                dr = LKF_DROP_OOO_MISS;  // inside the exclusion of a temporal drop of this run
+              } else {
+                // RangeMap.GetValue at this position, for a key in the run-start
+                // open range: the exclusions of the temporal drops in front each
+                // closed a range with the offset so far.  (A key in a closed
+                // range needs the ring, rm_load and what those exclusions
+                // pruned, rangemap.go:171: the full step.)
+                if (key < L.h.rmOpenStart) dr = -2;
+                if (dr == -1) {
+                  lsn = key - (L.h.rmOpenValue + u64(__popcll(__ballot(((tdB >> lane) & 1) && p.esn < key))));
+                  const u64 lastF = pfM ? rl64(osn, 63 - __clzll(pfM)) : 0ull;
+                  const u64 lastSN = pfM ? lastF : L.h.extLastSN, seqHi = pfM ? lastF : L.h.seqExtHighestSN;
+                  // the run's furthest push (its gap lanes' invalidated slots lie below it): a
+                  // slot a ring or more behind it is one this run pushes into or invalidates,
+                  // before or after this lane, or one the full step would not store at all
+                  const u64 fwRun = fwC & runM;
+                  const u64 reach = fwRun ? rl64(osn, 63 - __clzll(fwRun)) : L.h.seqExtHighestSN;
+                  if (lsn >= lastSN)
+                    dr = LKF_DROP_OOO_MISS;
+                  else if (lsn < L.h.seqExtStartSN || i64(lsn - seqHi) >= 0 || i64(lsn - reach) <= -i64(L.seqSize))
+                    dr = -2;  // (not a past slot of the ring clear of this run's pushes)
+                }
+                if (dr == -1 && video) {  // VP8.UpdateAndGet out of order: the picture's recorded offset
+                  const int idx = miss_find(L, eb);
+                  if (idx < 0) {
+                    dr = LKF_DROP_PICID_MISS;
+                  } else {
+                    const u32 vb = rl32(u32(p.vbits), b);
+                    lpid = u16((eb - L.missVal[idx]) & 0x7fff);
+                    const bool lM = lpid > 127, oM = vb & LKF_VP8_M;
+                    const int hs = int(rl32(u32(p.vhs), b)) + (lM == oM ? 0 : (lM ? 1 : -1));
+                    lcbLen = vp8_marshal(u8(rl32(u32(p.vfirst), b)), vb & LKF_VP8_I, lM, lpid, vb & LKF_VP8_L,
+                                         u8(rl32(u32(p.tl0), b) - L.h.tl0Off), vb & LKF_VP8_T, u8(rl32(u32(p.tid), b)),
+                                         vb & LKF_VP8_Y, vb & LKF_VP8_K, u8(rl32(u32(p.keyidx), b) - L.h.keyIdxOff),
+                                         hs, lcb);
+                    if (lcbLen < 0) dr = LKF_DROP_OTHER;
+                  }
+                }
+              }
+#if LKF_SVC_STATS
+              if (lane == 0) SVC_ADD(dr == -2 ? 54 : dr == -1 ? 52 : 53, 1ull);
+#endif
+              if (dr == -2) {  // the run ends in front of lane b: its full step
+                x = b;
+                runM &= below;
+                break;
+              }
+              o.drops[LKF_DROP_OOO_MISS] += dr == LKF_DROP_OOO_MISS ? 1u : 0u;
+              o.drops[LKF_DROP_PICID_MISS] += dr == LKF_DROP_PICID_MISS ? 1u : 0u;
+              o.drops[LKF_DROP_OTHER] += dr == LKF_DROP_OTHER ? 1u : 0u;
+              if (dr == -1 && lane == b) {
+                fwd = true;
+                osn = lsn;
+                cb = lcb;
+                cbLen = lcbLen;
+                mpid = lpid;
+              }
+              continue;
+            }
+#endif
             if (video) {
               vp8_record_missing(L, i32(rl32(u32(prevExt), b)), eb, i32(rl32(u32(picOff), b)));
               if (rl32(u32(overT), b)) {
@@ -3329,7 +3442,26 @@ __global__ void __launch_bounds__(64) DECIDE_ATTR k_decide_dt(DecideArgs A_, con
               store_rec(L.seq + x2, SeqMeta{});
             }
           }
+          if (lateR) {
+            inRun = (runM >> lane) & 1;  // (a late lane may have ended the run in front of it)
+            pdR &= runM;
+            gR &= runM;
+            lateR &= runM;
+            vm_drain();  // a late lane's slot may be one that an earlier gap's stores invalidate
+          }
         }
+        const u64 tdR = tdM & runM;
+        fwd = fwd && inRun;  // (with the late lanes the loop above let forward)
+        const u64 fwR = __ballot(fwd);             // every forwarded lane (output order)
+        const u64 fwInR = fwR & ~lateR;            // in-order pushes (a late lane's goes into a past slot)
+        const u64 selR = tdR | fwInR;              // lanes that advance the munger
+        o.nTuples += x - pos;
+        // the run's drops: the classification's no-state-change reasons + temporal filter
+        o.drops[LKF_DROP_MUTED] += u32(__popcll(__ballot(inRun && cls == LKF_DROP_MUTED)));
+        o.drops[LKF_DROP_PAUSED] += u32(__popcll(__ballot(inRun && cls == LKF_DROP_PAUSED)));
+        o.drops[LKF_DROP_NOT_SELECTED] += u32(__popcll(__ballot(inRun && cls == LKF_DROP_NOT_SELECTED)));
+        o.drops[LKF_DROP_DOWNGRADE] += u32(__popcll(__ballot(inRun && cls == LKF_DROP_DOWNGRADE)));
+        o.drops[LKF_DROP_TEMPORAL] += u32(__popcll(tdR));
         // output records + sequencer slots of the forwarded lanes
         const int cc = p.hdr0 & 0xf;
         const bool playout = L.extPlayout && !(fl & F_PLAYOUT_ACKED);
@@ -3353,8 +3485,9 @@ __global__ void __launch_bounds__(64) DECIDE_ATTR k_decide_dt(DecideArgs A_, con
                         (playout ? T_PLAYOUT : 0) | (useCodec ? T_CODEC : 0),
                     0u, useCodec ? vp8_aux(mpid, mtl0, mkey) : 0u);
           // sequencer.push (sequencer.go:123-209): in order, the slot the SN's
-          // distance past the highest
+          // distance past the highest (a late lane's: less than a ring before it)
           u32 slot = u32(L.h.seqHighSlot) + u32(osn - L.h.seqExtHighestSN);
+          if (LKF_OOO_RUN && i32(slot) < 0) slot += L.seqSize;
           while (slot >= L.seqSize) slot -= L.seqSize;
           SeqMeta m = {};
           m.sourceSeqNo = u16(p.esn);
@@ -3452,7 +3585,7 @@ __global__ void __launch_bounds__(64) DECIDE_ATTR k_decide_dt(DecideArgs A_, con
             }
             u64 pd = pdR;
             L.h.pictureIdOffset += i32(__popcll(pd));
-            while (pd && !gR) {  // (with gap lanes the drops went into the set in lane order above)
+            while (pd && !ordered) {  // (with gap or late lanes the drops went into the set in lane order above)
               const u32 b = u32(__ffsll((long long)pd) - 1);
               L.vcDirty = true;
               set_add(L.dropKey, L.h.dropHead, L.h.dropCount, i32(rl32(u32(ext), b)), kDropKeep);
@@ -3463,10 +3596,22 @@ __global__ void __launch_bounds__(64) DECIDE_ATTR k_decide_dt(DecideArgs A_, con
         if (fwR) o.relOff += rl32(relEx + aligned, 63 - __clzll(fwR));
       }
       gapStop = x < n && rl32(u32(gapLater), x) != 0;
+#if LKF_SVC_STATS
+      if (lane == 0) SVC_ADD(48, 1ull);
+      if (x < n)
+        whyStop = rl32((cand && (late || i64(p.esn - prevEsn) < 0) ? 1u : 0u) | (cand && p.esn == prevEsn ? 2u : 0u), x);
+#endif
       }  // (simulcast / audio runs)
       pos = x;
       if (x < n && rl32(pi, x) < nextAt && !gapStop) {
         // the packet at lane x needs the full restatement
+#if LKF_SVC_STATS
+        if (!DDK && lane == 0) {
+          SVC_ADD(49, 1ull);
+          if (whyStop & 1) SVC_ADD(50, 1ull);
+          if (whyStop & 2) SVC_ADD(51, 1ull);
+        }
+#endif
         const uint4 a0 = make_uint4(rl32(r0.x, x), rl32(r0.y, x), rl32(r0.z, x), rl32(r0.w, x));
         const uint4 a1 = make_uint4(rl32(r1.x, x), rl32(r1.y, x), rl32(r1.z, x), rl32(r1.w, x));
         const uint4 a2 = make_uint4(rl32(r2.x, x), rl32(r2.y, x), rl32(r2.z, x), rl32(r2.w, x));
@@ -4961,13 +5106,13 @@ hipError_t launch_dd_decode(hipStream_t s, const RunDesc *desc, const uint32_t *
 // ---------------------------------------------------------------------------
 static u32 nblk(u64 n, u32 t) { return u32((n + t - 1) / t); }
 
-hipError_t read_svc_stats(unsigned long long out[48], int reset) {
+hipError_t read_svc_stats(unsigned long long out[64], int reset) {
 #if LKF_SVC_STATS
-  static unsigned long long v[64 * 48];
+  static unsigned long long v[64 * 64];
   hipError_t r = hipMemcpyFromSymbol(v, HIP_SYMBOL(g_svc), sizeof(v));
-  for (int k = 0; k < 48; k++) {
+  for (int k = 0; k < 64; k++) {
     out[k] = 0;
-    for (int c = 0; c < 64; c++) out[k] += v[c * 48 + k];
+    for (int c = 0; c < 64; c++) out[k] += v[c * 64 + k];
   }
   if (r == hipSuccess && reset) {
     for (auto &x : v) x = 0;
@@ -4975,7 +5120,7 @@ hipError_t read_svc_stats(unsigned long long out[48], int reset) {
   }
   return r;
 #else
-  for (int i = 0; i < 48; i++) out[i] = 0;
+  for (int i = 0; i < 64; i++) out[i] = 0;
   (void)reset;
   return hipErrorNotSupported;
 #endif

@@ -1,9 +1,13 @@
 """Diagnostic: where the SVC runs of k_decide_dt<true> stop on configs[4]
 (needs the LKF_SVC_STATS build: make -C livekit-server_amd/csrc ab
 ABNAME=svcst ABFLAGS=-DLKF_SVC_STATS=1, run with LKF_LIB=liblkfwd_svcst.so).
-Prints the counters per batch (forwarding path, ExtPackets)."""
+Prints the counters per batch (forwarding path, ExtPackets).  For the plain
+DownTracks of k_decide_dt<false> it also prints the run iterations and the
+full steps by cause (one OOO_RUN_COUNTS JSON line per batch; the headline's
+batches: `svc_stats.py 100 -1 2 1.0 3.0`, with and without -DLKF_OOO_RUN=0)."""
 import ctypes as C
 import importlib
+import json
 import os
 import sys
 import time
@@ -30,7 +34,7 @@ def main():
     fn = eng.lib.lkf_debug_svc_stats
     fn.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.c_int]
     fn.restype = C.c_int
-    out = (C.c_uint64 * 48)()
+    out = (C.c_uint64 * 64)()
     fn(eng.h, out, 1)
     for b in range(tr.nbatches):
         workload.queue_events(eng.api, eng.h, tr, b)
@@ -65,6 +69,16 @@ def main():
                                                  [v[36], v[37] / v[36]]), flush=True)
             print("      body: to the first chunk's packets %.2f, RTPStatsSender folds %.2f" %
                   (v[38] / v[36] / 1000.0, v[39] / v[36] / 1000.0), flush=True)
+            # the plain DownTracks' runs: a late tuple is a (packet, DownTrack) pair whose packet
+            # lies behind the highest SN its DownTrack's munger has reached
+            late = v[50] + v[52] + v[53]
+            print("      runs: %d iterations, %d full steps (%d of a late packet, %d of a copy of the highest SN); "
+                  "late tuples %d: %d forwarded in a run, %d dropped in a run, %d of those full steps handed "
+                  "back by a run" % (v[48], v[49], v[50], v[51], late, v[52], v[53], v[54]), flush=True)
+            print("OOO_RUN_COUNTS " + json.dumps(dict(
+                batch=b, packets=n, downtracks=v[36], run_iterations=v[48], full_steps=v[49],
+                full_steps_late=v[50], full_steps_copy_of_highest=v[51], late_tuples=late,
+                late_forwarded_in_run=v[52], late_dropped_in_run=v[53], late_handed_back=v[54])), flush=True)
     tr.close()
 
 
